@@ -17,15 +17,21 @@ the device, verify, verdicts left in HBM; plus (N > 1) the RCCL all-gather of th
 vectors, the engine's only collective. `value` = signatures of all ranks / max-over-ranks time.
 The same shard through the host form (cg_verify_tx_signatures_packed: host arena -> host verdicts,
 the key-use count pass, ~85 B per signature over PCIe, D2H of the verdicts) is timed right after
-it on every rank and reported as summary.host_to_host (--headline host makes it the timed form).
+it on every rank with --full and reported as summary.host_to_host (--headline host makes it the
+timed form).
 
 Launch: ``python bench.py`` (N = 1), ``python bench.py --gpus N`` (this process checks that N
 devices are visible and starts ``torch.distributed.run --nproc-per-node N`` as a child before
 anything touches the GPU, then exits with its code) or ``torchrun --nproc-per-node N bench.py
 --gpus N`` (the driver's form); one process per GPU, each verifying its own shard (weak scaling).
-Rank 0 prints ONE compact JSON line (<= 4 KB, the last line on stdout): the headline, `roofline`
-and a `cpu_baseline` summary. Everything else (secondary legs, per-stage maps, the full CPU
-baseline) goes to --secondary-out (default gpurun_out/bench_secondary.json) and to stderr.
+Rank 0 prints ONE compact JSON line (<= 4 KB, the last line on stdout): the headline and `roofline`.
+
+A plain run does only what the headline needs: it generates the shard, warms up, times --steps
+steps, checks the last step's verdicts against the workload's labels, writes them with
+--dump-outputs DIR (DIR/verdicts.npy) and prints the line (`cpu_baseline` null, `roofline` priced
+from the stage events of the timed steps themselves). --full adds every other measurement (the
+host form, two contexts, `cpu_baseline` and `secondary` below), all after the timed steps; their
+JSON (per-stage maps, the full CPU baseline) goes to --secondary-out and to stderr.
   roofline      the dominant kernel (k_ed_ladder_wide: the shard's keys have wide tables; else
                 k_ed_ladder_pf), priced in the 32x32->64 multiply-accumulates
                 its lane code executes (host-counted) over its per-launch time from HIP events
@@ -115,6 +121,9 @@ TRAFFIC_FILE = os.path.join(ROOT, "profiles", "r06", "pmc_traffic.json")
 # Appendix A labels (tools/workload) -> the verdict Crypto.doVerify gives them (key decodes)
 ED_LABEL_EXPECT = {0: 0, 1: 1, 2: 1, 3: 1, 4: 0, 6: 1, 7: 2}       # A5 (high S) depends on slide()
 EC_LABEL_EXPECT = {0: 0, 1: 1, 2: 0, 3: 1, 6: 2, 7: 2}  # E5 (pad byte) is minimal when r >= 2^255
+# --dump-outputs: the whole verdict vector up to 15M signatures (60 MB of float32), else a sample
+# of 2^22 with its positions (16 + 32 MiB)
+DUMP_FULL_MAX, DUMP_SAMPLE = 15_000_000, 1 << 22
 
 
 def parse(argv=None):
@@ -132,6 +141,16 @@ def parse(argv=None):
     ap.add_argument("--msg-len", type=int, default=270)
     ap.add_argument("--chunk-items", type=int, default=0, help="device chunk (0: CG_DEFAULT_CHUNK_ITEMS = 8M)")
     ap.add_argument("--seed", type=int, default=20251015)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run everything beside the headline: the host arena -> host "
+                         "verdicts form, two contexts, the CPU baselines, the device-resident / message-form / "
+                         "key-distribution legs and the other BASELINE configs, written to --secondary-out. Off: "
+                         "none of them runs, whatever their own options say")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the timed call returned in its last timed step to DIR/verdicts.npy: rank 0's "
+                         "verdict vector (one float32 per signature, 0 = valid; cordagpu.h status codes). Above "
+                         f"{DUMP_FULL_MAX} signatures a seeded sample of {DUMP_SAMPLE}, its positions in "
+                         "DIR/verdicts_index.npy (float64), so a dump stays under 64 MB")
     ap.add_argument("--sigs-per-tx", type=int, default=5,
                     help="signatures per transaction id (GeneratedLedger: 1+Poisson(3) signers + the notary)")
     ap.add_argument("--device-steps", type=int, default=4, help="device-resident secondary calls (0: off)")
@@ -437,6 +456,17 @@ def check_verdicts(st, exp):
     return {"counts": {str(int(k)): int(v) for k, v in zip(*np.unique(st, return_counts=True))},
             "checked_vs_labels": int(m.sum()), "label_mismatches": bad,
             "not_run": int(np.count_nonzero(st == 255))}
+
+
+def dump_outputs(path, st, seed):
+    """--dump-outputs: the verdict vector the timed call left in its last step, as float32 (every
+    status code is exact); a vector longer than DUMP_FULL_MAX is sampled at seeded, sorted positions."""
+    os.makedirs(path, exist_ok=True)
+    if st.size > DUMP_FULL_MAX:
+        pos = np.sort(np.random.default_rng(seed).choice(st.size, DUMP_SAMPLE, replace=False))
+        np.save(os.path.join(path, "verdicts_index.npy"), pos.astype(np.float64))
+        st = st[pos]
+    np.save(os.path.join(path, "verdicts.npy"), st.astype(np.float32))
 
 
 # ------------------------------------------------------------------------------------ CPU legs
@@ -975,6 +1005,8 @@ def main_pool(a):
             st = call()
         el = (time.perf_counter() - t) / a.steps
         stats = dict(ep.last_stats)
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, st, a.seed)
     ver = check_verdicts(st, expected_verdicts(pl[idx], ps[idx]))
     line = {"metric": METRIC, "value": round(n / el, 1), "unit": "sigs/s", "n_gpus": len(set(devices)),
             "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(el * 1e3, 3), "higher_is_better": True,
@@ -1026,7 +1058,9 @@ def main(argv=None):
                                                      sig_group=a.sigs_per_tx)
     ids, id_idx = wl.pool_ids(pool, len(signable.template(1, 4)[0]))
     draws = wl.tx_ordered_draws(pool.n, a.items, id_idx, seed=a.seed + 31 * rank + 1)
-    batch, idx = wl.index_stream(pool, a.items, replicate=True, idx=draws)
+    # `batch` (every SignableData materialised, ~370 B per item) feeds --full's message-form and CPU
+    # legs; a plain run reads only its item and key tables, so it leaves the bytes in the pool's arena
+    batch, idx = wl.index_stream(pool, a.items, replicate=a.full, idx=draws)
     tb = wl.tx_sig_stream(pool, pool_schemes, idx, ids, id_idx, nthreads=threads)
     labels, schemes = pool_labels[idx], pool_schemes[idx]
     gen_s = time.time() - t0
@@ -1143,7 +1177,7 @@ def main(argv=None):
             el = float(tt.item())
         return el, all_stage_times(), cg
 
-    h2h_steps = a.steps if a.h2h_steps < 0 else a.h2h_steps
+    h2h_steps = (a.steps if a.h2h_steps < 0 else a.h2h_steps) if a.full else 0
     h2h = None
     if a.headline == "device":
         elapsed, stages, _ = timed(device_step, a.steps, a.warmup, False)
@@ -1151,7 +1185,7 @@ def main(argv=None):
         for other in dbuf["sts"][1:]:  # every context's last verdicts agree
             if not np.array_equal(other.cpu().numpy(), st):
                 st = np.full_like(st, 255)
-        c2_steps = a.steps if a.ctx2_steps < 0 else a.ctx2_steps
+        c2_steps = (a.steps if a.ctx2_steps < 0 else a.ctx2_steps) if a.full else 0
         if len(engs) == 1 and c2_steps > 0:
             # two verifier contexts on the device, calls alternating (each on its own stream): a call's
             # key-table phase runs beside the other call's ladders. Reported, not the headline: the
@@ -1183,6 +1217,8 @@ def main(argv=None):
         elapsed, stages, cg_ms = timed(host_step, a.steps, a.warmup, True)
         el_h, h2h_steps = elapsed, a.steps
         st = holder["st_host"]
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, st, a.seed)
 
     # ---- verdict checks: labels, and every draw of a pool item gets that item's verdict
     ver = check_verdicts(st, expected_verdicts(labels, schemes))
@@ -1223,12 +1259,13 @@ def main(argv=None):
                                  for k in ("ms_key_prep", "ms_h2d", "ms_verify", "ms_d2h", "ms_total")},
             "note": "the host arena -> host verdicts calls: ms_key_prep = host-side planning (the key-use "
                     "count pass), ms_h2d = until the first chunk's bytes are resident, ms_verify = the rest"}
-    extra["table_modes_items"] = table_modes(batch, schemes)
+    if a.full:
+        extra["table_modes_items"] = table_modes(batch, schemes)
     extra["host"] = {"threads": threads, "engine_host_threads": eng_threads or "library budget",
                      "registered_bytes": int(sum(x.nbytes for x in registered)), "host_register": a.host_register,
                      "anon_huge_pages_kB": anon_huge_kb()}
     cpu = None
-    if rank == 0 and world == 1:
+    if rank == 0 and world == 1 and a.full:
         if a.device_steps > 0:
             guarded(extra, "device_resident", lambda: bench_device(eng, dev, stream, batch, tb, st, a.device_steps))
         if a.host_steps > 0:
@@ -1267,8 +1304,9 @@ def main(argv=None):
                                    "Ed25519 / 20% secp256r1 / 10% secp256k1, one "
                                    + ("cg_verify_tx_signatures_packed" if pb is not None else "cg_verify_tx_signatures")
                                    + ("_device call per step, inputs resident in HBM when the timed region starts "
-                                      "(keys, ids, signature table and stream, templates; verdicts left in HBM); "
-                                      "host arena -> host verdicts (PCIe-inclusive) in summary.host_to_host"
+                                      "(keys, ids, signature table and stream, templates; verdicts left in HBM)"
+                                      + ("; host arena -> host verdicts (PCIe-inclusive) in summary.host_to_host"
+                                         if h2h is not None else "")
                                       if a.headline == "device" else
                                       " call per step, host arena -> host verdicts (PCIe-inclusive)")
                                    + " (batch Crypto.doVerify(txId, sig))",
@@ -1280,7 +1318,7 @@ def main(argv=None):
         }
         summary = {"verdicts_checked": ver["checked_vs_labels"], "label_mismatches": ver["label_mismatches"],
                    "not_run": ver["not_run"], "draws_consistent": ver["draws_consistent"],
-                   "secondary_file": os.path.relpath(a.secondary_out, ROOT) if a.secondary_out else None}
+                   "secondary_file": os.path.relpath(a.secondary_out, ROOT) if a.full and a.secondary_out else None}
         if holder.get("ctx2"):
             summary["two_contexts"] = holder["ctx2"]["value"]
             summary["two_contexts_equal"] = holder["ctx2"]["verdicts_equal"]
@@ -1298,7 +1336,8 @@ def main(argv=None):
                     v = v.get("tx_signatures", {})
                 summary[k] = v.get("value", v.get("error", "")[:80] if "error" in v else None)
         extra["cpu_baseline_full"] = cpu
-        write_secondary(a.secondary_out, extra)
+        if a.full:
+            write_secondary(a.secondary_out, extra)
         print(compact_line(head, roof, cpu, summary), flush=True)
     if world > 1:
         dist.destroy_process_group()

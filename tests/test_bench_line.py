@@ -91,6 +91,35 @@ def test_gpus_request_exceeding_devices_fails_before_gpu():
     assert "only 0 device" in r.stderr
 
 
+def test_plain_run_is_the_default_and_full_is_an_option():
+    """A plain run times the headline only; the host form, two contexts, the CPU baselines and the
+    secondary legs sit behind --full (their own options keep their defaults for it)."""
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "3"])
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, "", 7, 3)
+    f = bench.parse(["--full", "--dump-outputs", "d"])
+    assert f.full and f.dump_outputs == "d" and f.device_steps > 0 and not f.no_cpu_baseline
+
+
+def test_dump_outputs(tmp_path, monkeypatch):
+    """--dump-outputs: the verdict vector as float32, whole when it fits; else the same seeded,
+    sorted sample on every run, with its positions."""
+    import numpy as np
+    assert 4 * bench.DUMP_FULL_MAX <= 64e6 and (4 + 8) * bench.DUMP_SAMPLE <= 64e6  # under 64 MB either way
+    st = (np.arange(1000) % 3).astype(np.uint8)
+    bench.dump_outputs(str(tmp_path / "a"), st, 5)
+    got = np.load(tmp_path / "a" / "verdicts.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, st) and not (tmp_path / "a" / "verdicts_index.npy").exists()
+    monkeypatch.setattr(bench, "DUMP_FULL_MAX", 100)
+    monkeypatch.setattr(bench, "DUMP_SAMPLE", 64)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), st, 5)
+    pos = np.load(tmp_path / "b" / "verdicts_index.npy")
+    assert pos.dtype == np.float64 and pos.size == 64 and np.all(np.diff(pos) > 0)
+    assert np.array_equal(np.load(tmp_path / "b" / "verdicts.npy"), st[pos.astype(np.int64)])
+    for name in ("verdicts.npy", "verdicts_index.npy"):
+        assert np.array_equal(np.load(tmp_path / "b" / name), np.load(tmp_path / "c" / name))
+
+
 def test_headline_is_device_resident_by_default():
     """The timed form is the device-resident call (inputs in HBM when the timed region starts); the
     host arena -> host verdicts form is timed beside it (summary.host_to_host), or timed itself with

@@ -8,7 +8,7 @@ export TMPDIR=/tmp
 TAG=$1; ROUNDS=$2; shift 2
 OUT=gpurun_out/ab_$TAG
 mkdir -p $OUT
-B="python3 -u bench.py --steps 5 --warmup 2 --device-steps 0 --host-steps 0 --key-dists= --configs1-items 0 --ecdsa-items 0 --pipeline-txs 0 --tear-offs 0 --configs0-txs 0 --no-cpu-baseline"
+B="python3 -u bench.py --full --steps 5 --warmup 2 --device-steps 0 --host-steps 0 --key-dists= --configs1-items 0 --ecdsa-items 0 --pipeline-txs 0 --tear-offs 0 --configs0-txs 0 --no-cpu-baseline"
 summ() {
   python3 - "$1" "$2" <<'PY'
 import json, sys

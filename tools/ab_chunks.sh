@@ -7,7 +7,7 @@ TAG=$1; shift
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
 for ch in "$@"; do
-  timeout -k 10 300 python -u bench.py --steps 5 --warmup 2 --chunk-items $ch --device-steps 0 --host-steps 0 \
+  timeout -k 10 300 python -u bench.py --full --steps 5 --warmup 2 --chunk-items $ch --device-steps 0 --host-steps 0 \
     --key-dists '' --configs1-items 0 --ecdsa-items 0 --pipeline-txs 0 --tear-offs 0 --configs0-txs 0 \
     --no-cpu-baseline > $OUT/chunk_$ch.log 2>&1 || { echo FAIL $ch; tail -20 $OUT/chunk_$ch.log; exit 1; }
   python - $OUT/chunk_$ch.log $ch <<'PY'

@@ -6,7 +6,7 @@ set -o pipefail
 TAG=$1; shift
 OUT=gpurun_out/ab_$TAG
 mkdir -p $OUT
-B="python3 bench.py --steps 6 --warmup 2 --no-cpu-baseline --host-steps 0 --configs1-items 0 --ecdsa-items 0 --pipeline-txs 0 --tear-offs 0 --configs0-txs 0"
+B="python3 bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --host-steps 0 --configs1-items 0 --ecdsa-items 0 --pipeline-txs 0 --tear-offs 0 --configs0-txs 0"
 for round in 1 2; do
   i=0
   for v in "$@"; do

@@ -9,7 +9,7 @@ mkdir -p $OUT
 for kv in "$@"; do
   name=$(echo "$kv" | tr '=' '_')
   if [ "$kv" = "-" ]; then E=""; else E=$(echo "$kv" | tr '+' ' '); fi
-  env $E timeout -k 10 300 python -u bench.py --steps 5 --warmup 2 --device-steps 0 --host-steps 0 \
+  env $E timeout -k 10 300 python -u bench.py --full --steps 5 --warmup 2 --device-steps 0 --host-steps 0 \
     --key-dists '' --configs1-items 0 --ecdsa-items 0 --pipeline-txs 0 --tear-offs 0 --configs0-txs 0 \
     --no-cpu-baseline --secondary-out $OUT/h_${name}_sec.json > $OUT/h_$name.log 2> $OUT/h_$name.err || { echo FAIL $kv; tail -20 $OUT/h_$name.err; exit 1; }
   python - $OUT/h_$name.log "$kv" <<'PY'

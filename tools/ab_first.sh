@@ -7,7 +7,7 @@ TAG=$1; shift
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
 for dv in "$@"; do
-  CG_TXSIG_FIRST_DIV=$dv timeout -k 10 300 python -u bench.py --steps 5 --warmup 2 --device-steps 0 --host-steps 0 \
+  CG_TXSIG_FIRST_DIV=$dv timeout -k 10 300 python -u bench.py --full --steps 5 --warmup 2 --device-steps 0 --host-steps 0 \
     --key-dists '' --configs1-items 0 --ecdsa-items 0 --pipeline-txs 0 --tear-offs 0 --configs0-txs 0 \
     --no-cpu-baseline > $OUT/first_$dv.log 2>&1 || { echo FAIL $dv; tail -20 $OUT/first_$dv.log; exit 1; }
   python - $OUT/first_$dv.log $dv <<'PY'

@@ -7,7 +7,7 @@ export TMPDIR=/tmp
 TAG=$1; R=$2; LIBS=$3; ENVS=$4
 OUT=gpurun_out/p1_$TAG
 mkdir -p $OUT
-B="python3 -u bench.py --steps 5 --warmup 2 --device-steps 0 --host-steps 0 --key-dists= --configs1-items 0 --ecdsa-items 0 --pipeline-txs 0 --tear-offs 0 --configs0-txs 0 --no-cpu-baseline"
+B="python3 -u bench.py --full --steps 5 --warmup 2 --device-steps 0 --host-steps 0 --key-dists= --configs1-items 0 --ecdsa-items 0 --pipeline-txs 0 --tear-offs 0 --configs0-txs 0 --no-cpu-baseline"
 for r in $(seq 1 $R); do
   for lib in $LIBS; do
     for kv in $ENVS; do

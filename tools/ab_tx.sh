@@ -6,7 +6,7 @@ set -o pipefail
 export TMPDIR=/tmp
 OUT=$1; shift
 mkdir -p $OUT
-B="python3 bench.py --steps 1 --warmup 1 --items 262144 --pool 65536 --no-cpu-baseline --device-steps 0 --host-steps 0 --key-dists= --configs1-items 0 --ecdsa-items 0 --tear-offs 0 --configs0-txs 0"
+B="python3 bench.py --full --steps 1 --warmup 1 --items 262144 --pool 65536 --no-cpu-baseline --device-steps 0 --host-steps 0 --key-dists= --configs1-items 0 --ecdsa-items 0 --tear-offs 0 --configs0-txs 0"
 for v in base "$@"; do
   if [ "$v" = base ]; then L=""; else L="tools/variants/$v.so"; fi
   mkdir -p $OUT/$v

@@ -11,7 +11,8 @@ export TMPDIR=/tmp
 TAG=$1; ROUNDS=${2:-2}
 OUT=gpurun_out/host8_$TAG
 mkdir -p $OUT
-B="python3 -u bench.py --steps 5 --warmup 2 --threads 2 --engine-threads 2 --device-steps 0 --host-steps 0 --key-dists= --configs1-items 0 --ecdsa-items 0 --pipeline-txs 0 --tear-offs 0 --configs0-txs 0 --no-cpu-baseline"
+[ -x tools/host8/stage_load ] || cc -O2 -pthread tools/host8/stage_load.c -o tools/host8/stage_load || exit 1
+B="python3 -u bench.py --full --steps 5 --warmup 2 --threads 2 --engine-threads 2 --device-steps 0 --host-steps 0 --key-dists= --configs1-items 0 --ecdsa-items 0 --pipeline-txs 0 --tear-offs 0 --configs0-txs 0 --no-cpu-baseline"
 run() {  # name, loaders (0 none / copy / read), bench args
   local name=$1 load=$2; shift 2
   local pids=()
