@@ -245,10 +245,15 @@ class TxSigBatch:
             arena = self.arena[:start]
         else:
             stream = np.zeros(total, np.uint8)
-            src = self.sigs["sig_off"].astype(np.int64)
+            src = self.sigs["sig_off"]
             for j in range(n):
-                ln = int(self.sigs["sig_len"][j])
-                stream[int(rel[j]):int(rel[j]) + ln] = self.arena[src[j]:src[j] + ln]
+                ln, o = int(self.sigs["sig_len"][j]), int(src[j])
+                if o > self.arena.size or ln > self.arena.size - o:
+                    # bytes outside the arena: CG_NOT_RUN in the 24-byte form. The stream has no offset
+                    # to say so; an id index no table has gives the same status (include/cordagpu.h)
+                    sig12["tx_idx"][j] = 0xFFFFFFFF
+                    continue
+                stream[int(rel[j]):int(rel[j]) + ln] = self.arena[o:o + ln]
             arena = self.arena
         return PackedTxSigBatch(self.keys, self.ids, sig12, stream, self.tmpls, arena)
 

@@ -245,7 +245,9 @@ int cg_host_register_advised(uint32_t contexts_per_node);
  * messages) copying on a copy stream while chunk k verifies. Only the arena window the keys and
  * items reference is copied. Best throughput when the caller appends (sig, clear) per item in item
  * order after the keys (the layout corda_amd/batch.py and INTEGRATION.md use); any layout is
- * correct. Lengths: sig_len and cg_key.len are 16-bit; a JVM signature longer than 65 535 bytes is
+ * correct: no offset (key, signature, message, and in the calls below component, salt, nonce, hash,
+ * root, template) needs any alignment, fields may touch, and the arena may end at the last byte of
+ * the last field with arena_len no multiple of 4. Lengths: sig_len and cg_key.len are 16-bit; a JVM signature longer than 65 535 bytes is
  * packed as a surrogate with the same verdict. stats: ms_h2d = until the
  * first chunk is resident, ms_verify = the rest. On CG_ERR_DEVICE every status byte is
  * CG_NOT_RUN. */
@@ -262,7 +264,13 @@ int cg_verify_batch(cg_ctx* ctx, const cg_key* keys, uint32_t n_keys, const cg_i
  * hardware queue of its own), which waits for the work already on the caller's stream, and the
  * caller's stream waits for the call's end, so the call is ordered on the caller's stream as if it
  * ran there (a stream created elsewhere can share an in-order hardware queue with the context's
- * side streams: round 6, cordagpu.cpp stream_of). */
+ * side streams: round 6, cordagpu.cpp stream_of).
+ * The arena of every *_device form (this one and cg_prepare_keys_device, cg_verify_items_device,
+ * cg_sha256_batch_device, cg_tx_ids_device, cg_verify_transactions_device,
+ * cg_verify_tx_signatures_device, cg_verify_tx_signatures_packed_device, cg_verify_filtered_device):
+ * d_arena itself must be 4-byte aligned and readable up to arena_len rounded up to a multiple of 4
+ * (the kernels read aligned dwords; what the up to 3 bytes past arena_len hold never matters). The
+ * offsets inside it need no alignment, as in the host forms, which provide both themselves. */
 int cg_reserve(cg_ctx* ctx, uint32_t max_keys, uint64_t max_items);
 int cg_verify_batch_device(cg_ctx* ctx, const cg_key* d_keys, uint32_t n_keys, const cg_item* d_items,
                            uint64_t n_items, const uint8_t* d_arena, uint64_t arena_len, uint32_t mode,

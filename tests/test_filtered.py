@@ -137,12 +137,12 @@ def test_filtered_fixture_gpu(engine):
     assert len(bad) == 0, [(items[i]["cls"], int(st[i]), int(want[i])) for i in bad[:10]]
 
 
-@pytest.mark.gpu
-def test_filtered_random_vs_oracle(engine):
-    """Seeded tear-offs of random transactions (1-40 components, every corruption class)."""
-    rng = random.Random(77)
+def random_tearoffs(count, seed=77):
+    """``count`` seeded tear-offs of random transactions (1-40 components, every corruption class)
+    and the oracle's status for each (also the input of tests/test_gpu_layout.py)."""
+    rng = random.Random(seed)
     ftxs, want = [], []
-    for k in range(3000):
+    for k in range(count):
         n = rng.randrange(1, 40)
         blobs = [rng.randbytes(rng.randrange(0, 300)) for _ in range(n)]
         salt = rng.randbytes(32)
@@ -165,8 +165,14 @@ def test_filtered_random_vs_oracle(engine):
         want.append(C.filtered_status(root, leaves, pt))
         ftxs.append(M.FilteredTransaction(root, [b for b, _ in leaves], [x for _, x in leaves],
                                           _PostOrder(C.partial_tree_postorder(pt))))
+    return ftxs, np.array(want, dtype=np.uint8)
+
+
+@pytest.mark.gpu
+def test_filtered_random_vs_oracle(engine):
+    """Seeded tear-offs of random transactions (1-40 components, every corruption class)."""
+    ftxs, want = random_tearoffs(3000)
     st = M.verify_filtered_batch(ftxs, engine)
-    want = np.array(want, dtype=np.uint8)
     assert np.array_equal(st, want), np.nonzero(st != want)[0][:10]
     assert set(np.unique(want).tolist()) == {0, 1, 2}
 

@@ -402,6 +402,17 @@ def test_packed_edges():
         assert np.any(st[pb.sigs["key_idx"] == 1] != want[pb.sigs["key_idx"] == 1])
         empty = B.PackedTxSigBatch(pb.keys, pb.ids, pb.sigs[:0], pb.stream[:0], pb.tmpls, pb.arena)
         assert eng.verify_tx_signatures_packed(empty).size == 0
+        # a signature that runs one byte past an arena with no slack behind it (layout_util.relayout_txsig
+        # ends the arena at the last signature's last byte): NOT_RUN in the 24-byte form, and the packed
+        # mirror (TxSigBatch.packed) degrades the same way instead of raising; every other verdict stays
+        import layout_util
+        r = layout_util.relayout_txsig(tb, 5, rem=1, last="sig")
+        j = int(np.flatnonzero(r.sigs["sig_off"] + r.sigs["sig_len"] == r.arena.size)[0])
+        r.sigs["sig_len"][j] += 1
+        want_r = eng.verify_tx_signatures(r)
+        assert want_r[j] == B.NOT_RUN
+        assert np.array_equal(np.delete(want_r, j), np.delete(eng.verify_tx_signatures(tb), j))
+        assert np.array_equal(eng.verify_tx_signatures_packed(r.packed()), want_r)
 
 
 def test_packed_8m_one_call(spool):

@@ -152,6 +152,37 @@ def test_sha_lane_code():
             assert o8.astype(">u4").tobytes() == c_oracle.sha256(msg + sfx)
 
 
+def test_sha_lane_code_poisoned_exact_end():
+    """test_sha_lane_code's two entry points on the layout a JVM writer appending to a direct buffer
+    produces: 0xFF in front of the message (the bytes an unaligned message shares its first dword
+    with), the buffer ending at the message's last byte rounded up to 4 (t_sha512_prefix /
+    t_sha256_suffix pass exactly that as the readable length) and 0xFF in that rounded tail, which a
+    word that fails to mask the bytes behind the message would hash. Lengths at the padding and
+    block edges of both hashes, every byte phase, against hashlib."""
+    import ctypes
+    import hashlib
+    lib = hostk.lib()
+    rng = np.random.default_rng(8)
+    out = np.zeros(16, dtype=np.uint32)
+    lens = list(range(0, 9)) + [47, 48, 55, 56, 63, 64, 65, 111, 112, 119, 120, 127, 128, 129, 175, 176, 191, 192, 193,
+                               239, 240, 255, 256, 257, 1023, 1024, 1025]
+    for ln in lens:
+        msg = rng.integers(0, 256, ln, dtype=np.uint8).tobytes()
+        pre = rng.integers(0, 256, 64, dtype=np.uint8).tobytes()
+        sfx = rng.integers(0, 256, 32, dtype=np.uint8).tobytes()
+        sw = np.frombuffer(sfx, dtype=">u4").astype(np.uint32)
+        for off in (0, 1, 2, 3, 5, 6, 7):
+            buf = np.full((off + ln + 3) & ~3, 0xFF, dtype=np.uint8)
+            buf[off:off + ln] = np.frombuffer(msg, np.uint8)
+            lib.t_sha512_prefix(ptr(words(pre)), ptr(buf), ctypes.c_uint64(off), ctypes.c_uint64(ln), ptr(out))
+            assert out.tobytes() == hashlib.sha512(pre + msg).digest(), (ln, off)
+            o8 = np.zeros(8, dtype=np.uint32)
+            lib.t_sha256_suffix(ptr(buf), ctypes.c_uint64(off), ctypes.c_uint64(ln), ptr(sw), ptr(o8))
+            assert o8.astype(">u4").tobytes() == hashlib.sha256(msg + sfx).digest(), (ln, off)
+            lib.t_sha256_suffix(ptr(buf), ctypes.c_uint64(off), ctypes.c_uint64(ln), None, ptr(o8))
+            assert o8.astype(">u4").tobytes() == hashlib.sha256(msg).digest(), (ln, off)
+
+
 @pytest.mark.parametrize("w", [4, 6])
 def test_ed25519_row_table_lane_verify_on_fixtures(w):
     """The radix-2^W row-table double-scalar path (k_ed_verify's arithmetic) on the fixtures."""
