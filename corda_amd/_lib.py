@@ -46,6 +46,7 @@ class cg_pool_stats(ctypes.Structure):
 
 ABI_VERSION = 2
 FLAG_STAGE_TIMING = 1
+FLAG_RSA = 2  # CG_FLAG_RSA: RSA_SHA256 items verified on the device
 STAGE_NAMES = ["plan", "ed_hash", "ed_ladder", "ed_ladder_row0", "ed_finish", "r1_front", "r1_ladder",
                "r1_ladder_row0", "k1_front", "k1_ladder", "k1_ladder_row0", "ed_ladder_wide", "r1_ladder_wide",
                "k1_ladder_wide"]
@@ -150,12 +151,21 @@ def lib():
                 L.cg_table_bytes.restype = u64
                 L.cg_table_choice.argtypes = [u64, u64]
                 L.cg_table_choice.restype = u32
+            if hasattr(L, "cg_rsa_key_bits"):  # older builds (A/B variants) lack the RSA path
+                L.cg_rsa_key_bits.argtypes = [ctypes.c_char_p, u32]
+                L.cg_rsa_key_bits.restype = u32
             for name in ("cg_verify_filtered", "cg_verify_filtered_device", "cg_verify_transactions", "cg_verify_transactions_device", "cg_reserve", "cg_verify_batch", "cg_verify_batch_device", "cg_sha256_batch",
                          "cg_sha512_batch", "cg_sha256_batch_device", "cg_merkle_roots", "cg_tx_ids",
                          "cg_tx_ids_device"):
                 getattr(L, name).restype = i32
             _lib = L
         return _lib
+
+
+def rsa_key_bits(spki):
+    """cg_rsa_key_bits: the modulus bit length if an Engine(rsa=True) verifies under this SPKI key, else 0."""
+    spki = bytes(spki)
+    return int(lib().cg_rsa_key_bits(spki, len(spki))) if 0 < len(spki) <= 0xFFFF else 0
 
 
 def host_register(arr):

@@ -13,7 +13,9 @@ Mirrors core/src/main/kotlin/net/corda/core/crypto/Crypto.kt:
     per item (include/cordagpu.h). Ed25519 / ECDSA items run on the GPU. The schemes the GPU
     returns CG_UNSUPPORTED for are NOT errors -- Corda supports them (Crypto.kt:177-184, :891) --
     and are routed to the host, as the Kotlin binding falls back to ``Crypto.isValid``:
-      - RSA_SHA256: corda_amd/hostverify.py;
+      - RSA_SHA256: corda_amd/hostverify.py; when the engine in use was opened with ``rsa=True`` an
+        RSA item with an X.509 key joins the GPU batch first and only what comes back UNSUPPORTED
+        (a key the device decode declines) goes to the host;
       - COMPOSITE: corda_amd/composite.py -- the threshold walk on the host, every leaf signature
         expanded into the same GPU batch (isValid semantics over SignableData(txId, leaf meta));
       - SPHINCS-256: no host verifier in this mirror -> UnsupportedOperationException.
@@ -180,12 +182,17 @@ class _Crypto:
                 return HOST_EXCEPTION, e
             return B.NOT_RUN, None
 
+        gpu_rsa = bool(getattr(self.engine(), "rsa", False))
+
+        def on_gpu(pk):
+            return pk.scheme in GPU_SCHEMES or (gpu_rsa and pk.scheme == RSA_SHA256 and pk.fmt == B.KEY_SPKI)
+
         for i, it in enumerate(items):
             pk = it.public_key
             if pk.scheme not in SCHEME_CODE_NAMES:
                 st[i] = B.UNSUPPORTED
                 continue
-            if pk.scheme in GPU_SCHEMES:
+            if on_gpu(pk):
                 gpu[mode].append((i, it))
                 continue
             if pk.scheme != COMPOSITE_KEY:
@@ -217,7 +224,7 @@ class _Crypto:
                 for j, (s, msg) in enumerate(C.leaf_messages(sig, it.clear_data)):
                     ref = (i, j)
                     refs.append(ref)
-                    if s.by.scheme in GPU_SCHEMES:
+                    if on_gpu(s.by):
                         gpu[B.MODE_ISVALID].append((ref, BatchItem(s.by, s.bytes, msg)))
                     else:  # RSA / SPHINCS leaves on the host; a composite leaf cannot be fulfilled
                         host_leaf[ref] = host_scheme(s.by.scheme, s.by, s.bytes, msg, B.MODE_ISVALID)
@@ -231,11 +238,16 @@ class _Crypto:
             if not lst:
                 continue
             out = self.engine().verify(self.pack([b for _, b in lst]), m)
-            for (ref, _), s in zip(lst, out):
+            for (ref, b), s in zip(lst, out):
+                e = None
+                if s == B.UNSUPPORTED and b.public_key.scheme == RSA_SHA256:  # a key the GPU declined
+                    s, e = host_scheme(RSA_SHA256, b.public_key, b.signature_data, b.clear_data, m)
                 if isinstance(ref, tuple):
-                    leaf_st[ref] = (int(s), None)
+                    leaf_st[ref] = (int(s), e)
                 else:
                     st[ref] = s
+                    if e is not None:
+                        errors[ref] = e
         for ref, v in host_leaf.items():
             leaf_st[ref] = v
         # the `all { it.isValid(clearData) }` reduction: the first false or exception decides

@@ -25,6 +25,7 @@
 #include "host_budget.h"
 #include "host_pool.h"
 #include "pool.h"
+#include "rsa.h"
 #include "table_budget.h"
 
 // the other builds of the radix-dependent kernels (Makefile VARIANTS; engine.h EngineVariant)
@@ -108,6 +109,10 @@ struct cg_ctx {
   const cgt::EngineVariant* eng = nullptr;
   uint64_t tab_bytes = 0;
   DevBuf wide;  // wide-table pools (keyws.h), sized by the largest call's item count
+  // RSA_SHA256 (CG_FLAG_RSA; verify_rsa.hip): per-key records and the per-call item list + counter.
+  // Never allocated, and no RSA kernel launched, without the flag.
+  bool rsa = false;
+  DevBuf rsakeys, rsalist;
   // wide slots this context may allocate: lowered when the device's free memory cannot hold the
   // pool a call asks for (another process or context on the device), so the call runs
   // with fewer hot keys on wide tables (full tables for the rest: slower, same verdicts) instead of
@@ -304,7 +309,37 @@ uint64_t chunk_of(const cg_ctx* c, uint64_t n) {
 // A call of more than one chunk gets two item workspaces (launch_chunked runs chunk k + 1's front
 // before chunk k's back).
 size_t item_half_bytes(const cg_ctx* c, uint64_t ws_items) { return (c->eng->item_ws_bytes(ws_items) + 255) & ~(size_t)255; }
+// The RSA workspace (contexts with CG_FLAG_RSA only): key records and the item list. Grows like keyprep.
+hipError_t ensure_rsa(cg_ctx* c, uint32_t n_keys, uint64_t n_items) {
+  if (!c->rsa) return hipSuccess;
+  const size_t kb = cg::rsa_keys_bytes(n_keys), lb = cg::rsa_list_bytes(n_items);
+  if (c->rsakeys.cap >= kb && c->rsalist.cap >= lb) return hipSuccess;
+  hipError_t e = hipDeviceSynchronize();
+  if (e == hipSuccess) e = c->rsakeys.ensure(kb);
+  if (e == hipSuccess) e = c->rsalist.ensure(lb);
+  return e;
+}
+// The RSA halves of a call, on the stream of its other launches: the key records before any item
+// stage, the item pass after the last chunk's back (the item table, the arena window, the tx items
+// and the message workspace are whole-call buffers, intact until the call ends).
+hipError_t rsa_keyprep(cg_ctx* c, const cg_key* d_keys, uint32_t n_keys, const uint8_t* d_arena, uint64_t arena_len,
+                       hipStream_t s) {
+  if (!c->rsa) return hipSuccess;
+  return cg::launch_rsa_keyprep(d_keys, n_keys, d_arena, arena_len, c->rsakeys.p, s);
+}
+hipError_t rsa_items(cg_ctx* c, const cg_key* d_keys, uint32_t n_keys, const cg_item* d_items, uint64_t n_items,
+                     const uint8_t* d_arena, uint64_t arena_len, uint32_t mode, uint8_t* d_status, hipStream_t s,
+                     const uint8_t* d_msgs = nullptr, uint64_t msgs_len = 0) {
+  if (!c->rsa || n_items == 0) return hipSuccess;
+  return cg::launch_rsa_items(d_keys, n_keys, d_items, n_items, d_arena, arena_len, mode, d_status, c->rsakeys.p,
+                              c->rsalist.p, s, d_msgs, msgs_len);
+}
+
 hipError_t ensure_ws(cg_ctx* c, uint32_t n_keys, uint64_t ws_items, uint64_t call_items = 0) {
+  {
+    const hipError_t re = ensure_rsa(c, n_keys, call_items > ws_items ? call_items : ws_items);
+    if (re != hipSuccess) return re;
+  }
   // the wide pool is sized for the full slot cap (KEY_WIDE_MAX) whenever the device can hold it: a
   // cap lowered by an earlier call that met low free memory (another process on the device) is
   // raised again here once the memory is back, instead of staying low for the
@@ -377,6 +412,12 @@ hipError_t launch_chunked(cg_ctx* c, const cg_key* d_keys, uint32_t n_keys, cons
   const cg::WidePool wp = wide_for(c, n_keys, n_items);
   hipError_t e = c->eng->launch_keyprep(d_keys, n_keys, d_arena, arena_len, c->keyprep.p, s, &c->fork,
                                     uses ? nullptr : d_items, n_items, &wp, uses);
+  if (e == hipSuccess) e = rsa_keyprep(c, d_keys, n_keys, d_arena, arena_len, s);
+  // the RSA pass over the whole call, after the last chunk's back
+  auto rsa_pass = [&](hipError_t r) {
+    return r != hipSuccess ? r : rsa_items(c, d_keys, n_keys, d_items, n_items, d_arena, arena_len, mode, d_status, s,
+                                           d_msgs, msgs_len);
+  };
   // chunk k = items [at(k), at(k) + cnt(k)): the caller's bounds (bounds[0] = 0, bounds[nch] = n),
   // else equal chunks of chunk_of(c, n) items; `per` (the largest chunk) sizes the item workspaces
   uint64_t per = chunk_of(c, n_items);
@@ -478,7 +519,7 @@ hipError_t launch_chunked(cg_ctx* c, const cg_key* d_keys, uint32_t n_keys, cons
                 (unsigned long long)k, std::chrono::duration<double, std::milli>(h1 - h0).count(), prep_ms,
                 std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - h1).count());
     }
-    return e;
+    return rsa_pass(e);
   }
   // CG_DEV_FRONT_STREAM=1 (A/B, a two-chunk device tx-signature call): chunk 1's items and plan on the
   // caller's stream right after chunk 0's front, its hashes and ECDSA fronts on a stream of their own
@@ -506,7 +547,7 @@ hipError_t launch_chunked(cg_ctx* c, const cg_key* d_keys, uint32_t n_keys, cons
     if (e == hipSuccess) e = back(0);
     if (e == hipSuccess) e = hipStreamWaitEvent(s, c->fs[1], 0);
     if (e == hipSuccess) e = back(1);
-    return e;
+    return rsa_pass(e);
   }
   if (e == hipSuccess) e = front(0);
   for (uint64_t k = 0; k < nch && e == hipSuccess; ++k) {
@@ -514,7 +555,7 @@ hipError_t launch_chunked(cg_ctx* c, const cg_key* d_keys, uint32_t n_keys, cons
     if (two && k + 1 < nch && e == hipSuccess) e = front(k + 1);
     if (e == hipSuccess) e = back(k);
   }
-  return e;
+  return rsa_pass(e);
 }
 
 // ---- host-buffer verify: which arena bytes each pipeline chunk needs
@@ -635,6 +676,7 @@ int verify_host_locked(cg_ctx* c, const cg_key* keys, uint32_t n_keys, const cg_
   const cg::WidePool wp = wide_for(c, n_keys, n_items);
   HIP_TRY(c->eng->launch_keyprep(dk, n_keys, dbase, arena_len, c->keyprep.p, s, &c->fork, di, n_items, &wp, nullptr),
           "launch_keyprep");
+  HIP_TRY(rsa_keyprep(c, dk, n_keys, dbase, arena_len, s), "launch_rsa_keyprep");
   for (uint64_t k = 0; k < nch; ++k) {
     HIP_TRY(copy_missing(have, P.ext[k], arena, dwin, P.win.lo, c->copy), "H2D arena");
     HIP_TRY(hipEventRecord(c->seg[k], c->copy), "hipEventRecord");
@@ -644,6 +686,7 @@ int verify_host_locked(cg_ctx* c, const cg_key* keys, uint32_t n_keys, const cg_
     HIP_TRY(c->eng->launch_items(dk, n_keys, di + f, cnt, dbase, arena_len, mode, ds + f, c->keyprep.p, c->itemws.p,
                              c->btab, s, nullptr, 0, &c->fork, &wp), "launch_items");
   }
+  HIP_TRY(rsa_items(c, dk, n_keys, di, n_items, dbase, arena_len, mode, ds, s), "launch_rsa_items");
   HIP_TRY(hipEventRecord(c->tev[2], s), "hipEventRecord");
   HIP_TRY(hipMemcpyAsync(status_out, ds, n_items, hipMemcpyDeviceToHost, s), "D2H status");
   HIP_TRY(hipEventRecord(c->tev[3], s), "hipEventRecord");
@@ -745,7 +788,7 @@ int cg_open(cg_ctx** out, const cg_config* cfg) {
              (unsigned long long)tab_budget, (unsigned long long)table_sets().back().bytes, table_sets().back().bits);
     return fail(CG_ERR_ARG, "%s", m);
   }
-  if (cfg && (cfg->flags & ~CG_FLAG_STAGE_TIMING)) return fail(CG_ERR_ARG, "cg_open: unknown cg_config.flags bits");
+  if (cfg && (cfg->flags & ~(CG_FLAG_STAGE_TIMING | CG_FLAG_RSA))) return fail(CG_ERR_ARG, "cg_open: unknown cg_config.flags bits");
   int dev = cfg ? cfg->device : 0;
   int n = 0;
   HIP_TRY(hipGetDeviceCount(&n), "hipGetDeviceCount");
@@ -764,6 +807,7 @@ int cg_open(cg_ctx** out, const cg_config* cfg) {
     c->chunk_set = true;
   }
   if (cfg && (cfg->flags & CG_FLAG_STAGE_TIMING)) c->fork.timer = &c->timer;
+  c->rsa = cfg && (cfg->flags & CG_FLAG_RSA);
   // CG_STREAM_PRIORITY=1 (A/B): the context's stream at the device's highest priority, so its
   // blocks (the plan sort's decoupled look-back above all) dispatch ahead of the side streams'
   // table builds
@@ -872,7 +916,7 @@ void cg_close(cg_ctx* c) {
   c->aux1.release();
   c->aux2.release();
   for (DevBuf* b : {&c->txitems, &c->msgs, &c->tmpls, &c->h_txs, &c->h_comps, &c->h_sigs, &c->h_ids, &c->h_txst,
-                    &c->ftxws, &c->sig12ws})
+                    &c->ftxws, &c->sig12ws, &c->rsakeys, &c->rsalist})
     b->release();
   for (int k = 0; k < 3; ++k) {
     if (c->fork.side[k]) {
@@ -930,6 +974,15 @@ uint32_t cg_table_choice(uint64_t table_bytes_max, uint64_t device_free) {
   const std::vector<cgb::TableSet> sets = table_sets();
   const int k = cgb::pick_tables(sets.data(), (int)sets.size(), table_bytes_max, device_free, -1);
   return k < 0 ? 0u : sets[k].bits;
+}
+
+uint32_t cg_rsa_key_bits(const uint8_t* spki, uint32_t len) {
+  if (!spki || len == 0 || len > 0xffffu) return 0;
+  std::vector<uint32_t> buf((len + 3) / 4 + 1, 0u);  // aligned and padded: the decode reads dwords
+  memcpy(buf.data(), spki, len);
+  RsaKeyView v;
+  const uint64_t lr = ((uint64_t)len + 3) & ~(uint64_t)3;
+  return rsa_key_decode(v, (const uint8_t*)buf.data(), lr, 0, len) ? v.bits : 0u;
 }
 
 int cg_context_info(const cg_ctx* c, cg_info* out) {
@@ -1001,11 +1054,15 @@ int cg_prepare_keys_device(cg_ctx* c, const cg_key* d_keys, uint32_t n_keys, con
     HIP_TRY(hipDeviceSynchronize(), "hipDeviceSynchronize");
     HIP_TRY(c->keyprep.ensure(c->eng->keyprep_bytes(n_keys)), "hipMalloc(keyprep)");
   }
+  HIP_TRY(ensure_rsa(c, n_keys, 0), "hipMalloc(RSA workspace)");
   hipStream_t s = stream_of(c, hip_stream);
   HIP_TRY(order_in(c, s), "hipStreamWaitEvent");
-  HIP_TRY(c->eng->launch_keyprep(d_keys, n_keys, d_arena, arena_len, c->keyprep.p, s, &c->fork, nullptr, 0, nullptr,
-                                 nullptr),
-          "launch_keyprep");
+  {  // one guarded region for both launches: no early return of its own between them (stream_of's bridge)
+    hipError_t e = c->eng->launch_keyprep(d_keys, n_keys, d_arena, arena_len, c->keyprep.p, s, &c->fork, nullptr, 0,
+                                          nullptr, nullptr);
+    if (e == hipSuccess) e = rsa_keyprep(c, d_keys, n_keys, d_arena, arena_len, s);
+    HIP_TRY(e, "launch_keyprep");
+  }
   HIP_TRY(order_out(c, s), "hipEventRecord");
   return CG_OK;
 }
@@ -1019,17 +1076,22 @@ int cg_verify_items_device(cg_ctx* c, const cg_key* d_keys, uint32_t n_keys, con
   std::lock_guard<std::mutex> g(c->mu);
   if (c->keyprep.cap < c->eng->keyprep_bytes(n_keys))
     return fail(CG_ERR_ARG, "cg_verify_items_device: keys were not prepared (call cg_prepare_keys_device)");
+  if (c->rsa && c->rsakeys.cap < cg::rsa_keys_bytes(n_keys))
+    return fail(CG_ERR_ARG, "cg_verify_items_device: RSA keys were not prepared (call cg_prepare_keys_device)");
   HIP_TRY(hipSetDevice(c->device), "hipSetDevice");
   HIP_TRY(ensure_ws(c, n_keys, chunk_of(c, n_items)), "hipMalloc(item workspace)");
+  HIP_TRY(ensure_rsa(c, n_keys, n_items), "hipMalloc(RSA workspace)");
   hipStream_t s = stream_of(c, hip_stream);
   HIP_TRY(order_in(c, s), "hipStreamWaitEvent");
   const uint64_t per = chunk_of(c, n_items);
-  for (uint64_t f = 0; f < n_items; f += per) {
+  hipError_t le = hipSuccess;  // the chunks and the RSA pass in one guarded region (stream_of's bridge)
+  for (uint64_t f = 0; f < n_items && le == hipSuccess; f += per) {
     const uint64_t cnt = per < n_items - f ? per : n_items - f;
-    HIP_TRY(c->eng->launch_items(d_keys, n_keys, d_items + f, cnt, d_arena, arena_len, mode, d_status + f, c->keyprep.p,
-                             c->itemws.p, c->btab, s, nullptr, 0, &c->fork, nullptr),
-            "launch_items");
+    le = c->eng->launch_items(d_keys, n_keys, d_items + f, cnt, d_arena, arena_len, mode, d_status + f, c->keyprep.p,
+                              c->itemws.p, c->btab, s, nullptr, 0, &c->fork, nullptr);
   }
+  if (le == hipSuccess) le = rsa_items(c, d_keys, n_keys, d_items, n_items, d_arena, arena_len, mode, d_status, s);
+  HIP_TRY(le, "launch_items");
   HIP_TRY(order_out(c, s), "hipEventRecord");
   return CG_OK;
 }

@@ -247,6 +247,22 @@ hipError_t launch_items_back(const cg_key* d_keys, uint32_t n_keys, const cg_ite
                              void* d_item_ws, const void* d_btab, hipStream_t stream, const Fork* fork,
                              const WidePool* wide);
 
+// RSA_SHA256 (verify_rsa.hip; radix-independent, used only by contexts opened with CG_FLAG_RSA).
+// Key records for a key table (launch_rsa_keyprep fills them: accepted keys get their Montgomery
+// constants, every other key a "not accepted" mark), and one pass over a call's items after its
+// ladders: the items whose key was accepted are listed on the device (d_rsalist: the count, then the
+// list; rsa_list_bytes) and verified, overwriting the CG_UNSUPPORTED k_misc_status gave them. Nothing
+// comes back to the host. Calls of more than kRsaSegment items run the pass per segment.
+constexpr uint64_t kRsaSegment = 1ull << 30;
+size_t rsa_keys_bytes(uint32_t n_keys);
+size_t rsa_list_bytes(uint64_t n_items);
+hipError_t launch_rsa_keyprep(const cg_key* d_keys, uint32_t n_keys, const uint8_t* d_arena, uint64_t arena_len,
+                              void* d_rsakeys, hipStream_t stream);
+hipError_t launch_rsa_items(const cg_key* d_keys, uint32_t n_keys, const cg_item* d_items, uint64_t n_items,
+                            const uint8_t* d_arena, uint64_t arena_len, uint32_t mode, uint8_t* d_status,
+                            const void* d_rsakeys, void* d_rsalist, hipStream_t stream, const uint8_t* d_msgs = nullptr,
+                            uint64_t msgs_len = 0);
+
 // Hashing kernels
 hipError_t launch_sha256(const cg_span* d_spans, uint64_t n, const uint8_t* d_arena, uint64_t arena_len,
                          uint8_t* d_out, hipStream_t stream);

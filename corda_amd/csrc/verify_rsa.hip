@@ -1,0 +1,394 @@
+// RSA_SHA256 (RSASSA-PSS) batch verification for gfx950, run only by contexts opened with CG_FLAG_RSA.
+//
+//   k_rsa_keyprep  one wave per key of the table: strict DER decode (rsa.h rsa_key_decode), n as limbs,
+//                  -n^-1 mod 2^32, R^2 mod n, or a "not accepted" mark.
+//   k_rsa_select   the indices of the items whose key was accepted, compacted into a list; the count
+//                  stays in device memory.
+//   k_rsa_verify   one signature per wavefront, limbs spread over the lanes (lane l holds limbs
+//                  K l .. K l + K - 1; K = 1 up to 2048 bits, 2 above). s^e mod n by left-to-right
+//                  square-and-multiply over operand-scanning Montgomery products: per step the
+//                  multiplier limb a_i and the quotient digit m are wave-uniform (v_readlane), each
+//                  limb product is one v_mad_u64_u32 into a per-lane 64-bit accumulator, the
+//                  accumulator moves down one limb by a DPP wave shift, and the carries the lanes
+//                  hold back are resolved once per product with two ballots (generate / propagate).
+//                  The messages of a wave's G signatures are hashed first, one lane each, so the
+//                  SHA-256 of the clear data runs lane-parallel; G = count / waves, between 1 and 64,
+//                  from the device-side count. EMSA-PSS (rsa.h): EM goes to LDS, the MGF1 blocks are
+//                  one lane each, the final compare on lane 0.
+// The pass overwrites the CG_UNSUPPORTED k_misc_status gave these items and nothing else.
+#include "keyws.h"
+#include "rsa.h"
+
+namespace cg {
+
+#define RSA_PENDING 249u
+#define RSA_NONE 255u
+#define RSA_EM_LDS 528u  // 512 EM bytes + slack, per wave
+
+__global__ void __launch_bounds__(256) k_rsa_select(const cg_item* __restrict__ items, uint32_t n_items,
+                                                    const cg_key* __restrict__ keys, uint32_t n_keys,
+                                                    const RsaKeyRec* __restrict__ recs, uint32_t* __restrict__ list,
+                                                    uint32_t* __restrict__ count) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  bool take = false;
+  if (i < n_items) {
+    const uint32_t ki = items[i].key_idx;
+    take = ki < n_keys && keys[ki].scheme == CG_RSA_SHA256 && recs[ki].ok != 0;
+  }
+  const uint64_t m = __ballot(take);
+  if (m == 0) return;
+  const uint32_t lane = threadIdx.x & 63u;
+  const int leader = __ffsll((long long)m) - 1;
+  uint32_t base = 0;
+  if ((int)lane == leader) base = atomicAdd(count, (uint32_t)__popcll(m));
+  base = __shfl(base, leader, 64);
+  if (take) list[base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = i;
+}
+
+// ---- lane-cooperative big numbers: limb K * lane + k in w[k] of each lane; every function below is
+// called by all 64 lanes of the wave together.
+// Deferred carries -> limbs. acc[k] < 2^35; the carry out of the top limb (limb 64 K) adds to `top`.
+template <int K>
+__device__ __forceinline__ void rsa_resolve(uint32_t r[K], const uint64_t acc[K], uint32_t lane, uint32_t& top) {
+  uint64_t c = 0;
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    const uint64_t v = acc[k] + c;
+    r[k] = (uint32_t)v;
+    c = v >> 32;
+  }
+  uint32_t cin = __shfl_up((uint32_t)c, 1, 64);
+  if (lane == 0) cin = 0;
+  top += __shfl((uint32_t)c, 63, 64);
+  uint32_t g = cin;
+  bool p = true;
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    const uint64_t v = (uint64_t)r[k] + g;
+    r[k] = (uint32_t)v;
+    g = (uint32_t)(v >> 32);
+    p = p && r[k] == 0xffffffffu;
+  }
+  // what is left is a 0/1 ripple: lane l generates (g) or propagates (p: all ones), never both
+  const uint64_t G = __ballot(g != 0), P = __ballot(p);
+  const uint64_t C = ((G << 1) + P) ^ P;  // carry into lane l at bit l
+  top += (uint32_t)((G >> 63) | ((P >> 63) & (C >> 63)));
+  uint32_t ci = (uint32_t)(C >> lane) & 1u;
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    const uint64_t v = (uint64_t)r[k] + ci;
+    r[k] = (uint32_t)v;
+    ci = (uint32_t)(v >> 32);
+  }
+}
+
+// a >= b over all limbs
+template <int K>
+__device__ __forceinline__ bool rsa_geq(const uint32_t a[K], const uint32_t b[K]) {
+  bool gt = false, lt = false;
+#pragma unroll
+  for (int k = K - 1; k >= 0; --k) {
+    if (!gt && !lt) {
+      gt = a[k] > b[k];
+      lt = a[k] < b[k];
+    }
+  }
+  return __ballot(gt) >= __ballot(lt);
+}
+
+// acc (a value below 2 n, carries deferred) -> r = acc mod n over L limbs
+template <int K>
+__device__ __forceinline__ void rsa_finish(uint32_t r[K], const uint64_t acc[K], const uint32_t n[K], uint32_t L,
+                                           uint32_t lane) {
+  uint32_t top = 0;
+  rsa_resolve<K>(r, acc, lane, top);
+  bool hi = false;  // a limb at or above L set: the value is >= 2^(32 L) > n
+#pragma unroll
+  for (int k = 0; k < K; ++k) hi = hi || (K * lane + k >= L && r[k] != 0);
+  const bool over = top != 0 || __ballot(hi) != 0;
+  if (over || rsa_geq<K>(r, n)) {
+    uint64_t d[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) d[k] = (uint64_t)r[k] + (uint32_t)~n[k] + ((lane == 0 && k == 0) ? 1u : 0u);
+    uint32_t t2 = 0;
+    rsa_resolve<K>(r, d, lane, t2);
+  }
+#pragma unroll
+  for (int k = 0; k < K; ++k)
+    if (K * lane + k >= L) r[k] = 0;
+}
+
+// r = a b R^-1 mod n, R = 2^(32 L); a, b < n. r may alias a or b.
+template <int K>
+__device__ __forceinline__ void rsa_mont_mul(uint32_t r[K], const uint32_t a[K], const uint32_t b[K],
+                                             const uint32_t n[K], uint32_t n0inv, uint32_t L, uint32_t lane) {
+  uint64_t acc[K];
+#pragma unroll
+  for (int k = 0; k < K; ++k) acc[k] = 0;
+  const uint32_t nl = (L + K - 1) / K;
+  for (uint32_t li = 0; li < nl; ++li) {
+#pragma unroll
+    for (int kk = 0; kk < K; ++kk) {
+      if (K * li + kk >= L) break;
+      const uint32_t ai = __builtin_amdgcn_readlane(a[kk], li);
+      uint64_t p[K], q[K];
+#pragma unroll
+      for (int k = 0; k < K; ++k) p[k] = (uint64_t)ai * b[k] + (uint32_t)acc[k];
+      const uint32_t m = __builtin_amdgcn_readfirstlane((uint32_t)p[0] * n0inv);
+#pragma unroll
+      for (int k = 0; k < K; ++k) q[k] = (uint64_t)m * n[k] + (uint32_t)p[k];
+      // the next lane's lowest limb: a DPP wave shift (lane l reads lane l + 1, lane 63 reads 0), a
+      // VALU move instead of a round trip through the LDS crossbar on the per-step critical path
+      const uint32_t dn = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)q[0], 0x130, 0xf, 0xf, false);
+#pragma unroll
+      for (int k = 0; k < K; ++k) {
+        const uint32_t next = k + 1 < K ? (uint32_t)q[k + 1 < K ? k + 1 : 0] : dn;
+        acc[k] = (uint64_t)next + (p[k] >> 32) + (q[k] >> 32) + (acc[k] >> 32);
+      }
+    }
+  }
+  rsa_finish<K>(r, acc, n, L, lane);
+}
+
+// The per-key constants on one wave (limbs over the lanes as in the verify kernel): n, then R mod n
+// from 2^(bits - 1) < n by 32 L - bits + 1 modular doublings, then R^2 = 2^(32 L) R mod n as the
+// Montgomery form of 2^(32 L): square-and-double over the bits of 32 L (at most 12 products), where
+// the scalar form (rsa.h rsa_rr, kept for the host) needs 64 L doublings of L limbs on one lane.
+template <int K>
+__device__ __forceinline__ void rsa_double_mod_wave(uint32_t x[K], const uint32_t n[K], uint32_t L, uint32_t lane) {
+  uint64_t acc[K];
+#pragma unroll
+  for (int k = 0; k < K; ++k) acc[k] = 2ull * x[k];
+  rsa_finish<K>(x, acc, n, L, lane);
+}
+template <int K>
+__device__ __forceinline__ void rsa_keyprep_wave(RsaKeyRec* __restrict__ rec, const RsaKeyView& v,
+                                                 const uint8_t* __restrict__ arena, uint64_t lr, uint32_t lane) {
+  const uint32_t bits = v.bits, L = (bits + 31) / 32;
+  uint32_t n[K], x[K];
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    n[k] = rsa_be_limb(arena, lr, v.n_off, v.n_len, K * lane + k);
+    x[k] = (K * lane + k == (bits - 1) >> 5) ? 1u << ((bits - 1) & 31u) : 0u;
+  }
+  const uint32_t n0inv = rsa_n0inv(__shfl(n[0], 0, 64));
+  for (uint32_t s = 32 * L - (bits - 1); s > 0; --s) rsa_double_mod_wave<K>(x, n, L, lane);  // R mod n
+  rsa_double_mod_wave<K>(x, n, L, lane);                                                    // 2 R: "2"
+  const uint32_t E = 32 * L;
+  for (int bit = 30 - __builtin_clz(E); bit >= 0; --bit) {
+    rsa_mont_mul<K>(x, x, x, n, n0inv, L, lane);
+    if ((E >> bit) & 1u) rsa_double_mod_wave<K>(x, n, L, lane);
+  }
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    rec->n[K * lane + k] = n[k];
+    rec->rr[K * lane + k] = x[k];
+    if (K == 1) rec->n[64 + lane] = rec->rr[64 + lane] = 0;
+  }
+  if (lane == 0) {
+    rec->bits = bits;
+    rec->L = L;
+    rec->k = (bits + 7) / 8;
+    rec->em_bits = bits - 1;
+    rec->block_len = (bits + 6) / 8;
+    rec->e = v.e;
+    rec->n0inv = n0inv;
+    rec->ok = 1;
+  }
+}
+
+// One wave per key. Every lane runs the (uniform) decode; the constants are lane-cooperative.
+__global__ void __launch_bounds__(64) k_rsa_keyprep(const cg_key* __restrict__ keys, uint32_t n_keys,
+                                                    const uint8_t* __restrict__ arena, uint64_t arena_len,
+                                                    RsaKeyRec* __restrict__ recs) {
+  const uint32_t i = blockIdx.x, lane = threadIdx.x;
+  if (i >= n_keys) return;
+  const cg_key k = keys[i];
+  RsaKeyRec* rec = recs + i;
+  const uint64_t lr = round4(arena_len);
+  RsaKeyView v;
+  const bool ok = k.scheme == CG_RSA_SHA256 && k.fmt == CG_KEY_SPKI && in_arena(k.off, k.len, arena_len) &&
+                  rsa_key_decode(v, arena, lr, k.off, k.len);
+  if (!ok) {
+    if (lane == 0) rec->ok = 0;
+    return;
+  }
+  if (v.bits <= 2048) rsa_keyprep_wave<1>(rec, v, arena, lr, lane);
+  else rsa_keyprep_wave<2>(rec, v, arena, lr, lane);
+}
+
+// One signature on one wave: s^e mod n, the fit and EMSA-PSS checks. All 64 lanes call it with
+// wave-uniform arguments; returns CG_VALID or CG_INVALID (uniform).
+template <int K>
+__device__ __forceinline__ uint32_t rsa_wave_verify(const RsaKeyRec* __restrict__ rec, uint32_t L, uint32_t e,
+                                                    uint32_t n0inv, uint32_t block_len, uint32_t em_bits,
+                                                    const uint8_t* __restrict__ arena, uint64_t lr, uint64_t sig_off,
+                                                    uint32_t sig_len, const uint32_t mhash[8], uint8_t* em,
+                                                    uint32_t lane) {
+  uint32_t n[K], s[K], x[K], acc[K];
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    n[k] = rec->n[K * lane + k];
+    x[k] = rec->rr[K * lane + k];
+    s[k] = rsa_be_limb(arena, lr, sig_off, sig_len, K * lane + k);
+  }
+  if (rsa_geq<K>(s, n)) return CG_INVALID;  // RSACoreEngine.convertInput: input too large for RSA cipher
+  if (e > 1) {
+    rsa_mont_mul<K>(x, s, x, n, n0inv, L, lane);  // s R
+#pragma unroll
+    for (int k = 0; k < K; ++k) acc[k] = x[k];
+    const int top = 31 - __builtin_clz(e);
+    for (int bit = top - 1; bit >= 1; --bit) {
+      rsa_mont_mul<K>(acc, acc, acc, n, n0inv, L, lane);
+      if ((e >> bit) & 1u) rsa_mont_mul<K>(acc, acc, x, n, n0inv, L, lane);
+    }
+    rsa_mont_mul<K>(acc, acc, acc, n, n0inv, L, lane);
+    if (e & 1u) {
+      rsa_mont_mul<K>(acc, acc, s, n, n0inv, L, lane);  // times plain s: out of Montgomery form
+    } else {
+      uint32_t one[K];
+#pragma unroll
+      for (int k = 0; k < K; ++k) one[k] = (lane == 0 && k == 0) ? 1u : 0u;
+      rsa_mont_mul<K>(acc, acc, one, n, n0inv, L, lane);
+    }
+  } else {
+#pragma unroll
+    for (int k = 0; k < K; ++k) acc[k] = s[k];
+  }
+  // m as block_len big-endian bytes; a set byte above them: the block does not fit (false)
+  bool wide = false;
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+      const uint32_t j = 4 * (K * lane + k) + b;  // byte j from the least significant end
+      const uint32_t v = (acc[k] >> (8 * b)) & 0xffu;
+      if (j < block_len) em[block_len - 1 - j] = (uint8_t)v;
+      else wide = wide || v != 0;
+    }
+  }
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  if (__ballot(wide) != 0) return CG_INVALID;
+  uint32_t ok = lane == 0 ? (rsa_pss_pre(em, block_len) ? 1u : 0u) : 0u;
+  ok = __builtin_amdgcn_readfirstlane(ok);
+  if (!ok) return CG_INVALID;
+  const uint32_t db_len = block_len - RSA_HASH_LEN - 1u;
+  if (32u * lane < db_len) rsa_pss_unmask_block(em, db_len, lane);  // db_len <= 479: at most 15 lanes
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  ok = lane == 0 ? (rsa_pss_post(em, block_len, em_bits, mhash) ? 1u : 0u) : 0u;
+  ok = __builtin_amdgcn_readfirstlane(ok);
+  return ok ? CG_VALID : CG_INVALID;
+}
+
+__global__ void __launch_bounds__(256) k_rsa_verify(const cg_item* __restrict__ items,
+                                                    const uint32_t* __restrict__ list,
+                                                    const uint32_t* __restrict__ count_p,
+                                                    const RsaKeyRec* __restrict__ recs,
+                                                    const uint8_t* __restrict__ arena, uint64_t arena_len,
+                                                    const uint8_t* __restrict__ msgs, uint64_t msgs_len, uint32_t mode,
+                                                    uint8_t* __restrict__ status) {
+  __shared__ __attribute__((aligned(16))) uint8_t em_all[4 * RSA_EM_LDS];
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t wv = threadIdx.x >> 6;
+  uint8_t* em = em_all + wv * RSA_EM_LDS;
+  const uint32_t count = *count_p;
+  const uint32_t waves = gridDim.x * (blockDim.x >> 6);
+  const uint32_t wave_id = blockIdx.x * (blockDim.x >> 6) + wv;
+  uint32_t G = count / waves;  // signatures a wave takes per round: their messages hash lane-parallel
+  G = G < 1 ? 1 : G > 64 ? 64 : G;
+  const uint64_t lr = round4(arena_len);
+  for (uint64_t base = (uint64_t)wave_id * G; base < count; base += (uint64_t)waves * G) {
+    uint32_t st = RSA_NONE, idx = 0, key = 0, sig_len = 0;
+    uint64_t sig_off = 0;
+    uint32_t mh[8];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) mh[q] = 0;
+    if (lane < G && base + lane < count) {
+      idx = list[base + lane];
+      const cg_item it = items[idx];
+      key = it.key_idx;
+      sig_off = it.sig_off;
+      sig_len = it.sig_len;
+      if (mode == CG_MODE_DOVERIFY && (it.sig_len == 0 || it.msg_len == 0)) {
+        st = CG_EMPTY;
+      } else if (!in_arena(it.sig_off, it.sig_len, arena_len) ||
+                 (msgs ? !item_fused(it, msgs) : !in_arena(it.msg_off, it.msg_len, arena_len))) {
+        st = CG_NOT_RUN;
+      } else if (it.sig_len == 0 || it.sig_len > recs[key].k) {
+        st = CG_INVALID;  // longer than the modulus: DataLengthException, caught; empty: s = 0
+      } else {
+        if (msgs) {
+          const TmplMid* mid = item_tmpl_mid(it, msgs);
+          sha256_ld_suffix(mh, item_splice(it, msgs), 0, it.msg_len, nullptr, mid->state, mid->blocks);
+        } else {
+          sha256_ld_suffix(mh, ArenaLd{arena, lr}, it.msg_off, it.msg_len, nullptr);
+        }
+        st = RSA_PENDING;
+      }
+      if (st != RSA_PENDING) status[idx] = (uint8_t)st;
+    }
+    for (uint32_t t = 0; t < G; ++t) {
+      if ((uint32_t)__shfl((int)st, (int)t, 64) != RSA_PENDING) continue;
+      const uint32_t idx_t = __shfl(idx, t, 64);
+      const uint32_t key_t = __shfl(key, t, 64);
+      const uint32_t sl_t = __shfl(sig_len, t, 64);
+      const uint64_t so_t = ((uint64_t)__shfl((uint32_t)(sig_off >> 32), t, 64) << 32) | __shfl((uint32_t)sig_off, t, 64);
+      uint32_t mh_t[8];
+#pragma unroll
+      for (int q = 0; q < 8; ++q) mh_t[q] = __shfl(mh[q], t, 64);
+      const RsaKeyRec* rec = recs + key_t;
+      const uint32_t L = __builtin_amdgcn_readfirstlane(rec->L);
+      const uint32_t e = __builtin_amdgcn_readfirstlane(rec->e);
+      const uint32_t n0inv = __builtin_amdgcn_readfirstlane(rec->n0inv);
+      const uint32_t block_len = __builtin_amdgcn_readfirstlane(rec->block_len);
+      const uint32_t em_bits = __builtin_amdgcn_readfirstlane(rec->em_bits);
+      uint32_t v;
+      if (L <= 64)
+        v = rsa_wave_verify<1>(rec, L, e, n0inv, block_len, em_bits, arena, lr, so_t, sl_t, mh_t, em, lane);
+      else
+        v = rsa_wave_verify<2>(rec, L, e, n0inv, block_len, em_bits, arena, lr, so_t, sl_t, mh_t, em, lane);
+      if (lane == 0) status[idx_t] = (uint8_t)v;
+      __builtin_amdgcn_wave_barrier();  // the next signature reuses the wave's EM bytes
+    }
+  }
+}
+
+size_t rsa_keys_bytes(uint32_t n_keys) { return al256((size_t)(n_keys ? n_keys : 1) * sizeof(RsaKeyRec)); }
+size_t rsa_list_bytes(uint64_t n_items) {
+  const uint64_t n = n_items < kRsaSegment ? n_items : kRsaSegment;
+  return 256 + al256((size_t)(n ? n : 1) * sizeof(uint32_t));
+}
+
+hipError_t launch_rsa_keyprep(const cg_key* d_keys, uint32_t n_keys, const uint8_t* d_arena, uint64_t arena_len,
+                              void* d_rsakeys, hipStream_t stream) {
+  if (n_keys == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_rsa_keyprep, dim3(n_keys), dim3(64), 0, stream, d_keys, n_keys, d_arena, arena_len,
+                     (RsaKeyRec*)d_rsakeys);
+  return hipGetLastError();
+}
+
+hipError_t launch_rsa_items(const cg_key* d_keys, uint32_t n_keys, const cg_item* d_items, uint64_t n_items,
+                            const uint8_t* d_arena, uint64_t arena_len, uint32_t mode, uint8_t* d_status,
+                            const void* d_rsakeys, void* d_rsalist, hipStream_t stream, const uint8_t* d_msgs,
+                            uint64_t msgs_len) {
+  if (n_keys == 0) return hipSuccess;
+  uint32_t* count = (uint32_t*)d_rsalist;
+  uint32_t* list = (uint32_t*)((uint8_t*)d_rsalist + 256);
+  for (uint64_t f = 0; f < n_items; f += kRsaSegment) {
+    const uint32_t cnt = (uint32_t)(kRsaSegment < n_items - f ? kRsaSegment : n_items - f);
+    hipError_t e = hipMemsetAsync(count, 0, sizeof(uint32_t), stream);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_rsa_select, dim3((cnt + 255) / 256), dim3(256), 0, stream, d_items + f, cnt, d_keys, n_keys,
+                       (const RsaKeyRec*)d_rsakeys, list, count);
+    // one wave per listed signature at most; the count is read on the device (no host round trip)
+    const unsigned grid = walk_grid(((uint64_t)cnt + 3) / 4 * 256, 256, WALK_CAP(4));
+    hipLaunchKernelGGL(k_rsa_verify, dim3(grid), dim3(256), 0, stream, d_items + f, (const uint32_t*)list,
+                       (const uint32_t*)count, (const RsaKeyRec*)d_rsakeys, d_arena, arena_len, d_msgs, msgs_len, mode,
+                       d_status + f);
+  }
+  return hipGetLastError();
+}
+
+}  // namespace cg

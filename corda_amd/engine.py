@@ -18,17 +18,19 @@ def _p(a):
 
 
 class Engine:
-    def __init__(self, device=0, chunk_items=0, stage_timing=False, host_threads=0, table_bytes_max=0):
-        """host_threads: cg_config.host_threads (0: CG_HOST_THREADS, else the CPU quota divided by the
+    def __init__(self, device=0, chunk_items=0, stage_timing=False, host_threads=0, table_bytes_max=0, rsa=False):
+        """rsa: CG_FLAG_RSA, RSA_SHA256 items with a key the device decode accepts are verified on the
+        GPU (off: they stay UNSUPPORTED, as every other RSA key does either way); host_threads: cg_config.host_threads (0: CG_HOST_THREADS, else the CPU quota divided by the
         contexts open in this process); table_bytes_max: HBM the constant fixed-base tables may take
         (0: automatic; include/cordagpu.h, corda_amd/csrc/table_budget.h)."""
         L = _lib.lib()
-        cfg = _lib.cg_config(device, _lib.FLAG_STAGE_TIMING if stage_timing else 0, 0, 0, chunk_items, host_threads,
-                             0, table_bytes_max)
+        flags = (_lib.FLAG_STAGE_TIMING if stage_timing else 0) | (_lib.FLAG_RSA if rsa else 0)
+        cfg = _lib.cg_config(device, flags, 0, 0, chunk_items, host_threads, 0, table_bytes_max)
         h = ctypes.c_void_p()
         _lib.check(L.cg_open(ctypes.byref(h), ctypes.byref(cfg)), f"cg_open(device={device})")
         self._h = h
         self.device = device
+        self.rsa = bool(rsa)
         self.last_stats = None
 
     def info(self):
@@ -244,14 +246,15 @@ class EnginePool:
     slots, re-runs a failed slot's shard elsewhere, and returns one status byte per item (items
     no slot could run stay NOT_RUN and raise ``EngineUnavailable`` unless ``allow_partial``)."""
 
-    def __init__(self, devices, chunk_items=0, host_threads=0, table_bytes_max=0):
+    def __init__(self, devices, chunk_items=0, host_threads=0, table_bytes_max=0, rsa=False):
         L = _lib.lib()
-        cfg = _lib.cg_config(0, 0, 0, 0, chunk_items, host_threads, 0, table_bytes_max)
+        cfg = _lib.cg_config(0, _lib.FLAG_RSA if rsa else 0, 0, 0, chunk_items, host_threads, 0, table_bytes_max)
         devs = (ctypes.c_int32 * len(devices))(*devices)
         h = ctypes.c_void_p()
         _lib.check(L.cg_pool_open(ctypes.byref(h), devs, len(devices), ctypes.byref(cfg)), "cg_pool_open")
         self._h = h
         self.devices = list(devices)
+        self.rsa = bool(rsa)
         self.last_stats = None
 
     def close(self):

@@ -153,9 +153,15 @@ class SignedWireTransaction:
     notary: object = None
 
 
-def pack_signed_transactions(stxs):
+def _on_gpu(pk, rsa):
+    """Does the engine run this key's scheme (rsa: the engine was opened with rsa=True)?"""
+    return pk.scheme in GPU_SCHEMES or (rsa and pk.scheme == 1 and pk.fmt == B.KEY_SPKI)
+
+
+def pack_signed_transactions(stxs, rsa=False):
     """One arena for components, salts, keys, signatures and SignableData templates; returns
-    (txs, comps, keys, sigs, tmpls, arena) in the include/cordagpu.h layouts."""
+    (txs, comps, keys, sigs, tmpls, arena) in the include/cordagpu.h layouts. rsa: the engine verifies
+    RSA_SHA256 signatures (Engine(rsa=True)), so their bytes are packed too."""
     bb = B.BatchBuilder()
     comps, tx_rows, sig_rows, tmpl_rows, tmpl_index = [], [], [], [], {}
 
@@ -178,7 +184,7 @@ def pack_signed_transactions(stxs):
             k = bb.key(s.by.scheme, s.by.fmt, s.by.encoded)
             # a scheme the GPU does not run gets CG_UNSUPPORTED whatever its bytes (the host
             # verifies it afterwards, verify_wire_transactions): pack a 1-byte placeholder
-            sb = B.sig_field(s.by.scheme, s.bytes) if s.by.scheme in GPU_SCHEMES else b"\x00"
+            sb = B.sig_field(s.by.scheme, s.bytes) if _on_gpu(s.by, rsa) else b"\x00"
             sig_rows.append((bb._append(sb, 4), t, k, len(sb), tmpl_for(s.platform_version, s.scheme_number_id), 0))
     built = bb.build()
     txs = np.array(tx_rows, dtype=B.TX_DTYPE) if tx_rows else np.zeros(0, B.TX_DTYPE)
@@ -195,7 +201,8 @@ def verify_wire_transactions(stxs, crypto=Crypto):
     (TransactionWithSignatures.kt:58-61). Ids, SignableData messages and verdicts are all
     computed on the GPU in one cg_verify_transactions call."""
     from .merkle import MerkleTreeException
-    txs, comps, keys, sigs, tmpls, arena = pack_signed_transactions(stxs)
+    rsa = bool(getattr(crypto.engine(), "rsa", False))
+    txs, comps, keys, sigs, tmpls, arena = pack_signed_transactions(stxs, rsa)
     ids, txst, sst = crypto.engine().verify_transactions(txs, comps, keys, sigs, tmpls, arena, B.MODE_DOVERIFY)
     sst = sst.copy()
     # signatures the GPU returned CG_UNSUPPORTED for (RSA, SPHINCS, composite keys): the host
@@ -203,7 +210,8 @@ def verify_wire_transactions(stxs, crypto=Crypto):
     errors, fb, pos = {}, [], 0
     for t, stx in enumerate(stxs):
         for i, s in enumerate(stx.sigs):
-            if s.by.scheme not in GPU_SCHEMES and txst[t] == 0:
+            # (with an rsa engine: only the RSA signatures whose key the device decode declined)
+            if txst[t] == 0 and (not _on_gpu(s.by, rsa) or (s.by.scheme == 1 and sst[pos + i] == B.UNSUPPORTED)):
                 pre, suf = signable.template(s.platform_version, s.scheme_number_id)
                 fb.append((pos + i, BatchItem(s.by, s.bytes, pre + bytes(ids[t]) + suf)))
         pos += len(stx.sigs)

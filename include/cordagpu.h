@@ -38,7 +38,17 @@ extern "C" {
 
 #define CG_ABI_VERSION 2
 
-/* Corda SignatureScheme.schemeNumberID (Crypto.kt:78-184). Others => CG_UNSUPPORTED. */
+/* Corda SignatureScheme.schemeNumberID (Crypto.kt:78-184). Others => CG_UNSUPPORTED.
+ * CG_RSA_SHA256 (BouncyCastle SHA256WITHRSAANDMGF1: RSASSA-PSS, SHA-256, MGF1-SHA256, 32-byte salt,
+ * trailer 0xBC) is CG_UNSUPPORTED too unless the context was opened with CG_FLAG_RSA. With the flag
+ * an item gets a verdict when its key is CG_KEY_SPKI and the device decode accepts it: canonical DER
+ * SubjectPublicKeyInfo { AlgorithmIdentifier { rsaEncryption 1.2.840.113549.1.1.1, parameters absent
+ * or NULL }, BIT STRING with 0 unused bits { RSAPublicKey { n, e } } }, every length minimal, no
+ * trailing bytes, all inside cg_key.len, both INTEGERs minimal and positive, n odd with
+ * 1024 <= bitlen(n) <= 4096 (any bit length), 1 <= e < 2^32. Every other RSA key (BER forms, other
+ * sizes, even n, larger e, another fmt) stays CG_UNSUPPORTED, so the caller's host fallback decides
+ * it with the reference's own exception: the engine gives a verdict only for keys it has parsed fully
+ * and strictly. cg_rsa_key_bits tells which keys those are. */
 enum {
   CG_RSA_SHA256 = 1,
   CG_ECDSA_SECP256K1_SHA256 = 2,
@@ -137,6 +147,8 @@ typedef struct cg_tx {
 
 /* cg_config.flags */
 #define CG_FLAG_STAGE_TIMING 1u /* time every item stage with HIP events on the stream it runs on (cg_stage_times) */
+#define CG_FLAG_RSA 2u          /* verify CG_RSA_SHA256 items on the device (off: they stay CG_UNSUPPORTED, no RSA
+                                   kernel runs and no RSA workspace is allocated) */
 
 /* Item stages reported by cg_stage_times (one launch per verify chunk each). */
 enum {
@@ -220,6 +232,10 @@ int cg_context_info(const cg_ctx* ctx, cg_info* out);
  * every set, cg_open returns CG_ERR_ARG). */
 uint64_t cg_table_bytes(uint32_t fixed_base_bits);
 uint32_t cg_table_choice(uint64_t table_bytes_max, uint64_t device_free);
+/* The modulus bit length if a CG_FLAG_RSA context would verify under this CG_KEY_SPKI key (the
+ * accepted-key rule at the scheme enum; the same decode function the key-prep kernel runs), else 0:
+ * such a key's items keep CG_UNSUPPORTED. HIP-free: a binding can pre-route with it. */
+uint32_t cg_rsa_key_bits(const uint8_t* spki, uint32_t len);
 
 /* Host memory registration (zero-copy ingestion). A caller that keeps its buffers across calls (a
  * JVM direct ByteBuffer arena, the out-of-process verifier's request buffers) registers them once:
@@ -250,7 +266,17 @@ int cg_host_register_advised(uint32_t contexts_per_node);
  * the last field with arena_len no multiple of 4. Lengths: sig_len and cg_key.len are 16-bit; a JVM signature longer than 65 535 bytes is
  * packed as a surrogate with the same verdict. stats: ms_h2d = until the
  * first chunk is resident, ms_verify = the rest. On CG_ERR_DEVICE every status byte is
- * CG_NOT_RUN. */
+ * CG_NOT_RUN.
+ * CG_RSA_SHA256 items under a CG_FLAG_RSA context (this and every other verify entry point, the
+ * device, transaction, tx-signature and pool forms included): with an accepted key (scheme enum) the
+ * status is CG_VALID, CG_INVALID, CG_EMPTY (CG_MODE_DOVERIFY: sig_len == 0 or msg_len == 0) or
+ * CG_NOT_RUN (signature or message outside the arena), with the ECDSA path's precedence; never
+ * CG_SIG_MALFORMED or CG_KEY_INVALID: every failure inside BC's PSSSigner.verifySignature is `false`
+ * (a signature longer than the modulus, s >= n, a PKCS#1 v1.5 block), and under CG_MODE_ISVALID an
+ * empty signature is CG_INVALID. A shorter signature is the same integer with leading zeros. The bits
+ * of the encoded message above emBits are masked, not checked (BC 1.57; OpenSSL rejects them). Any
+ * other RSA key: CG_UNSUPPORTED, as without the flag. The RSA items are verified in one pass after
+ * the call's other items; a call without RSA keys pays a few small launches. */
 int cg_verify_batch(cg_ctx* ctx, const cg_key* keys, uint32_t n_keys, const cg_item* items, uint64_t n_items,
                     const uint8_t* arena, uint64_t arena_len, uint32_t mode, uint8_t* status_out,
                     cg_stats* stats_opt);

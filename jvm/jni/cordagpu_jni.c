@@ -23,18 +23,19 @@ static void throw_state(JNIEnv* env, const char* fn, int rc) {
   if (ex) (*env)->ThrowNew(env, ex, msg);
 }
 
-static cg_config make_config(jlong chunk_items, jint host_threads, jlong table_bytes_max) {
+static cg_config make_config(jlong chunk_items, jint host_threads, jlong table_bytes_max, jint flags) {
   cg_config cfg = {0}; /* ABI v2: reserved words must be 0 */
   cfg.chunk_items = (uint64_t)chunk_items;
   cfg.host_threads = (uint32_t)host_threads;
   cfg.table_bytes_max = (uint64_t)table_bytes_max; /* 0: automatic (include/cordagpu.h) */
+  cfg.flags = (uint32_t)flags;                     /* CG_FLAG_RSA when gpuVerifier.gpuRsa is set */
   return cfg;
 }
 
 JNIEXPORT jlong JNICALL Java_net_corda_core_crypto_CryptoBatch_nativeOpen(JNIEnv* env, jobject self, jint dev,
                                                                          jlong chunk_items, jint host_threads,
-                                                                         jlong table_bytes_max) {
-  cg_config cfg = make_config(chunk_items, host_threads, table_bytes_max);
+                                                                         jlong table_bytes_max, jint flags) {
+  cg_config cfg = make_config(chunk_items, host_threads, table_bytes_max, flags);
   cfg.device = dev;
   cg_ctx* ctx = 0;
   int rc = cg_open(&ctx, &cfg);
@@ -55,10 +56,11 @@ JNIEXPORT void JNICALL Java_net_corda_core_crypto_CryptoBatch_nativeClose(JNIEnv
 /* One JVM process, every GPU of the node: a pool over the device list. */
 JNIEXPORT jlong JNICALL Java_net_corda_core_crypto_CryptoBatch_nativeOpenPool(JNIEnv* env, jobject self,
                                                                              jintArray devs, jlong chunk_items,
-                                                                             jint host_threads, jlong table_bytes_max) {
+                                                                             jint host_threads, jlong table_bytes_max,
+                                                                             jint flags) {
   jsize n = (*env)->GetArrayLength(env, devs);
   jint* d = (*env)->GetIntArrayElements(env, devs, 0);
-  cg_config cfg = make_config(chunk_items, host_threads, table_bytes_max);
+  cg_config cfg = make_config(chunk_items, host_threads, table_bytes_max, flags);
   cg_pool* pool = 0;
   int rc = cg_pool_open(&pool, (const int32_t*)d, (uint32_t)n, &cfg);
   (*env)->ReleaseIntArrayElements(env, devs, d, JNI_ABORT);

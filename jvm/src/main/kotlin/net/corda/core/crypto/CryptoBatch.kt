@@ -28,7 +28,7 @@ data class BatchItem(val publicKey: PublicKey, val signatureData: ByteArray, val
  * (NodeConfiguration.kt:33,98-101):
  *
  *   gpuVerifier { devices = [0, 1, 2, 3, 4, 5, 6, 7], minBatch = 4096, chunkItems = 0, hostThreads = 0,
- *                 tableBytesMax = 0 }
+ *                 tableBytesMax = 0, gpuRsa = false }
  *
  * devices: HIP ordinals this process drives (one: a cg_ctx; several: a cg_pool sharding every batch:
  *   every entry point works with either, see CryptoBatch.withHandles).
@@ -40,9 +40,13 @@ data class BatchItem(val publicKey: PublicKey, val signatureData: ByteArray, val
  * tableBytesMax: cg_config.table_bytes_max, HBM per device for the constant fixed-base tables (0:
  *   automatic: ~91 GB when the device has room, ~25 / ~6.9 GB when other processes share it; a node
  *   that runs several verifier processes per GPU sets e.g. 26000000000).
+ * gpuRsa: CG_FLAG_RSA in cg_config.flags: RSA_SHA256 (SHA256WITHRSAANDMGF1) signatures whose key the
+ *   engine's strict decode accepts (canonical X.509, 1024..4096-bit odd modulus, e < 2^32) are verified
+ *   on the GPU; everything else still comes back CG_UNSUPPORTED and goes to Crypto.doVerify (raiseForStatus).
  */
 data class GpuVerifierConfig(val devices: IntArray = intArrayOf(0), val minBatch: Int = 4096,
-                             val chunkItems: Long = 0, val hostThreads: Int = 0, val tableBytesMax: Long = 0) {
+                             val chunkItems: Long = 0, val hostThreads: Int = 0, val tableBytesMax: Long = 0,
+                             val gpuRsa: Boolean = false) {
     init {
         require(devices.isNotEmpty() && devices.all { it >= 0 }) { "gpuVerifier.devices: at least one ordinal >= 0" }
         require(minBatch >= 0 && chunkItems >= 0 && hostThreads >= 0 && tableBytesMax >= 0) { "gpuVerifier: negative setting" }
@@ -57,7 +61,8 @@ data class GpuVerifierConfig(val devices: IntArray = intArrayOf(0), val minBatch
                 minBatch = opt("minBatch", g::getInt, 4096),
                 chunkItems = opt("chunkItems", g::getLong, 0L),
                 hostThreads = opt("hostThreads", g::getInt, 0),
-                tableBytesMax = opt("tableBytesMax", g::getLong, 0L))
+                tableBytesMax = opt("tableBytesMax", g::getLong, 0L),
+                gpuRsa = g.hasPath("gpuRsa") && g.getBoolean("gpuRsa"))
         }
     }
 }
@@ -65,8 +70,10 @@ data class GpuVerifierConfig(val devices: IntArray = intArrayOf(0), val minBatch
 object CryptoBatch {
     init { System.loadLibrary("cordagpu_jni") }           // links libcordagpu.so
 
-    private external fun nativeOpen(device: Int, chunkItems: Long, hostThreads: Int, tableBytesMax: Long): Long
-    private external fun nativeOpenPool(devices: IntArray, chunkItems: Long, hostThreads: Int, tableBytesMax: Long): Long
+    private const val CG_FLAG_RSA = 2                     // include/cordagpu.h cg_config.flags
+    private external fun nativeOpen(device: Int, chunkItems: Long, hostThreads: Int, tableBytesMax: Long, flags: Int): Long
+    private external fun nativeOpenPool(devices: IntArray, chunkItems: Long, hostThreads: Int, tableBytesMax: Long,
+                                        flags: Int): Long
     private external fun nativeClose(ctx: Long, pool: Long)
     private external fun nativeVerify(ctx: Long, pool: Long, keys: ByteBuffer, nKeys: Int, items: ByteBuffer, nItems: Long,
                                       arena: ByteBuffer, arenaLen: Long, mode: Int, status: ByteBuffer,
@@ -148,8 +155,9 @@ object CryptoBatch {
             rw.write {
                 if (ctx == 0L && pool == 0L) {
                     val c = config
-                    if (c.devices.size == 1) ctx = nativeOpen(c.devices[0], c.chunkItems, c.hostThreads, c.tableBytesMax)
-                    else pool = nativeOpenPool(c.devices, c.chunkItems, c.hostThreads, c.tableBytesMax)
+                    val flags = if (c.gpuRsa) CG_FLAG_RSA else 0
+                    if (c.devices.size == 1) ctx = nativeOpen(c.devices[0], c.chunkItems, c.hostThreads, c.tableBytesMax, flags)
+                    else pool = nativeOpenPool(c.devices, c.chunkItems, c.hostThreads, c.tableBytesMax, flags)
                 }
             }
         }
