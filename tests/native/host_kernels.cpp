@@ -1151,3 +1151,73 @@ extern "C" int t_row_parked_cmp(int family, uint32_t m) {
   return family == CG_CURVE_R1 ? cmp(std::integral_constant<int, CG_CURVE_R1>())
                                : cmp(std::integral_constant<int, CG_CURVE_K1>());
 }
+
+// ---------------------------------------------------------------- recodings, every radix
+// The digit recodings the ladders run, instantiated for the three fixed-base radixes the product
+// builds (Makefile VARIANTS and the default) whatever radix this host build's tables have, and for
+// the per-key configurations. digits[] receives the signed digits; returns their count (0: no such
+// configuration).
+template <int WB>
+static int sc_recode_digits(const uint32_t* a, int32_t* digits) {
+  constexpr int D = (253 + WB - 1) / WB + (253 % WB == 0 ? 1 : 0);
+  constexpr int Bits = WB <= 16 ? 16 : 32;  // EdWideCfg::kBBits
+  constexpr int NW = (D * Bits + 31) / 32;  // EdWideCfg::kBPackedWords
+  uint32_t packed[NW];
+  sc_recode_wb<WB, Bits>(packed, NW, a);
+  for (int t = 0; t < D; ++t) digits[t] = sc_digit_at<Bits>(packed, t);
+  return D;
+}
+extern "C" int t_sc_recode_wb(int wb, const uint32_t* a, int32_t* digits) {
+  switch (wb) {
+    case 26: return sc_recode_digits<26>(a, digits);
+    case 24: return sc_recode_digits<24>(a, digits);
+    case 22: return sc_recode_digits<22>(a, digits);
+    case 10: return sc_recode_digits<10>(a, digits);  // EdBTab's digits (sc_recode_w16)
+  }
+  return 0;
+}
+template <int W>
+static int ec_recode_g_digits(const u256w& a, int32_t* digits) {
+  constexpr int D = (257 + W - 1) / W;      // EC_WIDE_GDIGITS
+  constexpr int Bits = W <= 16 ? 16 : 32;   // EC_WIDE_GBITS
+  uint32_t packed[(D * Bits + 31) / 32];    // EC_WIDE_GPACKED
+  ec_recode_wide<W, D, false, Bits>(packed, a);
+  for (int t = 0; t < D; ++t) digits[t] = ec_digit_at<Bits>(packed, t);
+  return D;
+}
+// w = 26 / 24 / 22: the G digits of u1 (signed top digit, the carry out of bit 255 in the last one);
+// 10: EcGTab's (ec_recode_w10); 8: the per-key wide rows of u2 (top digit unsigned, in [0, 256]);
+// 6: the per-key radix-64 rows (ec_recode_w6)
+extern "C" int t_ec_recode(int w, const uint32_t* aw, int32_t* digits) {
+  u256w a;
+  for (int i = 0; i < 8; ++i) a.w[i] = aw[i];
+  switch (w) {
+    case 26: return ec_recode_g_digits<26>(a, digits);
+    case 24: return ec_recode_g_digits<24>(a, digits);
+    case 22: return ec_recode_g_digits<22>(a, digits);
+    case 10: {
+      uint32_t packed[EC_G_PACKED];
+      ec_recode_w10(packed, a);
+      for (int t = 0; t < EC_G_DIGITS; ++t) digits[t] = ec_digit10(packed, t);
+      return EC_G_DIGITS;
+    }
+    case 8: {
+      uint32_t packed[EC_WIDE_PACKED];
+      ec_recode_wide<EC_WIDE_W, EC_WIDE_DIGITS, true>(packed, a);
+      for (int t = 0; t < EC_WIDE_DIGITS; ++t) digits[t] = ec_digit10(packed, t);
+      return EC_WIDE_DIGITS;
+    }
+    case 6: {
+      uint32_t packed[EC_PACKED];
+      ec_recode_w6(packed, a);
+      for (int t = 0; t < EC_DIGITS; ++t) digits[t] = ec_digit6(packed, t);
+      return EC_DIGITS;
+    }
+  }
+  return 0;
+}
+// the fixed-base radix of this build's wide tables (ED_WIDE_BW = EC_WIDE_GW in every product build)
+extern "C" int t_wide_radix() {
+  static_assert(ED_WIDE_BW == EC_WIDE_GW, "one fixed-base radix per build");
+  return ED_WIDE_BW;
+}
