@@ -342,8 +342,15 @@ CG_HD void ec9_to_m29(f29& r, const f29& a) {
 }
 
 // Can H be 0 mod p? A filter on the value's low 29 bits (= limb 0's): |H| < 64 p, so H = k p with
-// |k| <= 64 and H mod 2^29 = k p mod 2^29: -k (r1, p = -1 mod 2^29) or -977 k (k1). False
-// positives ~2^-24 (k1) / ~2^-25 (r1) per lane; ec9_to_m29 + m29_iszero decide.
+// |k| <= 64 and H mod 2^29 = k p mod 2^29: -k (r1, p = -1 mod 2^29) or -977 k (k1). The test is
+// a window around 0, not the 129 values: r1 |x| <= 64, 129 of 2^29 = 2^-22.0 per addition if limb 0
+// of an honest H is uniform; k1 |x| <= 977 * 64, 125 057 of 2^29 = 2^-12.07. Counted in the host
+// build (EC_EXC_COUNT(3) below) over the Q-part additions of honest signatures of one key
+// (tests/golden/gen_ec_exceptional.py, 31 filtered additions per signature): k1 16 hits in 62 000
+// additions (2.6e-4, the window's rate: about 1 in 4 000 to 5 000 additions, 1% of the wide
+// items), r1 2 hits in 31 000 000 (6.5e-8, 2^-23.9: below the uniform figure). False positives
+// are H != 0: ec9_to_m29 + jac_madd_w's exact test decide, and the addition is the ordinary one
+// on the reduced form (tests/golden/ec_exceptional.json keeps such items for both curves).
 template <int C>
 CG_HD bool ec9_maybe_zero(const f29& a) {
   const uint32_t x = (0u - a.v[0]) & M29_MASK;
@@ -383,6 +390,7 @@ CG_HD void jac_madd9(Jac& r, bool& inf, const f29& x2, const f29& y2, bool neg, 
   ec9_sub(H, U2, r.X);
 #ifndef EC9_NO_EXACT  // (defined only by the instruction-count probe: the exact path compiled out)
   if (ec9_maybe_zero<C>(H)) {
+    EC_EXC_COUNT(3);
     Jac q;
     ec9_to_m29<C>(q.X, r.X);
     ec9_to_m29<C>(q.Y, r.Y);

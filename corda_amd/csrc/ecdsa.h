@@ -313,9 +313,20 @@ CG_HD void jac_dbl_w(Jac& r, const Jac& p) {
 #ifndef CG_EC_MADD_LAZY  // 0: round-3 v15 chains, 1: lazy 4HH + three-chain X3, 2: madd-2004-hmv (A/B)
 #define CG_EC_MADD_LAZY 2
 #endif
+// Host-build counters of the exceptional cases (tests/native/host_kernels.cpp, tests/test_ec_exceptional.py):
+// jac_madd_w's doublings taken [0], infinities produced [1] and loads into an infinite accumulator
+// [2], and jac_madd9's entries into the exact path [3] (ec9.h). Compiled out of the device build.
+// Defined here (an inline variable), so a host build needs no definition of its own.
+#ifdef FE_OP_COUNT
+inline uint64_t g_ec_exc[4] = {0, 0, 0, 0};
+#define EC_EXC_COUNT(I) (++g_ec_exc[I])
+#else
+#define EC_EXC_COUNT(I) ((void)0)
+#endif
 template <int C>
 CG_HD void jac_madd_w(Jac& r, bool& inf, const f29& x2, const f29& y2, bool neg, const EcConsts& K) {
   if (inf) {
+    EC_EXC_COUNT(2);
     r.X = x2;
     if (neg) m29_neg2<C, 0>(r.Y, y2);
     else r.Y = y2;
@@ -338,8 +349,10 @@ CG_HD void jac_madd_w(Jac& r, bool& inf, const f29& x2, const f29& y2, bool neg,
   if (m29_maybe_zero_semi<C, 0>(H)) {
     if (m29_zero_semi<C, 0>(H)) {
       if (m29_zero_semi<C, 0>(rr)) {
+        EC_EXC_COUNT(0);
         jac_dbl<C>(r, r);
       } else {
+        EC_EXC_COUNT(1);
         jac_set_inf<C>(r, K);
         inf = true;
       }
@@ -369,8 +382,10 @@ CG_HD void jac_madd_w(Jac& r, bool& inf, const f29& x2, const f29& y2, bool neg,
   if (m29_maybe_zero_semi<C, 0>(H)) {
     if (m29_zero_semi<C, 0>(H)) {
       if (m29_iszero<C, 0>(rr)) {
+        EC_EXC_COUNT(0);
         jac_dbl<C>(r, r);
       } else {
+        EC_EXC_COUNT(1);
         jac_set_inf<C>(r, K);
         inf = true;
       }

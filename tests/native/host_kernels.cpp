@@ -363,6 +363,9 @@ static int ecdsa_rows_verify(const uint8_t* arena, uint64_t lr, uint64_t key_off
   ecdsa_batch_inv<C, 1>(&ws, 1, 1u, K);
   kinit();
   ec_gwide_touch<C>(ws.a);
+#ifdef FE_OP_COUNT
+  memset(g_ec_exc, 0, sizeof g_ec_exc);  // the ladder's own (t_ec_exc_counts)
+#endif
   return (int)ecdsa_ladder_check<C>(ws.a, ws.b, ws.r, *ec_gwide_host<C>(), *TQ, K);
 }
 // Executed Montgomery products per ECDSA item and stage (the GPU path's own lane code, host build):
@@ -418,6 +421,19 @@ extern "C" int t_ecdsa_count(int scheme, const uint8_t* arena, uint64_t arena_le
   if (scheme == 3)
     return ecdsa_count<CG_CURVE_R1>(arena, lr, key_off, key_len, fmt, sig_off, sig_len, msg_off, msg_len, out);
   return ecdsa_count<CG_CURVE_K1>(arena, lr, key_off, key_len, fmt, sig_off, sig_len, msg_off, msg_len, out);
+}
+
+// The exceptional additions of the last t_ecdsa_verify_rows / t_ecdsa_verify_wide ladder (table builds
+// and the stages before it excluded): out[0] doublings taken inside jac_madd_w, [1] infinities it
+// produced, [2] loads into an infinite accumulator, [3] jac_madd9's entries into the exact path.
+extern "C" int t_ec_exc_counts(uint64_t* out) {
+#ifdef FE_OP_COUNT
+  memcpy(out, g_ec_exc, sizeof g_ec_exc);
+  return 0;
+#else
+  (void)out;
+  return -1;
+#endif
 }
 
 extern "C" int t_ecdsa_verify_rows(int scheme, const uint8_t* arena, uint64_t arena_len, uint64_t key_off,
@@ -750,6 +766,26 @@ extern "C" int t_ed_verify_wide(const uint32_t* aw, const uint32_t* sw, const ui
   return ed_encode_cmp(R, zi, sw);
 }
 
+// k_ec_wide_chain, then the k_ec_wide_rows lanes: the wide table of the key (xm, ym)
+template <int C>
+static void ec_wide_key_table(EcWideTab* TQ, EcWideScratch* WS, const f29& xm, const f29& ym, const EcConsts& K) {
+  static Jac jb[EC_WIDE_DIGITS];  // Jacobian chain, then affine bases
+  static EcAff ab[EC_WIDE_DIGITS];
+  Jac P = {xm, ym, K.one_p};
+  for (int j = 0; j < EC_WIDE_DIGITS; ++j) {
+    if (j > 0) jac_dbl_n<C>(P, P, EC_WIDE_W);
+    jb[j] = P;
+  }
+  jac_batch_to_affine<C>(ab, jb, EC_WIDE_DIGITS, WS->pre, K);
+  for (int j = 0; j < EC_WIDE_ROWS; ++j) {
+    const EcAff& base = ab[j < EC_WIDE_DIGITS ? j : EC_WIDE_DIGITS - 1];
+    for (int g = 0; g < EC_WIDE_ROW_LANES; ++g) {
+      const int e0 = g * (EC_WIDE_MULT / EC_WIDE_ROW_LANES), e1 = e0 + EC_WIDE_MULT / EC_WIDE_ROW_LANES;
+      ec_wide_row_build<C>(TQ->t[j], EcParkRow{TQ->t[j] + e0, WS->z + e0}, base, j == EC_WIDE_DIGITS, e0, e1, K);
+    }
+  }
+}
+
 // k_ec_gwide_init / k_ec_wide_chain / k_ec_wide_tab / k_ec_ladder_wide. counts (optional):
 // [0] ladder Montgomery products mod p per item, [1] table build per key (chain + rows).
 template <int C>
@@ -783,21 +819,7 @@ static int ecdsa_wide_verify(const uint8_t* arena, uint64_t lr, uint64_t key_off
 #ifdef FE_OP_COUNT
     g_m29_nmul[C][0] = g_m29_nmul[C][1] = 0;
 #endif
-    static Jac jb[EC_WIDE_DIGITS];  // k_ec_wide_chain: Jacobian chain, then affine bases
-    static EcAff ab[EC_WIDE_DIGITS];
-    Jac P = {xm, ym, K.one_p};
-    for (int j = 0; j < EC_WIDE_DIGITS; ++j) {
-      if (j > 0) jac_dbl_n<C>(P, P, EC_WIDE_W);
-      jb[j] = P;
-    }
-    jac_batch_to_affine<C>(ab, jb, EC_WIDE_DIGITS, WS->pre, K);
-    for (int j = 0; j < EC_WIDE_ROWS; ++j) {  // k_ec_wide_rows lanes
-      const EcAff& base = ab[j < EC_WIDE_DIGITS ? j : EC_WIDE_DIGITS - 1];
-      for (int g = 0; g < EC_WIDE_ROW_LANES; ++g) {
-        const int e0 = g * (EC_WIDE_MULT / EC_WIDE_ROW_LANES), e1 = e0 + EC_WIDE_MULT / EC_WIDE_ROW_LANES;
-        ec_wide_row_build<C>(TQ->t[j], EcParkRow{TQ->t[j] + e0, WS->z + e0}, base, j == EC_WIDE_DIGITS, e0, e1, K);
-      }
-    }
+    ec_wide_key_table<C>(TQ, WS, xm, ym, K);
 #ifdef FE_OP_COUNT
     build_count = g_m29_nmul[C][0];
 #endif
@@ -824,6 +846,7 @@ static int ecdsa_wide_verify(const uint8_t* arena, uint64_t lr, uint64_t key_off
 #ifdef FE_OP_COUNT
   g_m29_nmul[C][0] = g_m29_nmul[C][1] = 0;
   g_m29_nsqr[C] = 0;
+  memset(g_ec_exc, 0, sizeof g_ec_exc);  // the ladder's own (t_ec_exc_counts)
 #endif
   st = ecdsa_ladder_check_wide<C>(ws.a, ws.b, ws.r, *TG[C], *TQ, K);
 #ifdef FE_OP_COUNT
@@ -881,6 +904,55 @@ extern "C" int t_ecdsa_verify_wide(int scheme, const uint8_t* arena, uint64_t ar
   if (scheme == 3)
     return ecdsa_wide_verify<CG_CURVE_R1>(arena, lr, key_off, key_len, fmt, sig_off, sig_len, msg_off, msg_len, counts);
   return ecdsa_wide_verify<CG_CURVE_K1>(arena, lr, key_off, key_len, fmt, sig_off, sig_len, msg_off, msg_len, counts);
+}
+
+// The Q part of ecdsa_ladder_check_wide alone (its first loop, restated: the 32 additions over the
+// per-key wide table), for n candidate u2 (8 little-endian words each, below n) under one raw key
+// (64 bytes, x then y): out[i] = jac_madd9's entries into the exact path for candidate i. The table
+// is built once, with the lane functions ecdsa_wide_verify uses, so its entries are the device's bit
+// for bit. tests/golden/gen_ec_exceptional.py searches honest signatures for false positives of
+// the limb-0 filter (ec9_maybe_zero) with it. Returns 0, or the key's decode status.
+template <int C>
+static int ec_filter_search(const uint8_t* key, const uint32_t* u2, uint64_t n, uint8_t* out) {
+#ifdef FE_OP_COUNT
+  kinit();
+  const EcConsts& K = g_K[C];
+  static EcWideTab* TQ = new EcWideTab;
+  static EcWideScratch* WS = new EcWideScratch;
+  alignas(8) uint8_t arena[64];
+  memcpy(arena, key, 64);
+  f29 xm, ym;
+  const uint32_t st = ec_key_decode_bytes<C>(xm, ym, arena, 64, 0, 64, 0, K);
+  if (st) return (int)st;
+  ec_wide_key_table<C>(TQ, WS, xm, ym, K);
+  for (uint64_t i = 0; i < n; ++i) {
+    u256w b;
+    memcpy(b.w, u2 + 8 * i, 32);
+    uint32_t dq[EC_WIDE_PACKED];
+    ec_recode_wide<EC_WIDE_W, EC_WIDE_DIGITS, true>(dq, b);
+    Jac R;
+    jac_set_inf<C>(R, K);
+    bool inf = true;
+    g_ec_exc[3] = 0;
+    for (int j = 0; j < EC_WIDE_DIGITS; ++j) {
+      const int d = ec_digit10(dq, j);
+      if (d == 0) continue;
+      f29 x, y;
+      const int a = d < 0 ? -d : d;
+      if (a > EC_WIDE_MULT) ec_pick(x, y, TQ->t[EC_WIDE_DIGITS], a - EC_WIDE_MULT);
+      else ec_pick(x, y, TQ->t[j], a);
+      jac_madd9<C>(R, inf, x, y, d < 0, K);
+    }
+    out[i] = (uint8_t)g_ec_exc[3];
+  }
+  return 0;
+#else
+  (void)key; (void)u2; (void)n; (void)out;
+  return -1;
+#endif
+}
+extern "C" int t_ec_filter_search(int scheme, const uint8_t* key, const uint32_t* u2, uint64_t n, uint8_t* out) {
+  return scheme == 3 ? ec_filter_search<CG_CURVE_R1>(key, u2, n, out) : ec_filter_search<CG_CURVE_K1>(key, u2, n, out);
 }
 
 // jac_madd_w (the wide ladder's mixed addition: lazy sums, inf flag, Z3 = Z1 * 2H) against
