@@ -1,7 +1,7 @@
 // RSA_SHA256 (Corda scheme 1, BouncyCastle "SHA256WITHRSAANDMGF1": RSASSA-PSS, SHA-256, MGF1-SHA256,
 // 32-byte salt, trailer 0xBC) for host and device: the strict key decode, the per-key Montgomery
 // constants and the EMSA-PSS check of BC 1.57 PSSSigner.verifySignature as corda_amd/hostverify.py
-// restates it. The lane-cooperative modular exponentiation lives in verify_rsa.hip; the scalar one
+// restates it. The lane-cooperative modular exponentiation lives in rsa_wave.h; the scalar one
 // here serves the key preparation (one lane per key) and the host tests (tests/native/host_rsa.cpp).
 //
 // Accepted keys (everything else keeps CG_UNSUPPORTED and goes to the host fallback, which owns the

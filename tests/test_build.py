@@ -57,9 +57,15 @@ def test_makefile_lists_every_header_the_library_includes():
     got = local_includes(os.path.join(csrc, "cordagpu.cpp"), set())
     assert got - hdrs - cpp_hdrs == set(), "cordagpu.o does not depend on: %s" % sorted(got - hdrs - cpp_hdrs)
     for src in ("verify.hip", "verify_ed.hip", "verify_ec.hip", "hash.hip", "txpipe.hip", "plan_sort.hip",
-                "filtered.hip"):
+                "filtered.hip", "verify_rsa.hip"):
         got = local_includes(os.path.join(csrc, src), set())
         assert got - hdrs == set(), f"{src}: missing from HDRS: {sorted(got - hdrs)}"
+    assert "rsa_wave.h" in local_includes(os.path.join(csrc, "verify_rsa.hip"), set())
+    # the test-only device library over rsa_wave.h: the product's flags, rebuilt when the header changes
+    tmk = open(os.path.join(ROOT, "tests", "native", "Makefile")).read()
+    flags = lambda text: re.search(r"^HIPFLAGS\s*\?=\s*(.*)$", text, re.M).group(1).split()  # noqa: E731
+    assert flags(tmk) == flags(mk)
+    assert re.search(r"^\$\(OUT\):.*rsa_wave_gpu\.hip.*corda_amd/csrc/rsa_wave\.h", tmk, re.M)
     # the radix builds: each variant object of each radix-dependent source
     assert set(_make_var(mk, "VARIANT_SRCS")) == {"verify", "verify_ed", "verify_ec", "plan_sort"}
     assert set(_make_var(mk, "VARIANTS")) == {"24", "22"}
