@@ -9,7 +9,6 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
-#include <condition_variable>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -27,6 +26,7 @@
 #include "pool.h"
 #include "rsa.h"
 #include "table_budget.h"
+#include "txsig_plan.h"
 
 // the other builds of the radix-dependent kernels (Makefile VARIANTS; engine.h EngineVariant)
 namespace cg24 {
@@ -59,6 +59,18 @@ int hip_fail(hipError_t e, const char* where) {
     hipError_t _e = (expr);                \
     if (_e != hipSuccess) return hip_fail(_e, where); \
   } while (0)
+
+// Environment switches (A/B runs). A caller keeps the value in a function-local static, so each
+// is read once per process: flags are on with a leading '1' (default off) or off with a leading '0'
+// (default on); numbers are decimal.
+bool env_flag(const char* name, bool dflt) {
+  const char* v = getenv(name);
+  return v ? (dflt ? v[0] != '0' : v[0] == '1') : dflt;
+}
+uint64_t env_u64(const char* name, uint64_t dflt) {
+  const char* v = getenv(name);
+  return v ? (uint64_t)strtoull(v, nullptr, 10) : dflt;
+}
 
 struct DevBuf {
   void* p = nullptr;
@@ -126,13 +138,13 @@ struct cg_ctx {
   // host-buffer verify: a copy stream and one event per pipeline chunk (H2D of chunk k+1 overlaps
   // the verify of chunk k); timing events for cg_stats
   hipStream_t copy = nullptr;
-  // the tx-signature host path's second copy stream (chunk 0's bytes while the key-use counts are
-  // sampled) and a pinned buffer for those counts (a pinned copy does not queue behind a pageable one)
+  // a second stream on a hardware queue of its own, idle in every default schedule: the
+  // CG_HOST_TRACE marker "tables built" waits there (launch_chunked), and CG_DEV_FRONT_STREAM runs a
+  // device call's second front on it
   hipStream_t copy2 = nullptr;
-  // the exact key-use count (many keys): per host thread a byte counter per key (a wrap to 0 logs
-  // the key in ovf: +256), kept across calls so a call does not page-fault 16 fresh arrays in
-  std::vector<std::vector<uint8_t>> cnt8;
-  std::vector<std::vector<uint32_t>> ovf;
+  // the exact key-use count's per-thread byte counters (txsig_plan.h), kept across calls so a call
+  // does not page-fault 16 fresh arrays in
+  cg::CountScratch count_scratch;
   // host threads for the host paths' scans (host_pool.h), started on the first large call and sized
   // by the budget (host_budget.h: cg_config.host_threads, CG_HOST_THREADS, or the CPU quota divided
   // by the contexts open in the process), re-sized when the budget changes
@@ -140,12 +152,10 @@ struct cg_ctx {
   uint32_t host_req = 0;   // cg_config.host_threads
   uint32_t quota = 1;      // the process's CPUs at cg_open
   bool counted = false;    // included in g_live_ctx
-  uint32_t* pin_counts = nullptr;
-  size_t pin_counts_cap = 0;
   std::vector<hipEvent_t> seg;
   hipEvent_t tev[4] = {};
   std::vector<hipEvent_t> segt;  // CG_HOST_TRACE: timing events behind each chunk's copy
-  std::vector<hipEvent_t> segtab;  // CG_SPLIT_COPY: chunk k's signature-table slice landed
+  std::vector<hipEvent_t> segtab;  // the host tx-signature path: chunk k's signature-table slice landed
   hipEvent_t backt[2] = {nullptr, nullptr};  // CG_HOST_TRACE: chunk 0's back enqueued / tables ready
   std::vector<hipEvent_t> fbt;  // CG_HOST_TRACE: per chunk, the main stream reaching its front / its back's end
   std::vector<double> fbh;      // host ms at which chunk k's front kernels were enqueued
@@ -283,10 +293,7 @@ hipError_t order_out(cg_ctx* c, hipStream_t s) {
 // caller's stream wait for the call's end, so the call stays ordered on the caller's stream.
 // CG_STREAM_BRIDGE=0: run on the caller's stream itself (A/B).
 hipStream_t stream_of(cg_ctx* c, void* hip_stream) {
-  static const bool bridge = [] {
-    const char* v = getenv("CG_STREAM_BRIDGE");
-    return !(v && v[0] == '0');
-  }();
+  static const bool bridge = env_flag("CG_STREAM_BRIDGE", true);
   c->caller = nullptr;
   if (!hip_stream || (hipStream_t)hip_stream == c->stream) return c->stream;
   if (!bridge || !c->bridge || hipEventRecord(c->bridge, (hipStream_t)hip_stream) != hipSuccess ||
@@ -297,11 +304,7 @@ hipStream_t stream_of(cg_ctx* c, void* hip_stream) {
 }
 
 // Equal chunks of at most c->chunk items.
-uint64_t chunk_of(const cg_ctx* c, uint64_t n) {
-  if (n <= c->chunk) return n ? n : 1;
-  const uint64_t k = (n + c->chunk - 1) / c->chunk;
-  return (n + k - 1) / k;
-}
+uint64_t chunk_of(const cg_ctx* c, uint64_t n) { return cg::equal_chunk(c->chunk, n); }
 
 // Key and item workspace for n_keys keys and chunks of ws_items items, plus the wide-table pools
 // for a call of call_items items (0: none). Growing them waits for the device (cg_reserve ahead
@@ -378,20 +381,12 @@ hipError_t ensure_ws(cg_ctx* c, uint32_t n_keys, uint64_t ws_items, uint64_t cal
 
 // The wide pools a call may use: what ensure_ws reserved for it (none if the buffer is short).
 cg::WidePool wide_for(cg_ctx* c, uint32_t n_keys, uint64_t n_items) {
-  static const bool off = [] {  // CG_NO_WIDE_TABLES=1: never build wide tables (A/B runs)
-    const char* v = getenv("CG_NO_WIDE_TABLES");
-    return v && v[0] == '1';
-  }();
+  static const bool off = env_flag("CG_NO_WIDE_TABLES", false);  // =1: never build wide tables (A/B runs)
   if (off || c->wide.cap < c->eng->wide_bytes(n_keys, n_items, c->wide_max)) return cg::WidePool{};
   cg::WidePool p = c->eng->make_wide_pool(c->wide.p, n_keys, n_items, c->wide_max);
-  static const uint32_t min_ed = [] {  // CG_WIDE_MIN_USES_ED / _EC: override the thresholds (A/B runs)
-    const char* v = getenv("CG_WIDE_MIN_USES_ED");
-    return v ? (uint32_t)strtoul(v, nullptr, 10) : 0u;
-  }();
-  static const uint32_t min_ec = [] {
-    const char* v = getenv("CG_WIDE_MIN_USES_EC");
-    return v ? (uint32_t)strtoul(v, nullptr, 10) : 0u;
-  }();
+  // CG_WIDE_MIN_USES_ED / _EC: override the thresholds (A/B runs)
+  static const uint32_t min_ed = (uint32_t)env_u64("CG_WIDE_MIN_USES_ED", 0);
+  static const uint32_t min_ec = (uint32_t)env_u64("CG_WIDE_MIN_USES_EC", 0);
   if (min_ed) p.min_ed = min_ed;
   if (min_ec) p.min_ec = min_ec;
   return p;
@@ -438,27 +433,21 @@ hipError_t launch_chunked(cg_ctx* c, const cg_key* d_keys, uint32_t n_keys, cons
     return c->eng->launch_items_plan(d_keys, n_keys, d_items + at(k), cnt(k), d_status + at(k), c->keyprep.p, ws(k), s,
                                  &c->fork, &wp);
   };
+  // (the device tx-signature forms with both first chunks' items and plans before the table builds,
+  // as pre_plan does for the batch forms, measured slower: 388.3 vs 392.1 M sigs/s over 3 pairs,
+  // profiles/r06/preplan: chunk 0's Ed25519 ladder then starts earlier but shares the chip with chunk
+  // 1's ECDSA fronts, 12.5 vs 11.9 ms of ladder per step; the chip is already full in phase 1)
   const bool pre_plan = two && !prepare;
-  // CG_DEV_PRE_PLAN=1 (A/B, the device tx-signature forms): both first chunks' items and plans before
-  // the table builds, as pre_plan does for the batch forms, so that chunk 1's front is only its
-  // hashes. Measured slower (388.3 vs 392.1 M sigs/s over 3 pairs, profiles/r06/preplan): chunk 0's
-  // Ed25519 ladder then starts earlier but shares the chip with chunk 1's ECDSA fronts (12.5 vs
-  // 11.9 ms of ladder per step); the chip is already full in phase 1.
-  static const bool dev_pre_plan = [] {
-    const char* v = getenv("CG_DEV_PRE_PLAN");
-    return v && v[0] == '1';
-  }();
-  const bool pre_prep = two && prepare && !prepare_blocks && dev_pre_plan;
   double prep_ms = 0;  // CG_HOST_TRACE: the host's time in chunk k's prepare hook
   auto front = [&](uint64_t k) {
-    if (prepare && !(pre_prep && k < 2)) {
+    if (prepare) {
       const auto p0 = std::chrono::steady_clock::now();
       const hipError_t w = (*prepare)(k, at(k), cnt(k));
       prep_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - p0).count();
       if (w != hipSuccess) return w;
     }
     return c->eng->launch_items_front(d_keys, n_keys, d_items + at(k), cnt(k), d_arena, arena_len, mode, d_status + at(k),
-                                  c->keyprep.p, ws(k), s, d_msgs, msgs_len, &c->fork, &wp, (pre_plan || pre_prep) && k < 2);
+                                  c->keyprep.p, ws(k), s, d_msgs, msgs_len, &c->fork, &wp, pre_plan && k < 2);
   };
   // chunk k + 1's front (plan, hashes, ECDSA prep) before chunk k's back (ladders): the first
   // chunk's wait for the key tables is spent on the next chunk's fronts. Without a prepare hook the
@@ -466,27 +455,17 @@ hipError_t launch_chunked(cg_ctx* c, const cg_key* d_keys, uint32_t n_keys, cons
   // with one, the builds start first: they overlap the preparation of the first chunk.
   if (e == hipSuccess && pre_plan) e = plan(0);
   if (e == hipSuccess && pre_plan) e = plan(1);
-  for (uint64_t k = 0; k < 2 && pre_prep && e == hipSuccess; ++k) {
-    e = (*prepare)(k, at(k), cnt(k));
-    if (e == hipSuccess) e = plan(k);
-  }
   // The host forms start the table builds now, so that they overlap the first chunk's copies. The
   // device forms have no copy to hide: their builds start after the first chunk's plan
   // (launch_items_front), whose onesweep look-back otherwise stalls behind the builds (round 6,
   // device-resident headline: the first plan's last pass 0.2 -> 2.7 ms in some steps,
   // profiles/r06/bridge timeline). CG_DEV_TABS_FIRST=1: start them now in the device forms too (A/B).
-  static const bool dev_tabs_first = [] {
-    const char* v = getenv("CG_DEV_TABS_FIRST");
-    return v && v[0] == '1';
-  }();
+  static const bool dev_tabs_first = env_flag("CG_DEV_TABS_FIRST", false);
   if (e == hipSuccess && prepare && (prepare_blocks || dev_tabs_first)) e = c->eng->launch_key_tables(&c->fork, s);
   // CG_FRONT_AFTER_TABLES=1 (A/B): the first chunk's front waits for every key table, instead of
   // sharing the chip with the builds (both run at about half speed together:
   // profiles/r03/env_chains timelines)
-  static const bool after_tables = [] {
-    const char* v = getenv("CG_FRONT_AFTER_TABLES");
-    return v && v[0] == '1';
-  }();
+  static const bool after_tables = env_flag("CG_FRONT_AFTER_TABLES", false);
   if (e == hipSuccess && prepare && after_tables)
     for (int k = 0; k < 3 && e == hipSuccess; ++k) e = hipStreamWaitEvent(s, c->fork.ready[k], 0);
   auto back = [&](uint64_t k) {
@@ -528,11 +507,8 @@ hipError_t launch_chunked(cg_ctx* c, const cg_key* d_keys, uint32_t n_keys, cons
   // that front stream. Measured +0.9% (391.2 -> 394.6 M sigs/s, 3 of 3 pairs, profiles/r06/fstream), but
   // chunk 0's Ed25519 ladder then shares the chip with chunk 1's hashes (12.1 -> 13.3-13.9 ms of ladder
   // per step), so its launch time no longer measures the kernel: off by default
-  static const bool dev_front_stream = [] {
-    const char* v = getenv("CG_DEV_FRONT_STREAM");
-    return v && v[0] == '1';
-  }();
-  if (e == hipSuccess && dev_front_stream && two && nch == 2 && prepare && !prepare_blocks && !pre_prep && c->copy2 &&
+  static const bool dev_front_stream = env_flag("CG_DEV_FRONT_STREAM", false);
+  if (e == hipSuccess && dev_front_stream && two && nch == 2 && prepare && !prepare_blocks && c->copy2 &&
       c->fs[0] && c->fs[1]) {
     hipStream_t fs = c->copy2;
     e = front(0);
@@ -558,21 +534,8 @@ hipError_t launch_chunked(cg_ctx* c, const cg_key* d_keys, uint32_t n_keys, cons
   return rsa_pass(e);
 }
 
-// ---- host-buffer verify: which arena bytes each pipeline chunk needs
-struct Extent {
-  uint64_t lo = UINT64_MAX, hi = 0;
-  void add(uint64_t off, uint64_t len, uint64_t arena_len) {
-    if (off > arena_len) return;  // outside the arena: the kernels never read it (CG_NOT_RUN)
-    const uint64_t e = len > arena_len - off ? arena_len : off + len;
-    if (off < lo) lo = off;
-    if (e > hi) hi = e;
-  }
-  void merge(const Extent& o) {
-    if (o.lo < lo) lo = o.lo;
-    if (o.hi > hi) hi = o.hi;
-  }
-  bool empty() const { return lo >= hi; }
-};
+// ---- host-buffer verify: which arena bytes each pipeline chunk needs (txsig_plan.h)
+using cg::Extent;
 
 struct HostPlan {
   std::vector<uint64_t> first;  // chunk k = items [first[k], first[k+1])
@@ -604,34 +567,32 @@ void plan_host(cg_ctx* c, const cg_key* keys, uint32_t n_keys, const cg_item* it
   P.win.lo &= ~(uint64_t)15;  // the device window starts 16-aligned (kernels load aligned words)
 }
 
-// Copies the parts of [e.lo, e.hi) not yet resident (`have`: sorted disjoint intervals).
-hipError_t copy_missing(std::vector<std::pair<uint64_t, uint64_t>>& have, const Extent& e, const uint8_t* arena,
-                        uint8_t* dwin, uint64_t win_lo, hipStream_t s) {
-  if (e.empty()) return hipSuccess;
-  uint64_t cur = e.lo;
-  std::vector<std::pair<uint64_t, uint64_t>> gaps;
-  for (const auto& h : have) {
-    if (h.second <= cur) continue;
-    if (h.first >= e.hi) break;
-    if (h.first > cur) gaps.push_back({cur, h.first});
-    cur = h.second > cur ? h.second : cur;
-    if (cur >= e.hi) break;
-  }
-  if (cur < e.hi) gaps.push_back({cur, e.hi});
-  for (const auto& g : gaps) {
+// Copies the parts of [e.lo, e.hi) not yet resident.
+hipError_t copy_missing(cg::Resident& have, const Extent& e, const uint8_t* arena, uint8_t* dwin, uint64_t win_lo,
+                        hipStream_t s) {
+  for (const auto& g : have.missing(e)) {
     hipError_t r = hipMemcpyAsync(dwin + (g.first - win_lo), arena + g.first, g.second - g.first,
                                   hipMemcpyHostToDevice, s);
     if (r != hipSuccess) return r;
   }
-  have.push_back({e.lo, e.hi});
-  std::sort(have.begin(), have.end());
-  std::vector<std::pair<uint64_t, uint64_t>> m;
-  for (const auto& h : have) {
-    if (!m.empty() && h.first <= m.back().second) m.back().second = std::max(m.back().second, h.second);
-    else m.push_back(h);
-  }
-  have.swap(m);
   return hipSuccess;
+}
+
+// The device timings of a host call (tev[0..3]: start, first chunk ready, verify done, verdicts back).
+void fill_stats(cg_ctx* c, cg_stats* stats, uint64_t n_items, uint32_t n_keys, double ms_key_prep,
+                std::chrono::steady_clock::time_point t0) {
+  if (!stats) return;
+  float a = 0, b = 0, d = 0;
+  hipEventElapsedTime(&a, c->tev[0], c->tev[1]);
+  hipEventElapsedTime(&b, c->tev[1], c->tev[2]);
+  hipEventElapsedTime(&d, c->tev[2], c->tev[3]);
+  stats->n_items = n_items;
+  stats->n_keys = n_keys;
+  stats->ms_h2d = a;
+  stats->ms_key_prep = ms_key_prep;
+  stats->ms_verify = b;
+  stats->ms_d2h = d;
+  stats->ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
 
 // cg_verify_batch with the ctx lock held. On failure the status bytes are CG_NOT_RUN.
@@ -662,7 +623,7 @@ int verify_host_locked(cg_ctx* c, const cg_key* keys, uint32_t n_keys, const cg_
   HIP_TRY(order_in(c, s), "hipStreamWaitEvent");
   HIP_TRY(hipEventRecord(c->tev[0], s), "hipEventRecord");
   HIP_TRY(hipStreamWaitEvent(c->copy, c->tev[0], 0), "hipStreamWaitEvent");
-  std::vector<std::pair<uint64_t, uint64_t>> have;
+  cg::Resident have;
   if (n_keys)
     HIP_TRY(hipMemcpyAsync(c->keys.p, keys, sizeof(cg_key) * n_keys, hipMemcpyHostToDevice, c->copy), "H2D keys");
   HIP_TRY(copy_missing(have, P.keys, arena, dwin, P.win.lo, c->copy), "H2D key bytes");
@@ -692,19 +653,7 @@ int verify_host_locked(cg_ctx* c, const cg_key* keys, uint32_t n_keys, const cg_
   HIP_TRY(hipEventRecord(c->tev[3], s), "hipEventRecord");
   HIP_TRY(order_out(c, s), "hipEventRecord");
   HIP_TRY(hipStreamSynchronize(s), "hipStreamSynchronize");
-  if (stats) {
-    float a = 0, b = 0, d = 0;
-    hipEventElapsedTime(&a, c->tev[0], c->tev[1]);
-    hipEventElapsedTime(&b, c->tev[1], c->tev[2]);
-    hipEventElapsedTime(&d, c->tev[2], c->tev[3]);
-    stats->n_items = n_items;
-    stats->n_keys = n_keys;
-    stats->ms_h2d = a;
-    stats->ms_key_prep = 0;
-    stats->ms_verify = b;
-    stats->ms_d2h = d;
-    stats->ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  }
+  fill_stats(c, stats, n_items, n_keys, 0, t0);
   return CG_OK;
 }
 
@@ -811,10 +760,7 @@ int cg_open(cg_ctx** out, const cg_config* cfg) {
   // CG_STREAM_PRIORITY=1 (A/B): the context's stream at the device's highest priority, so its
   // blocks (the plan sort's decoupled look-back above all) dispatch ahead of the side streams'
   // table builds
-  static const bool prio = [] {
-    const char* v = getenv("CG_STREAM_PRIORITY");
-    return v && v[0] == '1';
-  }();
+  static const bool prio = env_flag("CG_STREAM_PRIORITY", false);
   int lo_pri = 0, hi_pri = 0;
   hipError_t e = hipSuccess;
   if (prio && hipDeviceGetStreamPriorityRange(&lo_pri, &hi_pri) == hipSuccess)
@@ -835,8 +781,7 @@ int cg_open(cg_ctx** out, const cg_config* cfg) {
   // hashes: gpurun_out/ab_mask), kept for A/B runs.
   {
     hipDeviceProp_t prop;
-    const char* mk = getenv("CG_MASKED_SIDE_STREAMS");
-    const bool masked = mk && mk[0] == '1' && hipGetDeviceProperties(&prop, c->device) == hipSuccess &&
+    const bool masked = env_flag("CG_MASKED_SIDE_STREAMS", false) && hipGetDeviceProperties(&prop, c->device) == hipSuccess &&
                         prop.multiProcessorCount > 0;
     std::vector<uint32_t> mask(masked ? (prop.multiProcessorCount + 31) / 32 : 0, 0u);
     for (int cu = 0; masked && cu < prop.multiProcessorCount; ++cu) mask[cu / 32] |= 1u << (cu % 32);
@@ -865,8 +810,7 @@ int cg_open(cg_ctx** out, const cg_config* cfg) {
   // plain streams (A/B).
   {
     hipDeviceProp_t prop;
-    const char* sh = getenv("CG_COPY_QUEUE_SHARED");
-    const bool own = !(sh && sh[0] == '1') && hipGetDeviceProperties(&prop, c->device) == hipSuccess &&
+    const bool own = !env_flag("CG_COPY_QUEUE_SHARED", false) && hipGetDeviceProperties(&prop, c->device) == hipSuccess &&
                      prop.multiProcessorCount > 0;
     std::vector<uint32_t> mask(own ? (prop.multiProcessorCount + 31) / 32 : 0, 0u);
     for (int cu = 0; own && cu < prop.multiProcessorCount; ++cu) mask[cu / 32] |= 1u << (cu % 32);
@@ -945,7 +889,6 @@ void cg_close(cg_ctx* c) {
   for (hipEvent_t e : c->fbt) hipEventDestroy(e);
   for (hipEvent_t e : c->backt)
     if (e) hipEventDestroy(e);
-  if (c->pin_counts) hipHostFree(c->pin_counts);
   for (hipEvent_t e : c->seg) hipEventDestroy(e);
   for (int k = 0; k < 4; ++k)
     if (c->tev[k]) hipEventDestroy(c->tev[k]);
@@ -1369,12 +1312,6 @@ static int verify_transactions_host_locked(cg_ctx* c, const cg_tx* txs, uint64_t
 }
 
 // ---------------------------------------------------------------- signatures over known tx ids
-// the host tx-signature forms split a large call into at least this many chunks besides the smaller
-// first one (CG_TXSIG_FIRST_DIV): round 6 A/B on the configs[4] shard, 1/6 + 4 / 1/6 + 3 / 1/6 + 2
-// chunks = 345.4 / 351.3 / 334.7 M sigs/s over 3 rounds (profiles/r06/h2hchunks)
-#define CG_TXSIG_MIN_CHUNKS 3u
-#define CG_TXSIG_COUNT_SAMPLE 32u  // hot-key calls: 1 in 32 (blocks of 8 records): plan 3.0 -> 1.4-1.8 ms, 235 -> 237 / 247 M (profiles/r03/env_fd12)
-#define CG_TXSIG_SAMPLE_BLOCK 8u
 // The spliced-message slot of a template set: the longest prefix || id || suffix, 16-aligned.
 static uint64_t tmpl_slot(const cg_signable_tmpl* tmpls, uint32_t n_tmpls) {
   uint64_t maxlen = 0;
@@ -1445,583 +1382,70 @@ static hipError_t launch_txsig(cg_ctx* c, const cg_key* d_keys, uint32_t n_keys,
   return e;
 }
 
-// cg_verify_tx_signatures with the ctx lock held. Host side, in order: the key table and key bytes,
-// the template bytes, the ids and the signature table (everything the key tables and the plans
-// need), then the signature bytes chunk by chunk, each copy issued just before its chunk's front
-// so that the key-table builds and the previous chunk's kernels run during it.
-// The 12-byte form (cg_verify_tx_signatures_packed): sigs is null, sigs12 the table, the signatures
-// dense in sig_bytes. On the device they follow the caller's arena at sig_region (16-aligned), so the
-// kernels address every byte by an absolute arena offset as in the 24-byte form; a key or template
-// that lies outside [0, arena_len) is moved out of the extended arena too (never reads a signature).
-static int verify_txsig_host_locked(cg_ctx* c, const cg_key* keys, uint32_t n_keys, const uint8_t* ids,
-                                    uint64_t n_ids, const cg_txsig* sigs, uint64_t n_sigs,
-                                    const cg_signable_tmpl* tmpls, uint32_t n_tmpls, const uint8_t* arena,
-                                    uint64_t arena_len, uint32_t mode, uint8_t* status_out, cg_stats* stats,
-                                    const cg_txsig_packed* sigs12 = nullptr, const uint8_t* sig_bytes = nullptr,
-                                    uint64_t sig_bytes_len = 0) {
-  const auto t0 = std::chrono::steady_clock::now();
-  const bool packed = sigs12 != nullptr;
-  const size_t rec_bytes = packed ? sizeof(cg_txsig_packed) : sizeof(cg_txsig);
-  const uint64_t caller_len = arena_len;
-  const uint64_t sig_region = packed ? ((arena_len + 15) & ~(uint64_t)15) : 0;
-  if (packed) arena_len = sig_region + sig_bytes_len;  // what the kernels see
-  std::vector<cg_key> keys_fix;
-  std::vector<cg_signable_tmpl> tmpls_fix;
-  if (packed) {  // out-of-arena keys / templates stay out of range in the extended arena
-    auto out = [&](uint64_t off, uint64_t len) { return off > caller_len || len > caller_len - off; };
-    for (uint32_t k = 0; k < n_keys; ++k)
-      if (out(keys[k].off, keys[k].len)) {
-        if (keys_fix.empty()) keys_fix.assign(keys, keys + n_keys);
-        keys_fix[k].off = UINT64_MAX;
-      }
-    for (uint32_t k = 0; k < n_tmpls; ++k)
-      if (out(tmpls[k].prefix_off, tmpls[k].prefix_len) || out(tmpls[k].suffix_off, tmpls[k].suffix_len)) {
-        if (tmpls_fix.empty()) tmpls_fix.assign(tmpls, tmpls + n_tmpls);
-        tmpls_fix[k].prefix_off = UINT64_MAX;
-      }
-    if (!keys_fix.empty()) keys = keys_fix.data();
-    if (!tmpls_fix.empty()) tmpls = tmpls_fix.data();
+static double ms_since(std::chrono::steady_clock::time_point t0) {
+  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+// CG_HOST_TRACE=1: per-chunk host timings of a host tx-signature call to stderr (extent scan, each
+// copy call's return) and, after the call, where the device was when (timing events behind each
+// chunk's copy, front and back). Off: every member returns at once and records nothing.
+struct HostTrace {
+  cg_ctx* c;
+  const std::chrono::steady_clock::time_point t0;
+  const bool on;
+  std::vector<double> ht;  // per chunk: the scan's start, the scan, the table slice's copy call (ms)
+
+  double ms() const { return on ? ms_since(t0) : 0; }
+  // the events launch_chunked and the feed record for nch chunks
+  hipError_t begin(uint64_t nch) {
+    c->htrace = on;
+    if (!on) return hipSuccess;
+    hipError_t e = hipSuccess;
+    for (int q = 0; q < 2 && e == hipSuccess; ++q)
+      if (!c->backt[q]) e = hipEventCreate(&c->backt[q]);
+    while (e == hipSuccess && c->fbt.size() < 3 * nch) {
+      hipEvent_t ev;
+      e = hipEventCreate(&ev);
+      if (e == hipSuccess) c->fbt.push_back(ev);
+    }
+    c->fbh.assign(nch, 0.0);
+    ht.assign(3 * nch, 0.0);
+    return e;
   }
-  // a record's key index, either table (the count passes)
-  auto key_at = [&](uint64_t i) -> uint32_t { return packed ? sigs12[i].key_idx : sigs[i].key_idx; };
-  if (c->fault) return fail(CG_ERR_DEVICE, "cg_verify_tx_signatures: device fault (injected by cg_pool_inject_fault)");
-  HIP_TRY(hipSetDevice(c->device), "hipSetDevice");
-  // chunks: the device chunk, but at least CG_TXSIG_MIN_CHUNKS of them for a large call unless the
-  // caller set cg_config.chunk_items (the first chunk's copy is the part nothing overlaps; measured on
-  // the configs[4] shard: 2 chunks 190.7M, 3 200.8M, 4 207.7M, 6 190.0M sigs/s,
-  // profiles/r03/chunks_v1)
-  uint64_t per = chunk_of(c, n_sigs);
-  if (!c->chunk_set && n_sigs >= CG_TXSIG_MIN_CHUNKS * (1ull << 20)) {
-    const uint64_t alt = (n_sigs + CG_TXSIG_MIN_CHUNKS - 1) / CG_TXSIG_MIN_CHUNKS;
-    if (alt < per) per = alt;
-  }
-  // chunk bounds: with a first-chunk divisor D > 1 (CG_TXSIG_FIRST_DIV, default 6; 0 or 1: equal
-  // chunks of `per`) the first chunk is 1/D of the call and the rest is split into as many chunks as
-  // the equal split would make: the first copy is the part nothing hides, and at 1/6 it lands as
-  // the key-table builds finish (headline A/B, 4 pairs: 257.0 -> 262.9 M sigs/s; 1/5 neutral, 1/7
-  // and 1/8 -3%: their fronts then share the chip with the builds; profiles/r03/env_fd15*)
-  std::vector<uint64_t> bounds;
-  {
-    static const uint64_t first_div = [] {
-      const char* v = getenv("CG_TXSIG_FIRST_DIV");
-      return v ? (uint64_t)strtoull(v, nullptr, 10) : 6ull;
-    }();
-    const uint64_t k0 = (n_sigs + per - 1) / per;
-    if (first_div > 1 && k0 > 1) {
-      const uint64_t f0 = n_sigs / first_div, rest = n_sigs - f0, kr = k0;
-      bounds.push_back(0);
-      bounds.push_back(f0);
-      for (uint64_t k = 1; k <= kr; ++k) bounds.push_back(f0 + rest * k / kr);
-    } else {
-      for (uint64_t k = 0; k <= k0; ++k) bounds.push_back(k == k0 ? n_sigs : k * per);
-    }
-    per = 0;
-    for (size_t k = 0; k + 1 < bounds.size(); ++k) per = std::max(per, bounds[k + 1] - bounds[k]);
-  }
-  const uint64_t nch = bounds.size() - 1;
-  // arena extents: key bytes + template bytes (the header), then each chunk's signature bytes
-  Extent head, win;
-  for (uint32_t k = 0; k < n_keys; ++k) head.add(keys[k].off, keys[k].len, caller_len);
-  for (uint32_t k = 0; k < n_tmpls; ++k) {
-    head.add(tmpls[k].prefix_off, tmpls[k].prefix_len, caller_len);
-    head.add(tmpls[k].suffix_off, tmpls[k].suffix_len, caller_len);
-  }
-  // Key-use counts for the table modes from a 1-in-CG_TXSIG_COUNT_SAMPLE sample of the signature
-  // table (16 host threads; the modes change only speed, never a verdict), every key at least 1 so
-  // that each key an unsampled signature may use has its row-0 table. Each chunk's byte extents are
-  // scanned just before its copy, while the device works on the chunks before it.
-  std::vector<uint32_t> counts(n_keys ? n_keys : 1, 0u);
-  // the budget's host threads (host_budget.h), on the context's pool (spawning 16 threads per scan
-  // cost 0.35-0.5 ms a round)
-  const uint64_t nt = host_threads_of(c, n_sigs);
-  auto par = [&](uint64_t m, const std::function<void(uint64_t)>& fn) { host_par(c, m, fn); };
-  auto sample_counts = [&] {
-    // 1 in S signatures counted (CG_TXSIG_SAMPLE, a power of two, overrides): S = 32 when keys average
-    // at least 256 uses (every key far above the 32-use full-table threshold), else 8: at S = 32 an
-    // unsampled key could not be told from one at the threshold, and a long-tailed key mix (Zipf
-    // over 1M keys) built full tables for every used key (125 -> 55 M sigs/s, profiles/r03/v12)
-    static const uint32_t S_env = [] {
-      const char* v = getenv("CG_TXSIG_SAMPLE");
-      const uint32_t x = v ? (uint32_t)strtoul(v, nullptr, 10) : 0u;
-      return x && (x & (x - 1)) == 0 ? x : 0u;
-    }();
-    // Round 4: 1 (exact counts) instead of 1 in 8 when keys are many. With the quarter mode from 3
-    // uses, an unsampled key (unused, or used a few times) could not be given a mode: row 0 for all
-    // of them left ~20% of the 2^20-distinct-key leg's keys (12 uses) on the Horner ladder, quarter
-    // tables for all of them built tables for the Zipf leg's ~900k unused keys (125 -> 108 M sigs/s)
-    const uint32_t S = S_env ? S_env : n_sigs >= 256ull * (n_keys ? n_keys : 1) ? CG_TXSIG_COUNT_SAMPLE : 1u;
-    // CG_TXSIG_SAMPLE_BLOCK (A/B): consecutive records per sample. 8 reads an eighth of the table's
-    // cache lines instead of all of them (every 8th 24-B record): the pass went 5.3 -> 2.8 ms on the
-    // configs[4] shard, 218 -> 238 M sigs/s (profiles/r03/env_ec3); a key the block sampling
-    // under-counts only lands in a smaller table mode, whose ladders run on the side streams
-    static const uint32_t B = [] {
-      const char* v = getenv("CG_TXSIG_SAMPLE_BLOCK");
-      const uint32_t x = v ? (uint32_t)strtoul(v, nullptr, 10) : CG_TXSIG_SAMPLE_BLOCK;
-      return x >= 1 && x <= 64 ? x : CG_TXSIG_SAMPLE_BLOCK;
-    }();
-    if (S == 1) {  // exact: byte counters per thread (1 MB for 2^20 keys, cache-resident), wraps logged
-      c->cnt8.resize(nt);
-      c->ovf.resize(nt);
-      auto scan8 = [&](uint64_t t) {
-        std::vector<uint8_t>& c8 = c->cnt8[t];
-        if (c8.size() < n_keys) c8.resize(n_keys);
-        memset(c8.data(), 0, n_keys);
-        std::vector<uint32_t>& of = c->ovf[t];
-        of.clear();
-        uint8_t* cc = c8.data();
-        auto run = [&](const auto* tab) {
-          for (uint64_t i = n_sigs * t / nt; i < n_sigs * (t + 1) / nt; ++i) {
-            const uint32_t k = tab[i].key_idx;
-            if (k < n_keys && ++cc[k] == 0) of.push_back(k);
-          }
-        };
-        if (packed) run(sigs12);
-        else run(sigs);
-      };
-      par(nt, scan8);
-      auto sum = [&](uint64_t t) {
-        for (uint64_t k = n_keys * t / nt; k < n_keys * (t + 1) / nt; ++k) {
-          uint32_t v = 0;
-          for (uint64_t u = 0; u < nt; ++u) v += c->cnt8[u][k];
-          counts[k] = v;
-        }
-      };
-      par(nt, sum);
-      for (uint64_t t = 0; t < nt; ++t)
-        for (uint32_t k : c->ovf[t]) counts[k] += 256u;
-      return;
-    }
-    const uint64_t Bs = B;
-    const uint64_t ng = (n_sigs + (uint64_t)S * Bs - 1) / ((uint64_t)S * Bs);
-    std::vector<std::vector<uint32_t>> pc(nt > 1 ? nt : 0, std::vector<uint32_t>(n_keys ? n_keys : 1, 0u));
-    auto scan = [&](uint64_t t) {
-      uint32_t* cnt = nt > 1 ? pc[t].data() : counts.data();
-      for (uint64_t g = ng * t / nt; g < ng * (t + 1) / nt; ++g) {
-        // B consecutive records per group of S B, the block at a hashed position (no aliasing with
-        // a layout that cycles through the keys); B > 1 reads fewer cache lines per sample
-        const uint64_t i0 = (g * S + (((uint32_t)g * 0x9E3779B1u) >> 24) % S) * Bs;
-        for (uint64_t i = i0; i < i0 + Bs && i < n_sigs; ++i) {
-          const uint32_t k = key_at(i);
-          if (k < n_keys) ++cnt[k];
-        }
-      }
-    };
-    if (nt == 1) {
-      scan(0);
-    } else {
-      par(nt, scan);
-      par(nt, [&](uint64_t t) {  // sum the per-thread counts, key ranges in parallel
-        for (uint64_t k = n_keys * t / nt; k < n_keys * (t + 1) / nt; ++k)
-          for (uint64_t u = 0; u < nt; ++u) counts[k] += pc[u][k];
-      });
-    }
-    // c sampled uses -> S (c + 3 sqrt(c) + 1): about three standard deviations above the unbiased
-    // S c, so a key whose true count clears a mode threshold is not sampled below it (two were not
-    // enough at 1 in 32: a few keys got full tables and a 0.18 ms full-table ladder per chunk,
-    // profiles/r03/v14; on the
-    // configs[4] shard the plain estimate put 2 of 4096 Ed25519 keys, true minimum 1 634 uses, under
-    // the 1 536 wide threshold: full tables and a 170 us pf ladder per chunk, profiles/r03/v5); an
-    // unsampled key counts min(S, 8): its row-0 table, so every key a signature may use has one
-    // In a hot call (1 in 32: keys average 256+ uses) every sampled key is counted up to the wide
-    // threshold: a few keys left in full-table mode cost a serial full-table launch per chunk (0.18
-    // ms, ~1.4% of the headline, profiles/r03/ab_der), a wide table costs about 230 items' work.
-    const cg::WidePool thr = c->eng->make_wide_pool(nullptr, n_keys, n_sigs, cg::kKeyWideMax);  // the wide thresholds
-    const uint64_t floor_hot = S >= CG_TXSIG_COUNT_SAMPLE ? (uint64_t)std::max(thr.min_ed, thr.min_ec) : 0u;
-    // The raised estimate only where it decides a wide table: below the wide threshold the plain
-    // S c decides row 0 against full tables (a wrong full table costs ~230 ns, a wrong row 0 ~7 ns
-    // per use; at 1 in 8 the raised estimate put every sampled key of the 2^20-distinct-key leg,
-    // ~12 uses each, in full mode: 22-row builds for ~1M keys, profiles/r04/kd)
-    for (uint32_t k = 0; k < n_keys; ++k) {
-      const uint64_t c = counts[k];
-      const uint64_t up = (uint64_t)S * (c + 3 * (uint64_t)std::ceil(std::sqrt((double)c)) + 1);
-      const uint64_t wmin = keys[k].scheme == CG_EDDSA_ED25519_SHA512 ? thr.min_ed : thr.min_ec;
-      uint64_t e = c ? (up >= wmin ? up : (uint64_t)S * c)
-                     : (S < 8u ? S : 8u);  // unsampled: row-0 tables (below the 32-use threshold)
-      if (c && e < floor_hot) e = floor_hot;
-      counts[k] = e > 0xfffffff0ull ? 0xfffffff0u : (uint32_t)e;
-    }
-  };
-  // chunk k's signature bytes and id bytes (exact: a threaded scan of its slice of the table). The
-  // 12-byte table: the chunk's stream bytes (the sum of round_up(sig_len, 4)) in `span`, its extent
-  // set once its stream offset is known (copy_table: the chunks before it summed)
-  auto chunk_extents = [&](uint64_t k, Extent& ext, Extent& idx, uint64_t& span) {
-    const uint64_t f = bounds[k], e = bounds[k + 1];
-    const uint64_t m = (e - f) < (1u << 16) ? 1 : nt;
-    std::vector<Extent> pe(m), pi(m);
-    std::vector<uint64_t> ps(m, 0);
-    auto scan = [&](uint64_t t) {
-      Extent a, b;  // thread-local until the end (the vector slots share cache lines)
-      uint64_t sp = 0;
-      const uint64_t i0 = f + (e - f) * t / m, i1 = f + (e - f) * (t + 1) / m;
-      if (packed) {
-        for (uint64_t i = i0; i < i1; ++i) {
-          sp += ((uint64_t)sigs12[i].sig_len + 3u) & ~(uint64_t)3;
-          if (sigs12[i].tx_idx < n_ids) b.add(32ull * sigs12[i].tx_idx, 32, 32ull * n_ids);
-        }
-      } else {
-        for (uint64_t i = i0; i < i1; ++i) {
-          a.add(sigs[i].sig_off, sigs[i].sig_len, arena_len);
-          if (sigs[i].tx_idx < n_ids) b.add(32ull * sigs[i].tx_idx, 32, 32ull * n_ids);
-        }
-      }
-      pe[t] = a;
-      pi[t] = b;
-      ps[t] = sp;
-    };
-    par(m, scan);
-    span = 0;
-    for (uint64_t t = 0; t < m; ++t) {
-      ext.merge(pe[t]);
-      idx.merge(pi[t]);
-      span += ps[t];
-    }
-  };
-  // the 12-byte table: chunk k's first signature at stream offset cbase[k] (cbase[k + 1] is set when
-  // chunk k's table slice is staged)
-  std::vector<uint64_t> cbase(nch + 1, 0);
-  // the device arena mirrors [0, arena_len) (only referenced bytes are copied)
-  win.lo = 0;
-  win.hi = arena_len;
-  const uint64_t slot = tmpl_slot(tmpls, n_tmpls);
-  HIP_TRY(c->keys.ensure(sizeof(cg_key) * (n_keys ? n_keys : 1)), "hipMalloc(keys)");
-  HIP_TRY(c->h_sigs.ensure(rec_bytes * n_sigs), "hipMalloc(sigs)");
-  if (packed) HIP_TRY(c->sig12ws.ensure(cg::tx_sig12_scratch_bytes(per)), "hipMalloc(signature offsets)");
-  HIP_TRY(c->aux1.ensure(sizeof(uint32_t) * counts.size()), "hipMalloc(key use counts)");
-  HIP_TRY(c->h_ids.ensure(32 * (n_ids ? n_ids : 1)), "hipMalloc(ids)");
-  HIP_TRY(c->arena.ensure((win.hi - win.lo) + 16), "hipMalloc(arena window)");
-  HIP_TRY(c->status.ensure(n_sigs), "hipMalloc(status)");
-  HIP_TRY(ensure_txsig_ws(c, n_sigs, n_tmpls, slot), "hipMalloc(tx signature workspace)");
-  HIP_TRY(ensure_ws(c, n_keys, per, n_sigs), "hipMalloc(workspace)");
-  // CG_TXSIG_OVERLAP_PLAN=1 (A/B): sample the counts while chunk 0 copies. Measured slower on the
-  // configs[4] shard (197 / 205 vs 213 / 220 M sigs/s, profiles/r03/ab_sc): the sample pass slows
-  // 2x beside the pageable copy's staging and the late counts delay the key tables.
-  static const bool overlap = [] {
-    const char* v = getenv("CG_TXSIG_OVERLAP_PLAN");
-    return v && v[0] == '1';
-  }();
-  if (overlap && c->pin_counts_cap < counts.size()) {
-    if (c->pin_counts) HIP_TRY(hipHostFree(c->pin_counts), "hipHostFree");
-    c->pin_counts = nullptr;
-    c->pin_counts_cap = 0;
-    HIP_TRY(hipHostMalloc((void**)&c->pin_counts, sizeof(uint32_t) * counts.size(), hipHostMallocDefault),
-            "hipHostMalloc(key use counts)");
-    c->pin_counts_cap = counts.size();
-  }
-  while (c->seg.size() < nch + 1) {
-    hipEvent_t e;
-    HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming), "hipEventCreate");
-    c->seg.push_back(e);
-  }
-  hipStream_t s = c->stream;
-  uint8_t* dwin = (uint8_t*)c->arena.p;
-  const uint8_t* dbase = dwin - win.lo;  // kernels index the arena by absolute offsets
-  HIP_TRY(order_in(c, s), "hipStreamWaitEvent");
-  HIP_TRY(hipEventRecord(c->tev[0], s), "hipEventRecord");
-  HIP_TRY(hipStreamWaitEvent(c->copy, c->tev[0], 0), "hipStreamWaitEvent");
-  HIP_TRY(hipStreamWaitEvent(c->copy2, c->tev[0], 0), "hipStreamWaitEvent");
-  std::vector<std::pair<uint64_t, uint64_t>> have;
-  if (n_keys)
-    HIP_TRY(hipMemcpyAsync(c->keys.p, keys, sizeof(cg_key) * n_keys, hipMemcpyHostToDevice, c->copy), "H2D keys");
-  HIP_TRY(copy_missing(have, head, arena, dwin, win.lo, c->copy), "H2D key / template bytes");
-  std::vector<std::pair<uint64_t, uint64_t>> have_ids;  // id bytes already resident
-  std::vector<std::pair<uint64_t, uint64_t>> have_sig;  // the 12-byte form's stream bytes already resident
-  // chunk k: its slice of the signature table, the ids it references not yet resident (a caller that
-  // lists each transaction's signatures together ships each id once, with its first chunk), then its
-  // signature bytes, on copy stream cs; seg[k] marks the end
-  // CG_HOST_TRACE=1: per-chunk host timings to stderr (extent scan, each copy call's return)
-  static const bool htrace = [] {
-    const char* v = getenv("CG_HOST_TRACE");
-    return v && v[0] == '1';
-  }();
-  auto ms_since = [&] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); };
-  c->htrace = htrace;
-  for (int q = 0; q < 2 && htrace; ++q)
-    if (!c->backt[q]) HIP_TRY(hipEventCreate(&c->backt[q]), "hipEventCreate");
-  while (htrace && c->fbt.size() < 3 * nch) {
-    hipEvent_t ev;
-    HIP_TRY(hipEventCreate(&ev), "hipEventCreate");
-    c->fbt.push_back(ev);
-  }
-  if (htrace) c->fbh.assign(nch, 0.0);
-  // CG_SCAN_AHEAD=1 (A/B): chunk k+1's extent scan runs on the pool from a helper thread while this
-  // thread stages chunk k's copies (round 4 measured scanning ahead neutral to -1%, the copies'
-  // landing times did not move, profiles/r04/ahead; round 5's trace shows the main stream waiting
-  // 0.33 ms for chunk 1's bytes)
-  bool ct_active = false;  // the copy thread below issues the copies (it runs ahead: no scan-ahead helper)
-  static const bool scan_ahead = [] {
-    const char* v = getenv("CG_SCAN_AHEAD");
-    return v && v[0] == '1';
-  }();
-  std::thread ahead_thr;
-  uint64_t ahead_k = ~0ull, ahead_span = 0;
-  Extent ahead_ek, ahead_ik;
-  struct JoinAhead {  // every exit path joins the helper before the extents it writes go away
-    std::thread& t;
-    ~JoinAhead() {
-      if (t.joinable()) t.join();
-    }
-  } join_ahead{ahead_thr};
-  // chunk k's copies in two parts: the extent scan and the signature-table slice (all its plan
-  // needs), then the ids and signature bytes (what its hashes need); seg[k] marks the end
-  std::vector<Extent> ext_e(nch), ext_i(nch);
-  std::vector<double> ht(3 * nch, 0.0);
-  auto copy_table = [&](uint64_t k, hipStream_t cs) {
-    Extent& ek = ext_e[k];
-    Extent& ik = ext_i[k];
-    const double h0 = htrace ? ms_since() : 0;
-    uint64_t span = 0;
-    if (ahead_k == k) {
-      ahead_thr.join();
-      ek = ahead_ek;
-      ik = ahead_ik;
-      span = ahead_span;
-      ahead_k = ~0ull;
-    } else {
-      chunk_extents(k, ek, ik, span);
-    }
-    if (packed) {  // the chunk's stream bytes, clipped to the caller's buffer (past it: CG_NOT_RUN)
-      cbase[k + 1] = cbase[k] + span;
-      ek = Extent();
-      ek.add(cbase[k], span, sig_bytes_len);
-    }
-    if (scan_ahead && !ct_active && k + 1 < nch) {
-      ahead_k = k + 1;
-      ahead_ek = Extent();
-      ahead_ik = Extent();
-      ahead_thr = std::thread([&, k] { chunk_extents(k + 1, ahead_ek, ahead_ik, ahead_span); });
-    }
-    const double h1 = htrace ? ms_since() : 0;
-    const uint64_t first = bounds[k], cnt = bounds[k + 1] - bounds[k];
-    const hipError_t e =
-        packed ? hipMemcpyAsync((cg_txsig_packed*)c->h_sigs.p + first, sigs12 + first, rec_bytes * cnt,
-                                hipMemcpyHostToDevice, cs)
-               : hipMemcpyAsync((cg_txsig*)c->h_sigs.p + first, sigs + first, rec_bytes * cnt, hipMemcpyHostToDevice,
-                                cs);
+  // chunk k's scan ran from h0 to h1, then its table slice's copy call until now
+  void table_staged(uint64_t k, double h0, double h1) {
+    if (!on) return;
     ht[3 * k] = h0;
     ht[3 * k + 1] = h1 - h0;
-    ht[3 * k + 2] = htrace ? ms_since() - h1 : 0;
-    return e;
-  };
-  auto copy_bytes = [&](uint64_t k, hipStream_t cs) {
-    const Extent& ek = ext_e[k];
-    const double h2 = htrace ? ms_since() : 0;
-    hipError_t e = copy_missing(have_ids, ext_i[k], ids, (uint8_t*)c->h_ids.p, 0, cs);
-    const double h3 = htrace ? ms_since() : 0;
-    if (e == hipSuccess && packed) e = copy_missing(have_sig, ek, sig_bytes, dwin + sig_region, 0, cs);
-    else if (e == hipSuccess) e = copy_missing(have, ek, arena, dwin, win.lo, cs);
-    if (e == hipSuccess) e = hipEventRecord(c->seg[k], cs);
-    if (e == hipSuccess && htrace) {
-      while (c->segt.size() <= k) {
-        hipEvent_t ev;
-        if (hipEventCreate(&ev) != hipSuccess) break;
-        c->segt.push_back(ev);
-      }
-      if (c->segt.size() > k) e = hipEventRecord(c->segt[k], cs);
-    }
-    if (htrace)
-      fprintf(stderr, "[cg host] chunk %llu at %.3f: scan %.3f sigs %.3f (%.1f MB) ids %.3f arena %.3f (%.1f MB) ms\n",
-              (unsigned long long)k, ht[3 * k], ht[3 * k + 1], ht[3 * k + 2],
-              rec_bytes * (bounds[k + 1] - bounds[k]) / 1e6, h3 - h2, ms_since() - h3,
-              ek.empty() ? 0.0 : (ek.hi - ek.lo) / 1e6);
-    return e;
-  };
-  auto copy_chunk = [&](uint64_t k, hipStream_t cs) {
-    hipError_t e = copy_table(k, cs);
-    if (e == hipSuccess) e = copy_bytes(k, cs);
-    return e;
-  };
-  // The key-use counts gate only the key tables; chunk 0's bytes gate everything else. With
-  // `overlap`, chunk 0's copy (its own thread, second copy stream) runs while this thread samples
-  // the counts, which then go from the pinned buffer behind the key bytes on the first copy stream.
-  hipError_t pre_err = hipSuccess;
-  double ms_plan = 0;
-  if (overlap) {
-    std::thread pre([&] {
-      pre_err = hipSetDevice(c->device);
-      if (pre_err == hipSuccess) pre_err = copy_chunk(0, c->copy2);
-    });
-    sample_counts();
-    ms_plan = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    memcpy(c->pin_counts, counts.data(), sizeof(uint32_t) * counts.size());
-    const hipError_t e = hipMemcpyAsync(c->aux1.p, c->pin_counts, sizeof(uint32_t) * counts.size(),
-                                        hipMemcpyHostToDevice, c->copy);
-    pre.join();
-    HIP_TRY(e, "H2D key use counts");
-    HIP_TRY(pre_err, "H2D chunk 0");
-  } else {
-    sample_counts();
-    ms_plan = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    HIP_TRY(hipMemcpyAsync(c->aux1.p, counts.data(), sizeof(uint32_t) * counts.size(), hipMemcpyHostToDevice,
-                           c->copy),
-            "H2D key use counts");
+    ht[3 * k + 2] = ms() - h1;
   }
-  HIP_TRY(hipEventRecord(c->seg[nch], c->copy), "hipEventRecord");
-  HIP_TRY(hipStreamWaitEvent(s, c->seg[nch], 0), "hipStreamWaitEvent");
-  // Round 5: chunk k's front waits only for its signature-table slice; its item build and plan are
-  // enqueued before the host stages the chunk's ids and signature bytes (launch_items_front runs the
-  // hook between the plan and the hashes), so the plan overlaps the byte copy. Headline A/B, 10
-  // interleaved pairs: 327.7 -> 330.5 M sigs/s, 7 of 10 pairs faster (profiles/r05/split);
-  // CG_SPLIT_COPY=0 restores the whole-chunk wait.
-  static const bool split = [] {
-    const char* v = getenv("CG_SPLIT_COPY");
-    return !(v && v[0] == '0');
-  }();
-  const bool split_on = split && !overlap;
-  while (split_on && c->segtab.size() < nch) {
-    hipEvent_t ev;
-    HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming), "hipEventCreate");
-    c->segtab.push_back(ev);
-  }
-  hipError_t copy_err = hipSuccess;
-  uint64_t mid_k = 0;
-  // the second half of chunk mid_k's before(): bytes copied, the front's stream ordered after them
-  // Round 6 (CG_COPY_THREAD=1, A/B): a copy thread issues every chunk's table slice and bytes in
-  // order, running ahead, while this thread enqueues the kernels. The pageable copies block the
-  // issuing thread for the runtime's staging (~4 ms of a ~6-ms chunk on the headline) and the kernel
-  // and event calls of a chunk take ~2 ms of host time more (CG_HOST_TRACE, profiles/r06/copy_thread):
-  // in one thread the device waited ~0.3 ms per chunk for the host. This thread now waits (host
-  // condition) only until the copier has recorded the event it orders the main stream after.
-  static const bool copy_thread_env = [] {
-    const char* v = getenv("CG_COPY_THREAD");
-    return v && v[0] == '1';
-  }();
-  const bool ct = copy_thread_env && split_on && nch > 1;
-  ct_active = ct;
-  struct Feed {
-    std::mutex m;
-    std::condition_variable cv;
-    uint64_t tab = 0, bytes = 0;  // chunks whose table slice / bytes the copier has issued
-    hipError_t err = hipSuccess;
-    bool stop = false;
-  } feed;
-  auto feed_wait = [&](bool bytes, uint64_t k) -> hipError_t {
-    std::unique_lock<std::mutex> lk(feed.m);
-    feed.cv.wait(lk, [&] { return feed.err != hipSuccess || (bytes ? feed.bytes : feed.tab) > k; });
-    return (bytes ? feed.bytes : feed.tab) > k ? hipSuccess : feed.err;
-  };
-  std::thread copier;
-  struct JoinCopier {  // every exit path stops and joins the copier before the locals it uses go away
-    std::thread& t;
-    Feed& f;
-    ~JoinCopier() {
-      {
-        std::lock_guard<std::mutex> g(f.m);
-        f.stop = true;
-      }
-      if (t.joinable()) t.join();
+  // chunk k's id copies were issued from h2 to h3, then its signature bytes (ek) until now; a timing
+  // event behind them on the copy stream
+  hipError_t bytes_staged(uint64_t k, hipStream_t cs, double h2, double h3, double table_mb, const Extent& ek) {
+    if (!on) return hipSuccess;
+    hipError_t e = hipSuccess;
+    while (c->segt.size() <= k) {
+      hipEvent_t ev;
+      if (hipEventCreate(&ev) != hipSuccess) break;
+      c->segt.push_back(ev);
     }
-  } join_copier{copier, feed};
-  const std::function<hipError_t()> mid = [&]() -> hipError_t {
-    c->fork.mid_front = nullptr;
-    const uint64_t k = mid_k;
-    hipError_t e = ct ? feed_wait(true, k) : copy_bytes(k, c->copy);
-    if (e == hipSuccess) e = hipStreamWaitEvent(s, c->seg[k], 0);
-    if (e == hipSuccess && htrace && 3 * k < c->fbt.size()) {
-      c->fbh[k] = ms_since();
-      e = hipEventRecord(c->fbt[3 * k], s);
-    }
-    if (e == hipSuccess && k == 0) e = hipEventRecord(c->tev[1], s);
-    if (e != hipSuccess) copy_err = e;
+    if (c->segt.size() > k) e = hipEventRecord(c->segt[k], cs);
+    fprintf(stderr, "[cg host] chunk %llu at %.3f: scan %.3f sigs %.3f (%.1f MB) ids %.3f arena %.3f (%.1f MB) ms\n",
+            (unsigned long long)k, ht[3 * k], ht[3 * k + 1], ht[3 * k + 2], table_mb, h3 - h2, ms() - h3,
+            ek.empty() ? 0.0 : (ek.hi - ek.lo) / 1e6);
     return e;
-  };
-  struct ClearHook {  // no hook outlives this call's locals, whatever the exit path
-    cg_ctx* c;
-    ~ClearHook() { c->fork.mid_front = nullptr; }
-  } clear_hook{c};
-  const std::function<hipError_t(uint64_t, uint64_t, uint64_t)> before = [&](uint64_t k, uint64_t, uint64_t) {
-    if (split_on) {
-      hipError_t e = c->fork.mid_front ? mid() : hipSuccess;  // a hook a front did not consume
-      if (ct) {
-        if (e == hipSuccess) e = feed_wait(false, k);  // the copier recorded segtab[k]
-      } else {
-        if (e == hipSuccess) e = copy_table(k, c->copy);
-        if (e == hipSuccess) e = hipEventRecord(c->segtab[k], c->copy);
-      }
-      if (e == hipSuccess) e = hipStreamWaitEvent(s, c->segtab[k], 0);
-      if (e == hipSuccess) {
-        mid_k = k;
-        c->fork.mid_front = &mid;
-      }
-      if (e != hipSuccess) copy_err = e;
-      return e;
-    }
-    hipError_t e = overlap && k == 0 ? hipSuccess : copy_chunk(k, c->copy);
-    const hipStream_t fs = s;  // the stream chunk k's front runs on
-    if (e == hipSuccess) e = hipStreamWaitEvent(fs, c->seg[k], 0);
-    if (e == hipSuccess && htrace && 3 * k < c->fbt.size()) {
-      c->fbh[k] = ms_since();
-      e = hipEventRecord(c->fbt[3 * k], fs);  // the front's stream reaches chunk k's front
-    }
-    if (e == hipSuccess && k == 0) e = hipEventRecord(c->tev[1], fs);
-    if (e != hipSuccess) copy_err = e;
-    return e;
-  };
-  uint8_t* ds = (uint8_t*)c->status.p;
-  cg::KeyUses uses;
-  uses.counts = (const uint32_t*)c->aux1.p;
-  uses.n = n_sigs;
-  uses.host_keys = keys;
-  uses.host_counts = counts.data();
-  Packed12 p12;
-  if (packed) {
-    p12.d_sigs = (const cg_txsig_packed*)c->h_sigs.p;
-    p12.sig_region = sig_region;
-    p12.sig_bytes_len = sig_bytes_len;
-    p12.chunk_base = &cbase;
   }
-  if (ct)
-    copier = std::thread([&] {
-      hipError_t e = hipSetDevice(c->device);
-      for (uint64_t k = 0; k < nch && e == hipSuccess; ++k) {
-        {
-          std::lock_guard<std::mutex> g(feed.m);
-          if (feed.stop) break;
-        }
-        e = copy_table(k, c->copy);
-        if (e == hipSuccess) e = hipEventRecord(c->segtab[k], c->copy);
-        if (e == hipSuccess) {
-          std::lock_guard<std::mutex> g(feed.m);
-          feed.tab = k + 1;
-        }
-        feed.cv.notify_all();
-        if (e == hipSuccess) e = copy_bytes(k, c->copy);  // records seg[k]
-        if (e == hipSuccess) {
-          std::lock_guard<std::mutex> g(feed.m);
-          feed.bytes = k + 1;
-        }
-        feed.cv.notify_all();
-      }
-      std::lock_guard<std::mutex> g(feed.m);
-      if (e != hipSuccess) feed.err = e;
-      else if (feed.bytes < nch) feed.err = hipErrorUnknown;  // stopped early: no waiter may hang
-      feed.cv.notify_all();
-    });
-  const hipError_t le = launch_txsig(c, (const cg_key*)c->keys.p, n_keys, (const uint8_t*)c->h_ids.p, n_ids,
-                                     packed ? nullptr : (const cg_txsig*)c->h_sigs.p, n_sigs, tmpls, n_tmpls, dbase,
-                                     arena_len, mode, ds, s, slot, uses, &before, &bounds, packed ? &p12 : nullptr);
-  if (le == hipSuccess && c->fork.mid_front) {  // the last front did not consume its hook
-    const hipError_t me = mid();
-    if (me != hipSuccess) copy_err = me;
+  // the main stream reaches chunk k's front (its bytes have landed)
+  hipError_t front_reached(uint64_t k, hipStream_t s) {
+    if (!on || 3 * k >= c->fbt.size()) return hipSuccess;
+    c->fbh[k] = ms();
+    return hipEventRecord(c->fbt[3 * k], s);
   }
-  if (copier.joinable()) {
-    {
-      std::lock_guard<std::mutex> g(feed.m);
-      feed.stop = true;
-    }
-    copier.join();
-    if (feed.err != hipSuccess && copy_err == hipSuccess && le == hipSuccess) copy_err = feed.err;
-  }
-  if (copy_err != hipSuccess) return hip_fail(copy_err, "H2D signature bytes");
-  HIP_TRY(le, "launch_txsig");
-  HIP_TRY(hipEventRecord(c->tev[2], s), "hipEventRecord");
-  HIP_TRY(hipMemcpyAsync(status_out, ds, n_sigs, hipMemcpyDeviceToHost, s), "D2H status");
-  HIP_TRY(hipEventRecord(c->tev[3], s), "hipEventRecord");
-  HIP_TRY(order_out(c, s), "hipEventRecord");
-  const double h_enq = htrace ? ms_since() : 0;
-  HIP_TRY(hipStreamSynchronize(s), "hipStreamSynchronize");
-  if (htrace) {
+  // after the call's stream is drained: enqueued at h_enq
+  void report(uint64_t nch, double h_enq) {
+    if (!on) return;
     fprintf(stderr, "[cg host] enqueued at %.3f, done at %.3f ms; copies landed (device ms after the call's first event):",
-            h_enq, ms_since());
+            h_enq, ms());
     for (uint64_t k = 0; k < nch && k < c->segt.size(); ++k) {
       float t = 0;
       hipEventElapsedTime(&t, c->tev[0], c->segt[k]);
@@ -2041,21 +1465,254 @@ static int verify_txsig_host_locked(cg_ctx* c, const cg_key* keys, uint32_t n_ke
               "kernels done %.3f, joins done %.3f\n", (unsigned long long)k, c->fbh[k], fs, bj, be);
     }
   }
-  if (stats) {
-    float a = 0, b = 0, d = 0;
-    hipEventElapsedTime(&a, c->tev[0], c->tev[1]);
-    hipEventElapsedTime(&b, c->tev[1], c->tev[2]);
-    hipEventElapsedTime(&d, c->tev[2], c->tev[3]);
-    stats->n_items = n_sigs;
-    stats->n_keys = n_keys;
-    stats->ms_h2d = a;
-    stats->ms_key_prep = ms_plan;  // host-side planning: the key-use sample pass
-    stats->ms_verify = b;
-    stats->ms_d2h = d;
-    stats->ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+};
+
+// The per-chunk feed of a host tx-signature call, all on the copy stream. Chunk k's copies go in two
+// parts around its front: `before` (launch_chunked's prepare hook) scans the chunk's extents and
+// stages its signature-table slice, all its plan needs (segtab[k]); `mid` (the hook
+// launch_items_front runs between the plan and the hashes) stages the ids it references that are
+// not yet resident (a caller that lists each transaction's signatures together ships each id once,
+// with its first chunk) and its signature bytes, what its hashes need (seg[k]). So the plan waits
+// only for the table slice and overlaps the byte copy. Round 5 headline A/B against waiting for
+// the whole chunk before its front, 10 interleaved pairs: 327.7 -> 330.5 M sigs/s, 7 of 10 pairs
+// faster (profiles/r05/split).
+// Measured and not kept: the next chunk's extent scan on the pool from a helper thread while this
+// chunk's copies stage (round 4 neutral to -1%, the copies' landing times did not move,
+// profiles/r04/ahead; round 5 326.7 vs 326.4 M, profiles/r05/scan_ahead), and a copy thread that
+// issues every chunk's copies in order, running ahead of the thread that enqueues the kernels
+// (round 6: the chunks land earlier, the step does not move, profiles/r06/copy_thread).
+struct TxsigFeed {
+  cg_ctx* c;
+  HostTrace& tr;
+  const std::vector<uint64_t>& bounds;
+  // the caller's buffers: one of the two tables, the ids, the arena, the 12-byte form's stream
+  const cg_txsig* sigs = nullptr;
+  const cg_txsig_packed* sigs12 = nullptr;
+  const uint8_t *ids = nullptr, *arena = nullptr, *sig_bytes = nullptr;
+  uint64_t n_ids = 0, arena_len = 0, sig_region = 0, sig_bytes_len = 0;  // arena_len: what the kernels see
+  uint64_t nt = 1;  // host threads of the extent scans, run through `par`
+  cg::ParFor par;
+  std::vector<Extent> ext_e, ext_i;  // chunk k's signature bytes / id bytes
+  // the 12-byte table: chunk k's first signature at stream offset cbase[k] (cbase[k + 1] is set when
+  // chunk k's table slice is staged)
+  std::vector<uint64_t> cbase;
+  cg::Resident have, have_ids, have_sig;  // arena bytes / id bytes / the 12-byte form's stream bytes on the device
+  hipError_t copy_err = hipSuccess;       // the first failure inside a hook
+  uint64_t mid_k = 0;                     // the chunk whose `mid` is pending
+  const std::function<hipError_t()> mid_hook = [this] { return mid(); };
+  const std::function<hipError_t(uint64_t, uint64_t, uint64_t)> before_hook = [this](uint64_t k, uint64_t, uint64_t) {
+    return before(k);
+  };
+
+  bool packed() const { return sigs12 != nullptr; }
+  TxsigFeed(cg_ctx* ctx, HostTrace& trace, const std::vector<uint64_t>& b)
+      : c(ctx), tr(trace), bounds(b), ext_e(b.size() - 1), ext_i(b.size() - 1), cbase(b.size(), 0) {}
+  TxsigFeed(const TxsigFeed&) = delete;
+  ~TxsigFeed() { c->fork.mid_front = nullptr; }  // no hook outlives the call, whatever the exit path
+
+  // chunk k's extents (exact: a threaded scan of its slice of the table) and its table slice
+  hipError_t copy_table(uint64_t k) {
+    const uint64_t first = bounds[k], cnt = bounds[k + 1] - bounds[k];
+    const double h0 = tr.ms();
+    const cg::ChunkScan x = packed() ? cg::scan_chunk(sigs12, first, first + cnt, n_ids, arena_len, nt, par)
+                                     : cg::scan_chunk(sigs, first, first + cnt, n_ids, arena_len, nt, par);
+    ext_e[k] = x.sig;
+    ext_i[k] = x.ids;
+    if (packed()) {  // the chunk's stream bytes, clipped to the caller's buffer (past it: CG_NOT_RUN)
+      cbase[k + 1] = cbase[k] + x.span;
+      ext_e[k] = Extent();
+      ext_e[k].add(cbase[k], x.span, sig_bytes_len);
+    }
+    const double h1 = tr.ms();
+    const hipError_t e =
+        packed() ? hipMemcpyAsync((cg_txsig_packed*)c->h_sigs.p + first, sigs12 + first, sizeof(cg_txsig_packed) * cnt,
+                                  hipMemcpyHostToDevice, c->copy)
+                 : hipMemcpyAsync((cg_txsig*)c->h_sigs.p + first, sigs + first, sizeof(cg_txsig) * cnt,
+                                  hipMemcpyHostToDevice, c->copy);
+    tr.table_staged(k, h0, h1);
+    return e;
   }
+  // chunk k's ids and signature bytes; seg[k] marks the end
+  hipError_t copy_bytes(uint64_t k) {
+    const Extent& ek = ext_e[k];
+    uint8_t* dwin = (uint8_t*)c->arena.p;  // the device arena mirrors [0, arena_len)
+    const double h2 = tr.ms();
+    hipError_t e = copy_missing(have_ids, ext_i[k], ids, (uint8_t*)c->h_ids.p, 0, c->copy);
+    const double h3 = tr.ms();
+    if (e == hipSuccess && packed()) e = copy_missing(have_sig, ek, sig_bytes, dwin + sig_region, 0, c->copy);
+    else if (e == hipSuccess) e = copy_missing(have, ek, arena, dwin, 0, c->copy);
+    if (e == hipSuccess) e = hipEventRecord(c->seg[k], c->copy);
+    if (e == hipSuccess)
+      e = tr.bytes_staged(k, c->copy, h2, h3,
+                          (packed() ? sizeof(cg_txsig_packed) : sizeof(cg_txsig)) * (bounds[k + 1] - bounds[k]) / 1e6, ek);
+    return e;
+  }
+  // the second half of chunk mid_k's staging: bytes copied, the front's stream ordered after them
+  hipError_t mid() {
+    c->fork.mid_front = nullptr;
+    const uint64_t k = mid_k;
+    hipStream_t s = c->stream;
+    hipError_t e = copy_bytes(k);
+    if (e == hipSuccess) e = hipStreamWaitEvent(s, c->seg[k], 0);
+    if (e == hipSuccess) e = tr.front_reached(k, s);
+    if (e == hipSuccess && k == 0) e = hipEventRecord(c->tev[1], s);
+    if (e != hipSuccess) copy_err = e;
+    return e;
+  }
+  // chunk k's front waits only for its signature-table slice; `mid` is left for the front to run
+  hipError_t before(uint64_t k) {
+    hipStream_t s = c->stream;
+    hipError_t e = c->fork.mid_front ? mid() : hipSuccess;  // a hook a front did not consume
+    if (e == hipSuccess) e = copy_table(k);
+    if (e == hipSuccess) e = hipEventRecord(c->segtab[k], c->copy);
+    if (e == hipSuccess) e = hipStreamWaitEvent(s, c->segtab[k], 0);
+    if (e == hipSuccess) {
+      mid_k = k;
+      c->fork.mid_front = &mid_hook;
+    }
+    if (e != hipSuccess) copy_err = e;
+    return e;
+  }
+};
+
+// At least n events without timing in v.
+static hipError_t ensure_events(std::vector<hipEvent_t>& v, uint64_t n) {
+  while (v.size() < n) {
+    hipEvent_t e;
+    const hipError_t r = hipEventCreateWithFlags(&e, hipEventDisableTiming);
+    if (r != hipSuccess) return r;
+    v.push_back(e);
+  }
+  return hipSuccess;
+}
+
+// cg_verify_tx_signatures with the ctx lock held. Host side, in order: the key table and key bytes,
+// the template bytes, the ids and the signature table (everything the key tables and the plans
+// need), then the signature bytes chunk by chunk, each copy issued just before its chunk's front
+// so that the key-table builds and the previous chunk's kernels run during it.
+// The 12-byte form (cg_verify_tx_signatures_packed): sigs is null, sigs12 the table, the signatures
+// dense in sig_bytes. On the device they follow the caller's arena at sig_region (16-aligned), so the
+// kernels address every byte by an absolute arena offset as in the 24-byte form; a key or template
+// that lies outside [0, arena_len) is moved out of the extended arena too (never reads a signature).
+static int verify_txsig_host_locked(cg_ctx* c, const cg_key* keys, uint32_t n_keys, const uint8_t* ids,
+                                    uint64_t n_ids, const cg_txsig* sigs, uint64_t n_sigs,
+                                    const cg_signable_tmpl* tmpls, uint32_t n_tmpls, const uint8_t* arena,
+                                    uint64_t arena_len, uint32_t mode, uint8_t* status_out, cg_stats* stats,
+                                    const cg_txsig_packed* sigs12 = nullptr, const uint8_t* sig_bytes = nullptr,
+                                    uint64_t sig_bytes_len = 0) {
+  const auto t0 = std::chrono::steady_clock::now();
+  const bool packed = sigs12 != nullptr;
+  const uint64_t caller_len = arena_len;
+  const uint64_t sig_region = packed ? ((arena_len + 15) & ~(uint64_t)15) : 0;
+  if (packed) arena_len = sig_region + sig_bytes_len;  // what the kernels see
+  std::vector<cg_key> keys_fix;
+  std::vector<cg_signable_tmpl> tmpls_fix;
+  if (packed) {  // out-of-arena keys / templates stay out of range in the extended arena
+    cg::txsig_packed_fixup(keys, n_keys, tmpls, n_tmpls, caller_len, keys_fix, tmpls_fix);
+    if (!keys_fix.empty()) keys = keys_fix.data();
+    if (!tmpls_fix.empty()) tmpls = tmpls_fix.data();
+  }
+  if (c->fault) return fail(CG_ERR_DEVICE, "cg_verify_tx_signatures: device fault (injected by cg_pool_inject_fault)");
+  HIP_TRY(hipSetDevice(c->device), "hipSetDevice");
+  // chunk bounds (txsig_plan.h); `per`, the largest chunk, sizes the item workspaces
+  static const uint64_t first_div = env_u64("CG_TXSIG_FIRST_DIV", cg::kTxsigFirstDiv);
+  const std::vector<uint64_t> bounds = cg::txsig_bounds(n_sigs, c->chunk, c->chunk_set, first_div);
+  const uint64_t nch = bounds.size() - 1, per = cg::largest_chunk(bounds);
+  // arena extents: key bytes + template bytes (the header), then each chunk's signature bytes, scanned
+  // just before its copy, while the device works on the chunks before it
+  const Extent head = cg::txsig_head_extent(keys, n_keys, tmpls, n_tmpls, caller_len);
+  // the budget's host threads (host_budget.h), on the context's pool (spawning 16 threads per scan
+  // cost 0.35-0.5 ms a round)
+  const uint64_t nt = host_threads_of(c, n_sigs);
+  const cg::ParFor par = [c](uint64_t m, const std::function<void(uint64_t)>& fn) { host_par(c, m, fn); };
+  std::vector<uint32_t> counts(n_keys ? n_keys : 1, 0u);
+  const uint64_t slot = tmpl_slot(tmpls, n_tmpls);
+  HIP_TRY(c->keys.ensure(sizeof(cg_key) * (n_keys ? n_keys : 1)), "hipMalloc(keys)");
+  HIP_TRY(c->h_sigs.ensure((packed ? sizeof(cg_txsig_packed) : sizeof(cg_txsig)) * n_sigs), "hipMalloc(sigs)");
+  if (packed) HIP_TRY(c->sig12ws.ensure(cg::tx_sig12_scratch_bytes(per)), "hipMalloc(signature offsets)");
+  HIP_TRY(c->aux1.ensure(sizeof(uint32_t) * counts.size()), "hipMalloc(key use counts)");
+  HIP_TRY(c->h_ids.ensure(32 * (n_ids ? n_ids : 1)), "hipMalloc(ids)");
+  HIP_TRY(c->arena.ensure(arena_len + 16), "hipMalloc(arena window)");  // mirrors [0, arena_len): only referenced bytes are copied
+  HIP_TRY(c->status.ensure(n_sigs), "hipMalloc(status)");
+  HIP_TRY(ensure_txsig_ws(c, n_sigs, n_tmpls, slot), "hipMalloc(tx signature workspace)");
+  HIP_TRY(ensure_ws(c, n_keys, per, n_sigs), "hipMalloc(workspace)");
+  HIP_TRY(ensure_events(c->seg, nch + 1), "hipEventCreate");
+  HIP_TRY(ensure_events(c->segtab, nch), "hipEventCreate");
+  static const bool htrace = env_flag("CG_HOST_TRACE", false);
+  HostTrace tr{c, t0, htrace, {}};
+  HIP_TRY(tr.begin(nch), "hipEventCreate");
+  hipStream_t s = c->stream;
+  const uint8_t* dbase = (const uint8_t*)c->arena.p;  // kernels index the arena by absolute offsets
+  HIP_TRY(order_in(c, s), "hipStreamWaitEvent");
+  HIP_TRY(hipEventRecord(c->tev[0], s), "hipEventRecord");
+  HIP_TRY(hipStreamWaitEvent(c->copy, c->tev[0], 0), "hipStreamWaitEvent");
+  TxsigFeed feed(c, tr, bounds);
+  feed.sigs = sigs;
+  feed.sigs12 = sigs12;
+  feed.ids = ids;
+  feed.arena = arena;
+  feed.sig_bytes = sig_bytes;
+  feed.n_ids = n_ids;
+  feed.arena_len = arena_len;
+  feed.sig_region = sig_region;
+  feed.sig_bytes_len = sig_bytes_len;
+  feed.nt = nt;
+  feed.par = par;
+  if (n_keys)
+    HIP_TRY(hipMemcpyAsync(c->keys.p, keys, sizeof(cg_key) * n_keys, hipMemcpyHostToDevice, c->copy), "H2D keys");
+  HIP_TRY(copy_missing(feed.have, head, arena, (uint8_t*)c->arena.p, 0, c->copy), "H2D key / template bytes");
+  // The key-use counts (txsig_plan.h) gate only the key tables; chunk 0's bytes gate everything else.
+  // (Sampling the counts while chunk 0 copies, on a second copy stream with a pinned counts buffer,
+  // measured slower on the configs[4] shard: 197 / 205 vs 213 / 220 M sigs/s, profiles/r03/ab_sc: the
+  // sample pass slows 2x beside the pageable copy's staging and the late counts delay the key tables.)
+  {
+    static const uint32_t S_env = cg::sample_override((uint32_t)env_u64("CG_TXSIG_SAMPLE", 0));
+    static const uint32_t B = cg::sample_block((uint32_t)env_u64("CG_TXSIG_SAMPLE_BLOCK", cg::kTxsigSampleBlock));
+    const uint32_t S = cg::sample_rate(S_env, n_sigs, n_keys);
+    const cg::WidePool thr = c->eng->make_wide_pool(nullptr, n_keys, n_sigs, cg::kKeyWideMax);  // the wide thresholds
+    if (packed)
+      cg::key_use_counts(sigs12, n_sigs, keys, n_keys, nt, par, S, B, thr.min_ed, thr.min_ec, c->count_scratch,
+                         counts.data());
+    else
+      cg::key_use_counts(sigs, n_sigs, keys, n_keys, nt, par, S, B, thr.min_ed, thr.min_ec, c->count_scratch,
+                         counts.data());
+  }
+  const double ms_plan = ms_since(t0);  // host-side planning: the key-use sample pass
+  HIP_TRY(hipMemcpyAsync(c->aux1.p, counts.data(), sizeof(uint32_t) * counts.size(), hipMemcpyHostToDevice, c->copy),
+          "H2D key use counts");
+  HIP_TRY(hipEventRecord(c->seg[nch], c->copy), "hipEventRecord");
+  HIP_TRY(hipStreamWaitEvent(s, c->seg[nch], 0), "hipStreamWaitEvent");
+  uint8_t* ds = (uint8_t*)c->status.p;
+  cg::KeyUses uses;
+  uses.counts = (const uint32_t*)c->aux1.p;
+  uses.n = n_sigs;
+  uses.host_keys = keys;
+  uses.host_counts = counts.data();
+  Packed12 p12;
+  if (packed) {
+    p12.d_sigs = (const cg_txsig_packed*)c->h_sigs.p;
+    p12.sig_region = sig_region;
+    p12.sig_bytes_len = sig_bytes_len;
+    p12.chunk_base = &feed.cbase;
+  }
+  const hipError_t le = launch_txsig(c, (const cg_key*)c->keys.p, n_keys, (const uint8_t*)c->h_ids.p, n_ids,
+                                     packed ? nullptr : (const cg_txsig*)c->h_sigs.p, n_sigs, tmpls, n_tmpls, dbase,
+                                     arena_len, mode, ds, s, slot, uses, &feed.before_hook, &bounds,
+                                     packed ? &p12 : nullptr);
+  if (le == hipSuccess && c->fork.mid_front) feed.mid();  // the last front did not consume its hook
+  if (feed.copy_err != hipSuccess) return hip_fail(feed.copy_err, "H2D signature bytes");
+  HIP_TRY(le, "launch_txsig");
+  HIP_TRY(hipEventRecord(c->tev[2], s), "hipEventRecord");
+  HIP_TRY(hipMemcpyAsync(status_out, ds, n_sigs, hipMemcpyDeviceToHost, s), "D2H status");
+  HIP_TRY(hipEventRecord(c->tev[3], s), "hipEventRecord");
+  HIP_TRY(order_out(c, s), "hipEventRecord");
+  const double h_enq = tr.ms();
+  HIP_TRY(hipStreamSynchronize(s), "hipStreamSynchronize");
+  tr.report(nch, h_enq);
+  fill_stats(c, stats, n_sigs, n_keys, ms_plan, t0);
   return CG_OK;
 }
+
 
 static int txsig_args(const char* fn, cg_ctx* c, uint32_t n_keys, const void* keys, uint64_t n_ids, const void* ids,
                       uint64_t n_sigs, const void* sigs, const void* status, uint32_t n_tmpls, const void* tmpls,
@@ -2120,8 +1777,7 @@ int cg_verify_tx_signatures_packed_device(cg_ctx* c, const cg_key* d_keys, uint3
   // CG_DEV_FIRST_PCT=<p> (A/B): a two-chunk call's first chunk p% of the call instead of half; 50 / 60
   // / 67% measured 391.2 / 392.1 / 392.3 M sigs/s over 3 rounds, within the noise (profiles/r06/firstpct)
   static const uint64_t first_pct = [] {
-    const char* v = getenv("CG_DEV_FIRST_PCT");
-    const uint64_t x = v ? (uint64_t)strtoull(v, nullptr, 10) : 0ull;
+    const uint64_t x = env_u64("CG_DEV_FIRST_PCT", 0);
     return x >= 10 && x <= 90 ? x : 0ull;
   }();
   if (first_pct && bounds.size() == 3) {

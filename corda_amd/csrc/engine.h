@@ -107,8 +107,8 @@ struct Fork {
   hipEvent_t ec_front_go = nullptr, ec_front_done[2] = {nullptr, nullptr};
   mutable PendingTabs pending;
   hipEvent_t mark = nullptr;  // CG_HOST_TRACE: recorded on the main stream before a back's final joins
-  // Host hook launch_items_front runs once between a chunk's plan and its hashes (the host path's
-  // CG_SPLIT_COPY: the chunk's signature bytes are copied there, after its plan is enqueued)
+  // Host hook launch_items_front runs once between a chunk's plan and its hashes (the host
+  // tx-signature path copies the chunk's signature bytes there, after its plan is enqueued)
   const std::function<hipError_t()>* mid_front = nullptr;
 };
 
