@@ -44,8 +44,14 @@ class cg_pool_stats(ctypes.Structure):
                 ("reserved", ctypes.c_uint32), ("not_run", ctypes.c_uint64), ("ms_total", ctypes.c_double)]
 
 
+class cg_key_cache_info(ctypes.Structure):
+    _fields_ = [("enabled", ctypes.c_uint32), ("slots", ctypes.c_uint32), ("hits", ctypes.c_uint32 * 2),
+                ("built", ctypes.c_uint32 * 2), ("evicted", ctypes.c_uint32 * 2), ("fell_back", ctypes.c_uint32 * 2)]
+
+
 ABI_VERSION = 2
 FLAG_STAGE_TIMING = 1
+FLAG_NO_KEY_CACHE = 8  # CG_FLAG_NO_KEY_CACHE: no wide table kept between calls
 FLAG_RSA = 2  # CG_FLAG_RSA: RSA_SHA256 items verified on the device
 STAGE_NAMES = ["plan", "ed_hash", "ed_ladder", "ed_ladder_row0", "ed_finish", "r1_front", "r1_ladder",
                "r1_ladder_row0", "k1_front", "k1_ladder", "k1_ladder_row0", "ed_ladder_wide", "r1_ladder_wide",
@@ -102,6 +108,9 @@ def lib():
             if hasattr(L, "cg_stage_times"):
                 L.cg_stage_times.argtypes = [vp, vp, vp, u32]
                 L.cg_stage_times.restype = i32
+            if hasattr(L, "cg_key_cache_stats"):  # older builds (A/B variants) lack the wide-table cache
+                L.cg_key_cache_stats.argtypes = [vp, ctypes.POINTER(cg_key_cache_info)]
+                L.cg_key_cache_stats.restype = i32
             if hasattr(L, "cg_host_register"):  # older builds (A/B variants) lack the registration
                 L.cg_host_register.argtypes = [vp, u64]
                 L.cg_host_register.restype = i32

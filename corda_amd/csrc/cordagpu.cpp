@@ -130,6 +130,19 @@ struct cg_ctx {
   // with fewer hot keys on wide tables (full tables for the rest: slower, same verdicts) instead of
   // failing with CG_ERR_NOMEM
   uint32_t wide_max = cg::kKeyWideMax;
+  // The wide-table cache (key_cache.h): the pool keeps its slots' tables between calls, and a call
+  // builds only the tables of the hot keys it does not find there. wide_slots: the slots the pool
+  // was allocated for (its layout); kcache: the owners, index and counters on the device.
+  // kc_dirty: the next call empties the cache first (the pool moved, or a call failed after it had
+  // claimed slots: kc_open is set while a call is between its claim and the enqueue of its last
+  // kernel, and a call that finds it set knows the one before did not get there).
+  DevBuf kcache;
+  uint32_t wide_slots = 0;
+  uint32_t wide_slots_max = cg::kKeyWideMax;  // CG_TEST_WIDE_SLOTS (tests): a smaller pool
+  uint32_t kc_bits = 32;                      // CG_TEST_KEY_CACHE_BITS (tests): 2^bits home entries in the index
+  bool kc_on = true;                          // off: CG_FLAG_NO_KEY_CACHE, CG_KEY_CACHE=0
+  bool kc_dirty = true;
+  bool kc_open = false;
   // transaction pipeline: verify items, spliced messages, templates; host-entry staging
   DevBuf txitems, msgs, tmpls, h_txs, h_comps, h_sigs, h_ids, h_txst;
   DevBuf sig12ws;  // the 12-byte signature table's per-block stream offsets (launch_tx_sig12_range)
@@ -347,7 +360,7 @@ hipError_t ensure_ws(cg_ctx* c, uint32_t n_keys, uint64_t ws_items, uint64_t cal
   // cap lowered by an earlier call that met low free memory (another process on the device) is
   // raised again here once the memory is back, instead of staying low for the
   // context's life
-  const uint32_t kmax = cg::kKeyWideMax;
+  const uint32_t kmax = c->wide_slots_max;
   size_t wide = c->eng->wide_bytes(n_keys, call_items, kmax);
   const size_t items = item_half_bytes(c, ws_items) * (call_items > ws_items ? 2 : 1);
   if (c->keyprep.cap >= c->eng->keyprep_bytes(n_keys) && c->itemws.cap >= items && c->wide.cap >= wide) {
@@ -375,7 +388,12 @@ hipError_t ensure_ws(cg_ctx* c, uint32_t n_keys, uint64_t ws_items, uint64_t cal
   hipError_t e = hipDeviceSynchronize();
   if (e == hipSuccess) e = c->keyprep.ensure(c->eng->keyprep_bytes(n_keys));
   if (e == hipSuccess) e = c->itemws.ensure(items);
-  if (e == hipSuccess) e = c->wide.ensure_exact(wide);
+  if (e == hipSuccess && wide > c->wide.cap) {  // a new pool, laid out by its own capacity: the cache starts empty
+    e = c->wide.ensure_exact(wide);
+    c->wide_slots = e == hipSuccess ? c->eng->wide_slots(n_keys, call_items, cap) : 0;
+    c->kc_dirty = true;
+    if (e == hipSuccess && c->kc_on) e = c->kcache.ensure(c->eng->key_cache_bytes(c->wide_slots));
+  }
   return e;
 }
 
@@ -383,7 +401,18 @@ hipError_t ensure_ws(cg_ctx* c, uint32_t n_keys, uint64_t ws_items, uint64_t cal
 cg::WidePool wide_for(cg_ctx* c, uint32_t n_keys, uint64_t n_items) {
   static const bool off = env_flag("CG_NO_WIDE_TABLES", false);  // =1: never build wide tables (A/B runs)
   if (off || c->wide.cap < c->eng->wide_bytes(n_keys, n_items, c->wide_max)) return cg::WidePool{};
-  cg::WidePool p = c->eng->make_wide_pool(c->wide.p, n_keys, n_items, c->wide_max);
+  cg::WidePool p = c->eng->make_wide_pool(c->wide.p, n_keys, n_items, c->wide_max, c->wide_slots);
+  if (c->kc_on && p.cap_ed && c->kcache.p && c->kcache.cap >= c->eng->key_cache_bytes(p.slots)) {
+    if (c->kc_open) {  // the last call failed between claim and commit: whatever it left on the streams ends first
+      (void)hipDeviceSynchronize();
+      c->kc_dirty = true;
+    }
+    p.cache = c->kcache.p;
+    p.cache_bits = c->kc_bits;
+    p.cache_dirty = c->kc_dirty;
+    c->kc_dirty = false;
+    c->kc_open = true;
+  }
   // CG_WIDE_MIN_USES_ED / _EC: override the thresholds (A/B runs)
   static const uint32_t min_ed = (uint32_t)env_u64("CG_WIDE_MIN_USES_ED", 0);
   static const uint32_t min_ec = (uint32_t)env_u64("CG_WIDE_MIN_USES_EC", 0);
@@ -410,6 +439,7 @@ hipError_t launch_chunked(cg_ctx* c, const cg_key* d_keys, uint32_t n_keys, cons
   if (e == hipSuccess) e = rsa_keyprep(c, d_keys, n_keys, d_arena, arena_len, s);
   // the RSA pass over the whole call, after the last chunk's back
   auto rsa_pass = [&](hipError_t r) {
+    if (r == hipSuccess) c->kc_open = false;  // every kernel of the call is enqueued, the cache's commits among them
     return r != hipSuccess ? r : rsa_items(c, d_keys, n_keys, d_items, n_items, d_arena, arena_len, mode, d_status, s,
                                            d_msgs, msgs_len);
   };
@@ -647,6 +677,7 @@ int verify_host_locked(cg_ctx* c, const cg_key* keys, uint32_t n_keys, const cg_
     HIP_TRY(c->eng->launch_items(dk, n_keys, di + f, cnt, dbase, arena_len, mode, ds + f, c->keyprep.p, c->itemws.p,
                              c->btab, s, nullptr, 0, &c->fork, &wp), "launch_items");
   }
+  c->kc_open = false;  // every kernel of the call is enqueued, the wide-table cache's commits among them
   HIP_TRY(rsa_items(c, dk, n_keys, di, n_items, dbase, arena_len, mode, ds, s), "launch_rsa_items");
   HIP_TRY(hipEventRecord(c->tev[2], s), "hipEventRecord");
   HIP_TRY(hipMemcpyAsync(status_out, ds, n_items, hipMemcpyDeviceToHost, s), "D2H status");
@@ -737,7 +768,7 @@ int cg_open(cg_ctx** out, const cg_config* cfg) {
              (unsigned long long)tab_budget, (unsigned long long)table_sets().back().bytes, table_sets().back().bits);
     return fail(CG_ERR_ARG, "%s", m);
   }
-  if (cfg && (cfg->flags & ~(CG_FLAG_STAGE_TIMING | CG_FLAG_RSA))) return fail(CG_ERR_ARG, "cg_open: unknown cg_config.flags bits");
+  if (cfg && (cfg->flags & ~(CG_FLAG_STAGE_TIMING | CG_FLAG_RSA | CG_FLAG_NO_KEY_CACHE))) return fail(CG_ERR_ARG, "cg_open: unknown cg_config.flags bits");
   int dev = cfg ? cfg->device : 0;
   int n = 0;
   HIP_TRY(hipGetDeviceCount(&n), "hipGetDeviceCount");
@@ -757,6 +788,12 @@ int cg_open(cg_ctx** out, const cg_config* cfg) {
   }
   if (cfg && (cfg->flags & CG_FLAG_STAGE_TIMING)) c->fork.timer = &c->timer;
   c->rsa = cfg && (cfg->flags & CG_FLAG_RSA);
+  // the wide-table cache: on unless the flag or CG_KEY_CACHE=0 (A/B runs) says otherwise; read here,
+  // per context. CG_TEST_WIDE_SLOTS / CG_TEST_KEY_CACHE_BITS (tests only): a pool of at most that
+  // many slots, so that keys are evicted; an index of 2^bits home entries, so that keys collide.
+  c->kc_on = !(cfg && (cfg->flags & CG_FLAG_NO_KEY_CACHE)) && env_flag("CG_KEY_CACHE", true);
+  c->wide_slots_max = (uint32_t)std::min<uint64_t>(env_u64("CG_TEST_WIDE_SLOTS", cg::kKeyWideMax), cg::kKeyWideMax);
+  c->kc_bits = (uint32_t)std::min<uint64_t>(env_u64("CG_TEST_KEY_CACHE_BITS", 32), 32);
   // CG_STREAM_PRIORITY=1 (A/B): the context's stream at the device's highest priority, so its
   // blocks (the plan sort's decoupled look-back above all) dispatch ahead of the side streams'
   // table builds
@@ -850,6 +887,7 @@ void cg_close(cg_ctx* c) {
   c->keyprep.release();
   c->itemws.release();
   c->wide.release();
+  c->kcache.release();
   if (c->btab) release_tables(c->device, c->btab);
   c->btab = nullptr;
   c->keys.release();
@@ -967,6 +1005,27 @@ int cg_reserve(cg_ctx* c, uint32_t max_keys, uint64_t max_items) {
   std::lock_guard<std::mutex> g(c->mu);
   HIP_TRY(hipSetDevice(c->device), "hipSetDevice");
   HIP_TRY(ensure_ws(c, max_keys, chunk_of(c, max_items), max_items), "hipMalloc(workspace)");
+  return CG_OK;
+}
+
+int cg_key_cache_stats(cg_ctx* c, cg_key_cache_info* out) {
+  if (!c || !out) return fail(CG_ERR_ARG, "cg_key_cache_stats: NULL argument");
+  std::lock_guard<std::mutex> g(c->mu);
+  HIP_TRY(hipSetDevice(c->device), "hipSetDevice");
+  memset(out, 0, sizeof *out);
+  out->enabled = c->kc_on ? 1u : 0u;
+  out->slots = c->wide_slots;
+  if (c->done_rec) HIP_TRY(hipEventSynchronize(c->done), "hipEventSynchronize");
+  HIP_TRY(hipStreamSynchronize(c->stream), "hipStreamSynchronize");
+  if (!c->kc_on || !c->kcache.p || c->kc_dirty) return CG_OK;  // no call has used the cache since it was emptied
+  uint32_t ctr[16];  // keyws.h KeyCache: 8 counters per pool head the buffer
+  HIP_TRY(hipMemcpy(ctr, c->kcache.p, sizeof ctr, hipMemcpyDeviceToHost), "hipMemcpy(key cache counters)");
+  for (int q = 0; q < 2; ++q) {
+    out->hits[q] = ctr[8 * q + 0];
+    out->built[q] = ctr[8 * q + 1];
+    out->evicted[q] = ctr[8 * q + 2];
+    out->fell_back[q] = ctr[8 * q + 3];
+  }
   return CG_OK;
 }
 
@@ -1669,7 +1728,7 @@ static int verify_txsig_host_locked(cg_ctx* c, const cg_key* keys, uint32_t n_ke
     static const uint32_t S_env = cg::sample_override((uint32_t)env_u64("CG_TXSIG_SAMPLE", 0));
     static const uint32_t B = cg::sample_block((uint32_t)env_u64("CG_TXSIG_SAMPLE_BLOCK", cg::kTxsigSampleBlock));
     const uint32_t S = cg::sample_rate(S_env, n_sigs, n_keys);
-    const cg::WidePool thr = c->eng->make_wide_pool(nullptr, n_keys, n_sigs, cg::kKeyWideMax);  // the wide thresholds
+    const cg::WidePool thr = c->eng->make_wide_pool(nullptr, n_keys, n_sigs, cg::kKeyWideMax, 0);  // the wide thresholds
     if (packed)
       cg::key_use_counts(sigs12, n_sigs, keys, n_keys, nt, par, S, B, thr.min_ed, thr.min_ec, c->count_scratch,
                          counts.data());

@@ -24,6 +24,14 @@ struct WidePool {
   void* ec = nullptr;
   uint32_t cap_ed = 0, cap_ec = 0;
   uint32_t min_ed = 0, min_ec = 0;  // items per key from which a key gets wide tables, per family
+  // The pools are laid out by `slots`, the capacity they were allocated for (a slot's address does
+  // not move between calls); cap_ed / cap_ec only limit how many keys may be wide in this call.
+  uint32_t slots = 0;
+  // The context's wide-table cache (key_cache.h; keyws.h KeyCache lays it out): null = off, every
+  // call builds the tables of its wide keys. cache_dirty: empty it at the start of this call.
+  void* cache = nullptr;
+  uint32_t cache_bits = 32;  // home entries of the cache's index: 2^bits (tests narrow it)
+  bool cache_dirty = false;
 };
 
 // Side streams + events owned by a context. Key preparation forks off the caller's stream:
@@ -146,7 +154,9 @@ struct EngineVariant {
   size_t (*keyprep_bytes)(uint32_t n_keys);
   size_t (*wide_bytes)(uint32_t n_keys, uint64_t n_items, uint32_t max_slots);
   size_t (*wide_slot_bytes)();
-  WidePool (*make_wide_pool)(void* base, uint32_t n_keys, uint64_t n_items, uint32_t max_slots);
+  WidePool (*make_wide_pool)(void* base, uint32_t n_keys, uint64_t n_items, uint32_t max_slots, uint32_t alloc_slots);
+  uint32_t (*wide_slots)(uint32_t n_keys, uint64_t n_items, uint32_t max_slots);
+  size_t (*key_cache_bytes)(uint32_t slots);
   size_t (*btab_bytes)();
   size_t (*btab_scratch_bytes)();
   hipError_t (*init_btab)(void* d_btab, void* d_scratch, hipStream_t stream);
@@ -196,7 +206,11 @@ size_t keyprep_bytes(uint32_t n_keys);
 size_t wide_bytes(uint32_t n_keys, uint64_t n_items, uint32_t max_slots = 8192u);
 size_t wide_slot_bytes();  // one Ed25519 + one ECDSA wide slot
 constexpr uint32_t kKeyWideMax = 8192u;  // keyws.h KEY_WIDE_MAX (static_assert in verify.hip)
-WidePool make_wide_pool(void* base, uint32_t n_keys, uint64_t n_items, uint32_t max_slots = 8192u);
+// alloc_slots: the slots the buffer at `base` was allocated for (0: as many as this call may use)
+WidePool make_wide_pool(void* base, uint32_t n_keys, uint64_t n_items, uint32_t max_slots = 8192u,
+                        uint32_t alloc_slots = 0);
+uint32_t wide_slots(uint32_t n_keys, uint64_t n_items, uint32_t max_slots);  // slots such a call may use
+size_t key_cache_bytes(uint32_t slots);  // the wide-table cache's bookkeeping for a pool of `slots` slots
 
 // Enqueue the whole verify pipeline for one batch on `stream`:
 //   key prep (one lane per key) -> per-scheme verify (one lane per item) -> status bytes.

@@ -8,6 +8,7 @@
 #include "ed25519.h"
 #include "ed25519_rows.h"
 #include "engine.h"
+#include "key_cache.h"
 #include "sha2.h"
 
 namespace cg {
@@ -234,6 +235,59 @@ static inline uint32_t tab_park_lanes(uint32_t n_keys, uint32_t rows) {
   if (l > TAB_PARK_LANES) l = TAB_PARK_LANES;
   return (uint32_t)((l + 63) & ~(uint64_t)63);
 }
+// The wide-table cache's bookkeeping (key_cache.h), one buffer per context, per pool (0 Ed25519,
+// 1 ECDSA: both curves share it, the scheme is part of a key's identity):
+//   [counters: 2 x 8 u32, 256 B][owners 0][owners 1][live 0][live 1][free list 0][free list 1][index 0][index 1]
+// Counters of the last call, per pool (cg_key_cache_stats):
+#define KC_CTR_HITS 0      // keys that found their tables
+#define KC_CTR_BUILT 1     // slots whose tables this call built and committed
+#define KC_CTR_EVICTED 2   // claimed slots that held another key's tables
+#define KC_CTR_FELL_BACK 3 // wide-eligible keys that took full tables (over the cap, or no slot left)
+#define KC_CTRS 8
+struct KeyCache {
+  uint32_t* ctr = nullptr;
+  KcOwner* owners[2] = {nullptr, nullptr};
+  uint32_t* live[2] = {nullptr, nullptr};
+  uint32_t* freel[2] = {nullptr, nullptr};
+  uint32_t* index[2] = {nullptr, nullptr};
+  uint32_t slots = 0, size = 0, bits = 0;
+  bool dirty = false;
+  __host__ __device__ bool on() const { return ctr != nullptr; }
+};
+static inline size_t key_cache_total(uint32_t slots) {
+  if (!slots) return 0;
+  return 256 + 2 * (al256((size_t)slots * sizeof(KcOwner)) + 2 * al256((size_t)slots * sizeof(uint32_t)) +
+                    al256((size_t)kc_index_size(slots) * sizeof(uint32_t)));
+}
+static inline KeyCache key_cache(void* base, uint32_t slots, uint32_t bits, bool dirty) {
+  KeyCache k;
+  if (!base || !slots) return k;
+  uint8_t* p = (uint8_t*)base;
+  k.ctr = (uint32_t*)p;
+  p += 256;
+  for (int q = 0; q < 2; ++q) {
+    k.owners[q] = (KcOwner*)p;
+    p += al256((size_t)slots * sizeof(KcOwner));
+  }
+  for (int q = 0; q < 2; ++q) {
+    k.live[q] = (uint32_t*)p;
+    p += al256((size_t)slots * sizeof(uint32_t));
+  }
+  for (int q = 0; q < 2; ++q) {
+    k.freel[q] = (uint32_t*)p;
+    p += al256((size_t)slots * sizeof(uint32_t));
+  }
+  k.size = kc_index_size(slots);
+  for (int q = 0; q < 2; ++q) {
+    k.index[q] = (uint32_t*)p;
+    p += al256((size_t)k.size * sizeof(uint32_t));
+  }
+  k.slots = slots;
+  k.bits = bits;
+  k.dirty = dirty;
+  return k;
+}
+
 #define ED_ROW_PARK_BYTES ((size_t)EdCfg::kMult * ED_PARK_DWORDS * 4)
 #define EC_ROW_PARK_BYTES ((size_t)EC_MULT * EC_ROW_PARK * 4)
 #define ROW0_COUNT_AT 8    // row0_count = full_count + 8 (the 256-B count block)
@@ -268,6 +322,7 @@ struct KeyWs {
   struct EcWideSlot* wec;
   uint32_t cap_ed, cap_ec;
   uint32_t min_ed, min_ec;
+  KeyCache kc;  // the context's wide-table cache (kc.on() false: every wide key's tables are built)
   // the counting plan (plan_sort.hip): per key its ticket in its (class, mode, short / long) group
   // (2n), the per-chunk bucket counts and their exclusive scan by bucket rank (2n + 1 each, plus
   // one scan partial per 16k-bucket tile), and 64 words of group counts [0, 32) / group bases [32, 64)
@@ -354,14 +409,19 @@ static inline uint32_t wide_cap(uint32_t n_keys, uint64_t n_items, uint32_t max_
 static inline size_t wide_pool_bytes(uint32_t cap) {
   return cap ? al256((size_t)cap * sizeof(EdWideSlot)) + al256((size_t)cap * sizeof(EcWideSlot)) : 0;
 }
-static inline WidePool wide_pool(void* base, uint32_t cap) {
+// The pools over a buffer allocated for `slots` slots, of which this call may use `cap`: the ECDSA
+// half starts where the allocation put it, whatever the call's cap, so a slot keeps its address
+// (and the tables the context's cache left in it) from call to call.
+static inline WidePool wide_pool(void* base, uint32_t cap, uint32_t slots = 0) {
   WidePool p;
   p.min_ed = KEY_WIDE_MIN_USES_ED;
   p.min_ec = KEY_WIDE_MIN_USES_EC;
-  if (!base || !cap) return p;
+  if (!slots) slots = cap;
+  if (!base || !cap || cap > slots) return p;
   p.ed = base;
-  p.ec = (uint8_t*)base + al256((size_t)cap * sizeof(EdWideSlot));
+  p.ec = (uint8_t*)base + al256((size_t)slots * sizeof(EdWideSlot));
   p.cap_ed = p.cap_ec = cap;
+  p.slots = slots;
   return p;
 }
 
@@ -418,6 +478,7 @@ static inline KeyWs key_ws(void* base, uint32_t n_keys, const WidePool* wp = nul
   w.cap_ec = wp ? wp->cap_ec : 0;
   w.min_ed = wp && wp->min_ed ? wp->min_ed : KEY_WIDE_MIN_USES_ED;
   w.min_ec = wp && wp->min_ec ? wp->min_ec : KEY_WIDE_MIN_USES_EC;
+  w.kc = wp && wp->cache && wp->cap_ed ? key_cache(wp->cache, wp->slots, wp->cache_bits, wp->cache_dirty) : KeyCache{};
   return w;
 }
 static inline size_t key_ws_bytes(uint32_t n_keys) {
@@ -520,6 +581,10 @@ static inline const EcGWideTab* gwide(const void* d_btab, int curve) {
 // Intermediate per-item status codes (never returned to the caller)
 #define ED_PENDING 254u
 #define EC_PENDING_BASE 250u  // + curve: parsed + hashed, awaiting the ladder
+
+// verify.hip: after plan class c's wide row builds, on their stream, the slots the call claimed in
+// the wide-table cache become valid (no-op without the cache)
+void kc_launch_commit(int c, uint32_t n_keys, const KeyWs& w, hipStream_t stream);
 
 // Per-scheme halves (verify_ed.hip / verify_ec.hip)
 hipError_t ed_upload_constants();

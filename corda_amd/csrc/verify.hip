@@ -99,19 +99,45 @@ __device__ __forceinline__ void list_append(int c, uint32_t i, uint32_t n_keys, 
   }
 }
 
+// The wide-table cache (key_cache.h) at the start of a call, one block per pool: every slot whose
+// tables are not known to be complete is empty again, nothing is live, the counters are zero, and
+// the index holds the valid owners (at most KEY_WIDE_MAX a pool: one block, two barriers).
+#define KC_BLOCK 1024
+__global__ void __launch_bounds__(KC_BLOCK) k_kc_begin(KeyCache kc) {
+  const int pool = blockIdx.x;
+  KcOwner* owners = kc.owners[pool];
+  uint32_t* index = kc.index[pool];
+  if (threadIdx.x < KC_CTRS) kc.ctr[pool * KC_CTRS + threadIdx.x] = 0;
+  for (uint32_t b = threadIdx.x; b < kc.size; b += KC_BLOCK) index[b] = 0;
+  for (uint32_t s = threadIdx.x; s < kc.slots; s += KC_BLOCK) kc_begin_slot(owners, kc.live[pool], s, kc.dirty);
+  __syncthreads();
+  for (uint32_t s = threadIdx.x; s < kc.slots; s += KC_BLOCK)
+    if (owners[s].state == KC_VALID) kc_index_insert(index, kc.size, kc.bits, owners, s);
+}
+
+__device__ __forceinline__ void kc_load_key(KcKey& k, const cg_key& key, const uint8_t* arena, uint64_t arena_len) {
+  kc_key_load(k, key.scheme, key.fmt, key.len, arena, arena_len, key.off);
+}
+
 // Table mode per key: wide tables for keys with >= min_ed / min_ec items while the family's
 // wide pool has slots (one atomic per wide key: they are few), else full tables from
 // ED_DIRECT_MAX_USES items, quarter tables from KEY_QUARTER_MIN_USES, else row 0; the keys of each
 // mode compacted per scheme class (row0 lists every used key without wide tables). One wave a block.
+// With the wide-table cache (kc.on()), the same keys are wide, but a key whose tables the context
+// still holds takes their slot (wide_idx) and joins no build list; the others are listed in `wide`
+// without a slot, which k_kc_claim gives them.
 __global__ void __launch_bounds__(64) k_key_classify(const cg_key* __restrict__ keys, uint32_t n_keys,
                                                      uint32_t* __restrict__ uses, const uint8_t* __restrict__ seen,
                                                      uint32_t* __restrict__ full, uint32_t* __restrict__ full_count,
                                                      uint32_t* __restrict__ wide_idx, uint32_t* __restrict__ wide,
                                                      uint32_t* __restrict__ wide_count, uint32_t* __restrict__ row0,
                                                      uint32_t* __restrict__ quart, uint32_t cap_ed, uint32_t cap_ec,
-                                                     uint32_t min_ed, uint32_t min_ec, uint32_t skip_mask) {
+                                                     uint32_t min_ed, uint32_t min_ec, uint32_t skip_mask,
+                                                     const uint8_t* __restrict__ arena, uint64_t arena_len,
+                                                     KeyCache kc) {
   const uint32_t i = blockIdx.x * 64 + threadIdx.x;
   int c = -1, cw = -1, c0 = -1, cq = -1;  // full list, wide list, row-0 list, quarter list
+  bool is_wide = false;
   uint32_t u = 0;
   if (i < n_keys) {  // the estimate, made exact where it matters: a used key counts >= 1
     u = uses[i];
@@ -132,14 +158,30 @@ __global__ void __launch_bounds__(64) k_key_classify(const cg_key* __restrict__ 
       if (cap) {
         const uint32_t slot = atomicAdd(&wide_count[PLAN_CLASSES + pool], 1u);
         if (slot < cap) {
-          wide_idx[i] = slot;
-          cw = c;
+          is_wide = true;
+          if (!kc.on()) {
+            wide_idx[i] = slot;
+            cw = c;
+          } else {
+            KcKey k;
+            kc_load_key(k, keys[i], arena, arena_len);
+            const uint32_t hit = kc_probe(kc.index[pool], kc.size, kc.bits, kc.owners[pool], k);
+            if (hit != KC_NONE) {
+              wide_idx[i] = hit;
+              kc.live[pool][hit] = 1;
+              atomicAdd(&kc.ctr[pool * KC_CTRS + KC_CTR_HITS], 1u);
+            } else {
+              cw = c;  // k_kc_claim finds it a slot
+            }
+          }
           c = -1;
+        } else if (kc.on()) {
+          atomicAdd(&kc.ctr[pool * KC_CTRS + KC_CTR_FELL_BACK], 1u);
         }
       }
     }
   }
-  if (i < n_keys && u >= 1 && cw < 0) {  // every used key without wide tables gets its row 0
+  if (i < n_keys && u >= 1 && !is_wide) {  // every used key without wide tables gets its row 0
     const uint8_t s = keys[i].scheme;
     c0 = s == CG_EDDSA_ED25519_SHA512 ? PLAN_ED
        : s == CG_ECDSA_SECP256R1_SHA256 ? PLAN_R1
@@ -156,6 +198,92 @@ __global__ void __launch_bounds__(64) k_key_classify(const cg_key* __restrict__ 
   list_append(cw, i, n_keys, wide, wide_count);
   list_append(c0, i, n_keys, row0, full_count + ROW0_COUNT_AT);
   list_append(cq, i, n_keys, quart, full_count + QUART_COUNT_AT);
+}
+
+// The cache's claim pass, one block per pool, after k_key_classify: the slots no key of this call
+// hit are listed (empty ones first), and the r-th key of the pool's build lists (Ed25519; secp256r1
+// then secp256k1) takes the r-th of them, its owner pending until the builds commit. The call's
+// wide keys number at most its cap, the slots at least that, so every listed key finds one; were
+// the list ever short, the keys at its tail take full tables, as a key over the cap does.
+__global__ void __launch_bounds__(KC_BLOCK) k_kc_claim(const cg_key* __restrict__ keys, uint32_t n_keys,
+                                                       const uint8_t* __restrict__ arena, uint64_t arena_len,
+                                                       uint32_t* __restrict__ wide_idx, uint32_t* __restrict__ wide,
+                                                       uint32_t* __restrict__ wide_count, uint32_t* __restrict__ full,
+                                                       uint32_t* __restrict__ full_count, uint32_t* __restrict__ row0,
+                                                       uint32_t skip_mask, KeyCache kc) {
+  __shared__ uint32_t sc[2][KC_BLOCK];
+  __shared__ uint32_t tot[2];
+  const int pool = blockIdx.x;
+  const uint32_t t = threadIdx.x;
+  KcOwner* owners = kc.owners[pool];
+  uint32_t cnt[2];
+  kc_free_count(owners, kc.live[pool], kc.slots, t, KC_BLOCK, cnt);
+  sc[0][t] = cnt[0];
+  sc[1][t] = cnt[1];
+  __syncthreads();
+  for (uint32_t d = 1; d < KC_BLOCK; d <<= 1) {  // inclusive scans of both counts
+    const uint32_t a = t >= d ? sc[0][t - d] : 0u, b = t >= d ? sc[1][t - d] : 0u;
+    __syncthreads();
+    sc[0][t] += a;
+    sc[1][t] += b;
+    __syncthreads();
+  }
+  if (t == KC_BLOCK - 1) {
+    tot[0] = sc[0][t];
+    tot[1] = sc[1][t];
+  }
+  __syncthreads();
+  kc_free_fill(owners, kc.live[pool], kc.slots, t, KC_BLOCK, sc[0][t] - cnt[0], tot[0] + sc[1][t] - cnt[1],
+               kc.freel[pool]);
+  const uint32_t nfree = tot[0] + tot[1];
+  const int c_lo = pool == 0 ? PLAN_ED : PLAN_R1, c_hi = pool == 0 ? PLAN_ED : PLAN_K1;
+  static_assert(PLAN_R1 + 1 == PLAN_K1, "the ECDSA pool's classes are adjacent");
+  uint32_t n_c[2] = {0, 0};
+  for (int c = c_lo; c <= c_hi; ++c) n_c[c - c_lo] = wide_count[c];
+  __syncthreads();  // the free list is written, the list lengths are read
+  uint32_t base = 0;
+  for (int c = c_lo; c <= c_hi; ++c) {
+    const uint32_t n = n_c[c - c_lo];
+    for (uint32_t l = t; l < n; l += KC_BLOCK) {
+      const uint32_t i = wide[(size_t)c * n_keys + l];
+      KcKey k;
+      kc_load_key(k, keys[i], arena, arena_len);
+      bool evicted;
+      const uint32_t s = kc_claim(owners, kc.freel[pool], nfree, base + l, k, &evicted);
+      if (s != KC_NONE) {
+        wide_idx[i] = s;
+        if (evicted) atomicAdd(&kc.ctr[pool * KC_CTRS + KC_CTR_EVICTED], 1u);
+      } else {  // full tables and a row 0, like a key over the cap (k_key_classify)
+        full[(size_t)c * n_keys + atomicAdd(&full_count[c], 1u)] = i;
+        row0[(size_t)c * n_keys + atomicAdd(&full_count[ROW0_COUNT_AT + c], 1u)] = i;
+        const uint32_t f = c == PLAN_R1 ? 0u : c == PLAN_K1 ? 1u : 2u;
+        if ((skip_mask >> f) & 1u) atomicOr(&full_count[SKIP_MISMATCH_AT], 1u << f);
+        atomicAdd(&kc.ctr[pool * KC_CTRS + KC_CTR_FELL_BACK], 1u);
+      }
+    }
+    if (t == 0) wide_count[c] = base >= nfree ? 0u : (n < nfree - base ? n : nfree - base);  // the claimed head
+    base += n;
+  }
+}
+
+// After class c's wide row builds, on their stream: the slots this call claimed hold complete
+// tables (valid) unless their key did not decode (empty again: such a key is never cached).
+__global__ void __launch_bounds__(256) k_kc_commit(int c, uint32_t n_keys, const EdKeyHdr* __restrict__ hdr,
+                                                   const uint32_t* __restrict__ wide,
+                                                   const uint32_t* __restrict__ wide_count,
+                                                   const uint32_t* __restrict__ wide_idx, KeyCache kc) {
+  const int pool = c == PLAN_ED ? 0 : 1;
+  const uint32_t n = wide_count[c];
+  for (uint32_t l = blockIdx.x * blockDim.x + threadIdx.x; l < n; l += gridDim.x * blockDim.x) {
+    const uint32_t i = wide[(size_t)c * n_keys + l];
+    if (kc_commit(kc.owners[pool], wide_idx[i], hdr[i].status == 0))
+      atomicAdd(&kc.ctr[pool * KC_CTRS + KC_CTR_BUILT], 1u);
+  }
+}
+void kc_launch_commit(int c, uint32_t n_keys, const KeyWs& w, hipStream_t stream) {
+  if (!w.kc.on()) return;
+  hipLaunchKernelGGL(k_kc_commit, dim3(8), dim3(256), 0, stream, c, n_keys, (const EdKeyHdr*)w.hdr,
+                     (const uint32_t*)w.wide, (const uint32_t*)w.wide_count, (const uint32_t*)w.wide_idx, w.kc);
 }
 
 // The items of family f's row-0 / quarter / full modes -> CG_NOT_RUN when k_key_classify flagged f
@@ -188,9 +316,11 @@ size_t wide_bytes(uint32_t n_keys, uint64_t n_items, uint32_t max_slots) {
 }
 size_t wide_slot_bytes() { return wide_pool_bytes(1); }
 static_assert(kKeyWideMax == KEY_WIDE_MAX, "engine.h mirrors keyws.h");
-WidePool make_wide_pool(void* base, uint32_t n_keys, uint64_t n_items, uint32_t max_slots) {
-  return wide_pool(base, wide_cap(n_keys, n_items, max_slots));
+WidePool make_wide_pool(void* base, uint32_t n_keys, uint64_t n_items, uint32_t max_slots, uint32_t alloc_slots) {
+  return wide_pool(base, wide_cap(n_keys, n_items, max_slots), alloc_slots);
 }
+uint32_t wide_slots(uint32_t n_keys, uint64_t n_items, uint32_t max_slots) { return wide_cap(n_keys, n_items, max_slots); }
+size_t key_cache_bytes(uint32_t slots) { return key_cache_total(slots); }
 size_t item_ws_bytes(uint64_t n_items) { return item_ws_total(n_items); }
 size_t btab_bytes() { return const_tab_bytes(); }
 size_t btab_scratch_bytes() { return const_scratch_bytes(); }
@@ -334,9 +464,15 @@ hipError_t launch_keyprep(const cg_key* d_keys, uint32_t n_keys, const uint8_t* 
     }
     fork->pending.skip_mask = skip_mask;
   }
+  // the wide-table cache (key_cache.h): its index before the classification probes it, the claim
+  // pass after; all on this stream, ahead of the fork
+  if (w.kc.on()) hipLaunchKernelGGL(k_kc_begin, dim3(2), dim3(KC_BLOCK), 0, stream, w.kc);
   hipLaunchKernelGGL(k_key_classify, dim3((n_keys + 63) / 64), dim3(64), 0, stream, d_keys, n_keys, w.uses,
                      (const uint8_t*)w.seen, w.full, w.full_count, w.wide_idx, w.wide, w.wide_count, w.row0,
-                     w.quart, w.cap_ed, w.cap_ec, w.min_ed, w.min_ec, skip_mask);
+                     w.quart, w.cap_ed, w.cap_ec, w.min_ed, w.min_ec, skip_mask, d_arena, arena_len, w.kc);
+  if (w.kc.on())
+    hipLaunchKernelGGL(k_kc_claim, dim3(2), dim3(KC_BLOCK), 0, stream, d_keys, n_keys, d_arena, arena_len, w.wide_idx,
+                       w.wide, w.wide_count, w.full, w.full_count, w.row0, skip_mask, w.kc);
   if (!fork || serial) {
     if (fork) {  // the item stages still wait for these events
       fork->pending.on = false;
@@ -584,7 +720,7 @@ hipError_t launch_verify(const cg_key* d_keys, uint32_t n_keys, const cg_item* d
 static_assert(ED_WIDE_BW == EC_WIDE_GW, "one fixed-base radix per build (Makefile VARIANTS)");
 const EngineVariant& variant() {
   static const EngineVariant v = {(uint32_t)ED_WIDE_BW, upload_constants, keyprep_bytes, wide_bytes, wide_slot_bytes,
-                                  make_wide_pool, btab_bytes, btab_scratch_bytes, init_btab, item_ws_bytes,
+                                  make_wide_pool, wide_slots, key_cache_bytes, btab_bytes, btab_scratch_bytes, init_btab, item_ws_bytes,
                                   launch_keyprep, launch_key_tables, launch_items, launch_items_plan,
                                   launch_items_front, launch_items_back};
   return v;

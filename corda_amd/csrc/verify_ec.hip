@@ -592,6 +592,7 @@ static void launch_keyprep_tabs(const cg_key* d_keys, uint32_t n_keys, const Key
       hipLaunchKernelGGL(k_ec_wide_bwd<C>, dim3((unsigned)((gl + B - 1) / B)), dim3(B), 0, stream, n_keys, w.hdr,
                          wl, wc, wi, w.wec);
     }
+    kc_launch_commit(C == CG_CURVE_R1 ? PLAN_R1 : PLAN_K1, n_keys, w, stream);
   }
 }
 

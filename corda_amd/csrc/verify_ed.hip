@@ -1081,6 +1081,7 @@ void ed_launch_keyprep_tabs(const cg_key* d_keys, uint32_t n_keys, const KeyWs& 
       hipLaunchKernelGGL(k_ed_wide_bwd, dim3((unsigned)((gl + B - 1) / B)), dim3(B), 0, stream, n_keys, w.hdr, wl,
                          wc, wi, w.wed);
     }
+    kc_launch_commit(PLAN_ED, n_keys, w, stream);
   }
 }
 

@@ -18,13 +18,15 @@ def _p(a):
 
 
 class Engine:
-    def __init__(self, device=0, chunk_items=0, stage_timing=False, host_threads=0, table_bytes_max=0, rsa=False):
-        """rsa: CG_FLAG_RSA, RSA_SHA256 items with a key the device decode accepts are verified on the
+    def __init__(self, device=0, chunk_items=0, stage_timing=False, host_threads=0, table_bytes_max=0, rsa=False,
+                 key_cache=True):
+        """key_cache=False: CG_FLAG_NO_KEY_CACHE, every call builds its hot keys' wide tables. rsa: CG_FLAG_RSA, RSA_SHA256 items with a key the device decode accepts are verified on the
         GPU (off: they stay UNSUPPORTED, as every other RSA key does either way); host_threads: cg_config.host_threads (0: CG_HOST_THREADS, else the CPU quota divided by the
         contexts open in this process); table_bytes_max: HBM the constant fixed-base tables may take
         (0: automatic; include/cordagpu.h, corda_amd/csrc/table_budget.h)."""
         L = _lib.lib()
         flags = (_lib.FLAG_STAGE_TIMING if stage_timing else 0) | (_lib.FLAG_RSA if rsa else 0)
+        flags |= 0 if key_cache else _lib.FLAG_NO_KEY_CACHE
         cfg = _lib.cg_config(device, flags, 0, 0, chunk_items, host_threads, 0, table_bytes_max)
         h = ctypes.c_void_p()
         _lib.check(L.cg_open(ctypes.byref(h), ctypes.byref(cfg)), f"cg_open(device={device})")
@@ -65,6 +67,16 @@ class Engine:
         if rc < 0:
             _lib.check(rc, "cg_stage_times")
         return {name: (ms[k], cnt[k]) for k, name in enumerate(_lib.STAGE_NAMES)}
+
+    def key_cache_stats(self):
+        """cg_key_cache_stats (waits for the context's stream): enabled, slots, and the last call's hits, built,
+        evicted and fell_back, each a pair (Ed25519 pool, ECDSA pool)."""
+        inf = _lib.cg_key_cache_info()
+        _lib.check(_lib.lib().cg_key_cache_stats(self._h, ctypes.byref(inf)), "cg_key_cache_stats")
+        out = {"enabled": bool(inf.enabled), "slots": inf.slots}
+        for k in ("hits", "built", "evicted", "fell_back"):
+            out[k] = tuple(getattr(inf, k))
+        return out
 
     # ------------------------------------------------------------------ signatures
     def verify(self, batch, mode=MODE_DOVERIFY):

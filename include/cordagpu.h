@@ -149,6 +149,8 @@ typedef struct cg_tx {
 #define CG_FLAG_STAGE_TIMING 1u /* time every item stage with HIP events on the stream it runs on (cg_stage_times) */
 #define CG_FLAG_RSA 2u          /* verify CG_RSA_SHA256 items on the device (off: they stay CG_UNSUPPORTED, no RSA
                                    kernel runs and no RSA workspace is allocated) */
+#define CG_FLAG_NO_KEY_CACHE 8u /* every call builds the wide tables of its hot keys (cg_key_cache_stats); bit 4u is
+                                   unassigned and rejected like every unknown bit */
 
 /* Item stages reported by cg_stage_times (one launch per verify chunk each). */
 enum {
@@ -315,6 +317,23 @@ int cg_verify_items_device(cg_ctx* ctx, const cg_key* d_keys, uint32_t n_keys, c
  * launches_out[stage] = their number, for stage < min(n, CG_STAGES); resets the record. Returns
  * the number of stages written. */
 int cg_stage_times(cg_ctx* ctx, double* ms_out, uint32_t* launches_out, uint32_t n);
+
+/* The context's wide-table cache. A key with many signatures in a call (>= 1,536 Ed25519, >= 512
+ * ECDSA) gets "wide" tables, and a context keeps them between calls, keyed by the scheme and the
+ * exact key bytes: a call builds them only for the hot keys it does not find (a full byte compare
+ * decides, never a hash alone). Verdicts do not depend on it. On by default; off for a context with
+ * CG_FLAG_NO_KEY_CACHE, for a process with CG_KEY_CACHE=0 in the environment at cg_open.
+ * cg_key_cache_stats waits for the context's stream and reports the last call's counts per pool
+ * ([0] Ed25519, [1] ECDSA, both curves). */
+typedef struct cg_key_cache_info {
+  uint32_t enabled;      /* 1: the cache is on for this context */
+  uint32_t slots;        /* wide-table slots per pool the context holds (0: no pool allocated yet) */
+  uint32_t hits[2];      /* hot keys whose tables were found */
+  uint32_t built[2];     /* tables built and kept (a key that does not decode is never kept) */
+  uint32_t evicted[2];   /* slots taken from another key's tables */
+  uint32_t fell_back[2]; /* hot keys that took full tables instead (more hot keys than slots) */
+} cg_key_cache_info;     /* 40 bytes */
+int cg_key_cache_stats(cg_ctx* ctx, cg_key_cache_info* out);
 
 /* Hashing. digests_out: 32*n (sha256) / 64*n (sha512) bytes. */
 int cg_sha256_batch(cg_ctx* ctx, const cg_span* spans, uint64_t n, const uint8_t* arena, uint64_t arena_len,
