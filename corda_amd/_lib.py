@@ -153,6 +153,26 @@ def lib():
                     L.cg_pool_verify_tx_signatures_packed.argtypes = [vp, vp, u32, vp, u64, vp, u64, vp, u64, vp, u32,
                                                                       vp, u64, u32, vp, ctypes.POINTER(cg_pool_stats)]
                     L.cg_pool_verify_tx_signatures_packed.restype = i32
+            if hasattr(L, "cg_tx_verdicts"):  # older builds (A/B variants) lack the per-transaction verdicts
+                txv = [vp, u32, u64, vp, vp, u32, vp, vp, u64, vp, u32, vp, u32, vp, vp]
+                L.cg_tx_verdicts.argtypes = [vp] + txv
+                L.cg_tx_verdicts.restype = i32
+                L.cg_tx_verdicts_device.argtypes = [vp] + txv + [vp]
+                L.cg_tx_verdicts_device.restype = i32
+                tables = [vp, vp, u64, vp, u32, vp, u32]  # key_class, checks, n_tx, reqs, n_reqs, nodes, n_nodes
+                L.cg_verify_required_signatures_packed.argtypes = [vp, vp, u32, vp, u64, vp, u64, vp, u64, vp, u32, vp,
+                                                                   u64, u32] + tables + [vp, vp, vp,
+                                                                                         ctypes.POINTER(cg_stats)]
+                L.cg_verify_required_signatures_packed.restype = i32
+                L.cg_verify_required_signatures_packed_device.argtypes = [vp, vp, u32, vp, u64, vp, u64, u64, u64, vp,
+                                                                          u32, vp, u64, u32] + tables + [vp, vp, vp, vp]
+                L.cg_verify_required_signatures_packed_device.restype = i32
+                if pool:
+                    L.cg_pool_verify_required_signatures_packed.argtypes = [vp, vp, u32, vp, u64, vp, u64, vp, u64, vp,
+                                                                            u32, vp, u64, u32] + tables + [
+                                                                                vp, vp, vp,
+                                                                                ctypes.POINTER(cg_pool_stats)]
+                    L.cg_pool_verify_required_signatures_packed.restype = i32
             if hasattr(L, "cg_context_info"):  # round 6: the fixed-base table budget
                 L.cg_context_info.argtypes = [vp, ctypes.POINTER(cg_info)]
                 L.cg_context_info.restype = i32

@@ -2,7 +2,9 @@
 
 ``KEY_DTYPE`` / ``ITEM_DTYPE`` / ``SPAN_DTYPE`` / ``COMPONENT_DTYPE`` / ``TX_DTYPE`` /
 ``TXSIG_DTYPE`` / ``TMPL_DTYPE`` are byte-for-byte ``cg_key`` / ``cg_item`` / ``cg_span`` /
-``cg_component`` / ``cg_tx`` / ``cg_txsig`` / ``cg_signable_tmpl`` of include/cordagpu.h. ``BatchBuilder`` packs (key, sig, clear) triples the way a JVM
+``cg_component`` / ``cg_tx`` / ``cg_txsig`` / ``cg_signable_tmpl`` of include/cordagpu.h
+(``TX_CHECK_DTYPE`` / ``REQ_NODE_DTYPE`` / ``TX_VERDICT_DTYPE``: ``cg_tx_check`` / ``cg_req_node`` /
+``cg_tx_verdict``, packed by ``RequirementBuilder``). ``BatchBuilder`` packs (key, sig, clear) triples the way a JVM
 caller of ``Crypto.verifyBatch`` would: each distinct PublicKey object once in the key
 table (as TransactionSignature.by references it), signatures and clear data appended to
 one arena.
@@ -32,6 +34,17 @@ PMT_NODE, PMT_LEAF, PMT_INCLUDED = 0, 1, 2
 FLEAF_SALT, FLEAF_HASH = 1, 2
 FTX_FILTERED = 1
 assert TXSIG_DTYPE.itemsize == 24 and TMPL_DTYPE.itemsize == 24
+# per-transaction verdicts (cg_tx_check / cg_req_node / cg_tx_verdict)
+TX_CHECK_DTYPE = np.dtype([("first_sig", "<u8"), ("n_sigs", "<u4"), ("first_req", "<u4"), ("n_req", "<u4"),
+                           ("reserved", "<u4")])
+REQ_NODE_DTYPE = np.dtype([("a", "<u4"), ("n_children", "<u4"), ("weight", "<i4"), ("threshold", "<i4")])
+TX_VERDICT_DTYPE = np.dtype([("first_bad", "<u4"), ("status", "u1"), ("flags", "u1"), ("n_missing", "<u2")])
+assert TX_CHECK_DTYPE.itemsize == 24 and REQ_NODE_DTYPE.itemsize == 16 and TX_VERDICT_DTYPE.itemsize == 8
+REQ_FULFILLED, REQ_MISSING, REQ_HOST, REQ_BAD = 0, 1, 2, 255
+TXV_SPAN_BAD, TXV_REQ_HOST, TXV_COMPOSITE_SIGNER = 1, 2, 4
+REQ_MAX_DEPTH, REQ_MAX_VISITS = 8, 4096
+NO_BAD = 0xFFFFFFFF
+COMPOSITE_KEY = 6
 assert KEY_DTYPE.itemsize == 16 and ITEM_DTYPE.itemsize == 32 and SPAN_DTYPE.itemsize == 16
 assert COMPONENT_DTYPE.itemsize == 16 and TX_DTYPE.itemsize == 24
 
@@ -327,3 +340,79 @@ class TxSigBuilder(BatchBuilder):
             tmpls[i] = t
         ids = np.frombuffer(b"".join(self._ids), dtype=np.uint8).copy() if self._ids else np.zeros(0, np.uint8)
         return TxSigBatch(b.keys, ids, sigs, tmpls, b.arena)
+
+
+class RequirementBuilder:
+    """Flattens the required keys of a batch of transactions (PublicKey / CompositeKey objects) into the
+    ``reqs`` / ``nodes`` tables of cg_tx_verdicts, and assigns key classes from the keys' own ``__eq__``
+    / ``__hash__`` (PublicKey compares canonical SPKI, so the raw and the SPKI form of a key share a
+    class; a required key that never signs simply gets a class no signer has).
+
+    A requirement is a root node: a leaf (``a`` = class) or a CompositeKey (``a`` = its first child).
+    The children of a CompositeKey are one contiguous block of nodes, each carrying its weight inside
+    that parent; equal CompositeKeys share one block and equal required keys one root. ``build`` lays
+    the roots out first and the blocks by decreasing height, so every child index is greater than
+    its parent's, as the device walk demands."""
+
+    def __init__(self):
+        self._classes = {}
+        self._roots = {}      # required key -> root ordinal
+        self._root_keys = []
+        self._reqs = []       # root ordinals, in reqs order
+
+    def key_class(self, key):
+        """The equality class of a key (a PublicKey, or a CompositeKey that signs)."""
+        return self._classes.setdefault(key, len(self._classes))
+
+    def key_classes(self, keys):
+        """``key_class`` array for a key table whose entry k is ``keys[k]``."""
+        return np.array([self.key_class(k) for k in keys], dtype=np.uint32)
+
+    def add_transaction(self, required_keys):
+        """Appends one transaction's required keys; returns (first_req, n_req) for its cg_tx_check."""
+        first = len(self._reqs)
+        for k in required_keys:
+            r = self._roots.get(k)
+            if r is None:
+                r = self._roots[k] = len(self._root_keys)
+                self._root_keys.append(k)
+            self._reqs.append(r)
+        return first, len(self._reqs) - first
+
+    @staticmethod
+    def _is_composite(k):
+        return hasattr(k, "children") and hasattr(k, "threshold")
+
+    def build(self):
+        """(reqs uint32[n_reqs], nodes REQ_NODE_DTYPE[n_nodes])."""
+        height, order = {}, []
+
+        def visit(k):  # post-order over the distinct composites: height 1 = leaves only
+            if k in height:
+                return height[k]
+            h = 1 + max([visit(c.node) for c in k.children if self._is_composite(c.node)], default=0)
+            height[k] = h
+            order.append(k)
+            return h
+
+        for k in self._root_keys:
+            if self._is_composite(k):
+                visit(k)
+        blocks, at = {}, len(self._root_keys)
+        for k in sorted(order, key=lambda c: -height[c]):  # stable: equal heights keep their order
+            blocks[k] = at
+            at += len(k.children)
+        nodes = np.zeros(at, dtype=REQ_NODE_DTYPE)
+
+        def fill(i, k, weight):
+            if self._is_composite(k):
+                nodes[i] = (blocks[k], len(k.children), weight, k.threshold)
+            else:
+                nodes[i] = (self.key_class(k), 0, weight, 0)
+
+        for i, k in enumerate(self._root_keys):
+            fill(i, k, 0)
+        for k, first in blocks.items():
+            for j, c in enumerate(k.children):
+                fill(first + j, c.node, c.weight)
+        return np.array(self._reqs, dtype=np.uint32), nodes

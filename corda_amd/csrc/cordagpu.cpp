@@ -146,6 +146,8 @@ struct cg_ctx {
   // transaction pipeline: verify items, spliced messages, templates; host-entry staging
   DevBuf txitems, msgs, tmpls, h_txs, h_comps, h_sigs, h_ids, h_txst;
   DevBuf sig12ws;  // the 12-byte signature table's per-block stream offsets (launch_tx_sig12_range)
+  // per-transaction verdicts (txverdict.hip): the long-span list, and the host forms' tables and results
+  DevBuf txvws, txvio;
   // tear-offs: leaf-hash workspace
   DevBuf ftxws;
   // host-buffer verify: a copy stream and one event per pipeline chunk (H2D of chunk k+1 overlaps
@@ -898,7 +900,7 @@ void cg_close(cg_ctx* c) {
   c->aux1.release();
   c->aux2.release();
   for (DevBuf* b : {&c->txitems, &c->msgs, &c->tmpls, &c->h_txs, &c->h_comps, &c->h_sigs, &c->h_ids, &c->h_txst,
-                    &c->ftxws, &c->sig12ws, &c->rsakeys, &c->rsalist})
+                    &c->ftxws, &c->sig12ws, &c->rsakeys, &c->rsalist, &c->txvws, &c->txvio})
     b->release();
   for (int k = 0; k < 3; ++k) {
     if (c->fork.side[k]) {
@@ -1645,6 +1647,79 @@ static hipError_t ensure_events(std::vector<hipEvent_t>& v, uint64_t n) {
   return hipSuccess;
 }
 
+// ---- per-transaction verdicts (txverdict.hip): the host forms' tables, staged in one buffer
+struct TxvHost {
+  const uint32_t* key_class = nullptr;
+  const cg_tx_check* checks = nullptr;
+  uint64_t n_tx = 0;
+  const uint32_t* reqs = nullptr;
+  uint32_t n_reqs = 0;
+  const cg_req_node* nodes = nullptr;
+  uint32_t n_nodes = 0;
+  cg_tx_verdict* verdicts_out = nullptr;
+  uint8_t* req_status_out = nullptr;
+};
+struct TxvDev {
+  uint32_t* key_class = nullptr;
+  cg_tx_check* checks = nullptr;
+  uint32_t* reqs = nullptr;
+  cg_req_node* nodes = nullptr;
+  cg_tx_verdict* verdicts = nullptr;
+  uint8_t* req_status = nullptr;
+};
+static hipError_t ensure_txv_ws(cg_ctx* c, uint64_t n_tx) {
+  const size_t need = cg::tx_verdicts_ws_bytes(n_tx);
+  if (c->txvws.cap >= need) return hipSuccess;
+  hipError_t e = hipDeviceSynchronize();
+  if (e == hipSuccess) e = c->txvws.ensure(need);
+  return e;
+}
+// Carves c->txvio for the tables of `h` (waits for the device when it grows), and the list workspace.
+static hipError_t txv_stage(cg_ctx* c, const TxvHost& h, uint32_t n_keys, TxvDev* d) {
+  auto up = [](size_t x) { return (x + 15) & ~(size_t)15; };
+  const size_t o_checks = 0, o_nodes = o_checks + up(sizeof(cg_tx_check) * h.n_tx),
+               o_verd = o_nodes + up(sizeof(cg_req_node) * h.n_nodes),
+               o_reqs = o_verd + up(sizeof(cg_tx_verdict) * h.n_tx),
+               o_class = o_reqs + up(sizeof(uint32_t) * h.n_reqs),
+               o_rst = o_class + up(h.key_class ? sizeof(uint32_t) * n_keys : 0), need = o_rst + up(h.n_reqs) + 16;
+  hipError_t e = ensure_txv_ws(c, h.n_tx);
+  if (e == hipSuccess && c->txvio.cap < need) {
+    e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = c->txvio.ensure(need);
+  }
+  if (e != hipSuccess) return e;
+  uint8_t* b = (uint8_t*)c->txvio.p;
+  d->checks = (cg_tx_check*)(b + o_checks);
+  d->nodes = (cg_req_node*)(b + o_nodes);
+  d->verdicts = (cg_tx_verdict*)(b + o_verd);
+  d->reqs = (uint32_t*)(b + o_reqs);
+  d->key_class = h.key_class ? (uint32_t*)(b + o_class) : nullptr;
+  d->req_status = b + o_rst;
+  return hipSuccess;
+}
+static hipError_t txv_upload(const TxvHost& h, uint32_t n_keys, const TxvDev& d, hipStream_t s) {
+  hipError_t e = hipSuccess;
+  if (h.n_tx) e = hipMemcpyAsync(d.checks, h.checks, sizeof(cg_tx_check) * h.n_tx, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess && h.n_nodes)
+    e = hipMemcpyAsync(d.nodes, h.nodes, sizeof(cg_req_node) * h.n_nodes, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess && h.n_reqs)
+    e = hipMemcpyAsync(d.reqs, h.reqs, sizeof(uint32_t) * h.n_reqs, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess && h.key_class && n_keys)
+    e = hipMemcpyAsync(d.key_class, h.key_class, sizeof(uint32_t) * n_keys, hipMemcpyHostToDevice, s);
+  return e;
+}
+static hipError_t txv_download(const TxvHost& h, const TxvDev& d, hipStream_t s) {
+  hipError_t e = hipSuccess;
+  if (h.n_tx) e = hipMemcpyAsync(h.verdicts_out, d.verdicts, sizeof(cg_tx_verdict) * h.n_tx, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess && h.n_reqs) e = hipMemcpyAsync(h.req_status_out, d.req_status, h.n_reqs, hipMemcpyDeviceToHost, s);
+  return e;
+}
+// what a call that failed leaves in the caller's result buffers: nothing ran
+static void txv_fill_not_run(const TxvHost& h) {
+  for (uint64_t t = 0; t < h.n_tx; ++t) h.verdicts_out[t] = cg_tx_verdict{0xFFFFFFFFu, CG_NOT_RUN, CG_TXV_SPAN_BAD, 0};
+  if (h.n_reqs) memset(h.req_status_out, CG_REQ_HOST, h.n_reqs);
+}
+
 // cg_verify_tx_signatures with the ctx lock held. Host side, in order: the key table and key bytes,
 // the template bytes, the ids and the signature table (everything the key tables and the plans
 // need), then the signature bytes chunk by chunk, each copy issued just before its chunk's front
@@ -1653,12 +1728,15 @@ static hipError_t ensure_events(std::vector<hipEvent_t>& v, uint64_t n) {
 // dense in sig_bytes. On the device they follow the caller's arena at sig_region (16-aligned), so the
 // kernels address every byte by an absolute arena offset as in the 24-byte form; a key or template
 // that lies outside [0, arena_len) is moved out of the extended arena too (never reads a signature).
+// txv (cg_verify_required_signatures_packed): the per-transaction verdict kernels follow the last chunk
+// on the same stream; their tables go up on the copy stream behind the last chunk's bytes. status_out
+// may then be null (the statuses stay on the device).
 static int verify_txsig_host_locked(cg_ctx* c, const cg_key* keys, uint32_t n_keys, const uint8_t* ids,
                                     uint64_t n_ids, const cg_txsig* sigs, uint64_t n_sigs,
                                     const cg_signable_tmpl* tmpls, uint32_t n_tmpls, const uint8_t* arena,
                                     uint64_t arena_len, uint32_t mode, uint8_t* status_out, cg_stats* stats,
                                     const cg_txsig_packed* sigs12 = nullptr, const uint8_t* sig_bytes = nullptr,
-                                    uint64_t sig_bytes_len = 0) {
+                                    uint64_t sig_bytes_len = 0, const TxvHost* txv = nullptr) {
   const auto t0 = std::chrono::steady_clock::now();
   const bool packed = sigs12 != nullptr;
   const uint64_t caller_len = arena_len;
@@ -1695,6 +1773,8 @@ static int verify_txsig_host_locked(cg_ctx* c, const cg_key* keys, uint32_t n_ke
   HIP_TRY(c->status.ensure(n_sigs), "hipMalloc(status)");
   HIP_TRY(ensure_txsig_ws(c, n_sigs, n_tmpls, slot), "hipMalloc(tx signature workspace)");
   HIP_TRY(ensure_ws(c, n_keys, per, n_sigs), "hipMalloc(workspace)");
+  TxvDev txd;
+  if (txv) HIP_TRY(txv_stage(c, *txv, n_keys, &txd), "hipMalloc(verdict tables)");
   HIP_TRY(ensure_events(c->seg, nch + 1), "hipEventCreate");
   HIP_TRY(ensure_events(c->segtab, nch), "hipEventCreate");
   static const bool htrace = env_flag("CG_HOST_TRACE", false);
@@ -1761,8 +1841,18 @@ static int verify_txsig_host_locked(cg_ctx* c, const cg_key* keys, uint32_t n_ke
   if (le == hipSuccess && c->fork.mid_front) feed.mid();  // the last front did not consume its hook
   if (feed.copy_err != hipSuccess) return hip_fail(feed.copy_err, "H2D signature bytes");
   HIP_TRY(le, "launch_txsig");
+  if (txv) {  // after the last chunk's back, the joined side streams and the mode guard: all on s by now
+    HIP_TRY(txv_upload(*txv, n_keys, txd, c->copy), "H2D verdict tables");
+    HIP_TRY(hipEventRecord(c->seg[nch], c->copy), "hipEventRecord");
+    HIP_TRY(hipStreamWaitEvent(s, c->seg[nch], 0), "hipStreamWaitEvent");
+    HIP_TRY(cg::launch_tx_verdicts(c->h_sigs.p, (uint32_t)sizeof(cg_txsig_packed), n_sigs, ds, (const cg_key*)c->keys.p,
+                                   n_keys, txd.key_class, txd.checks, (uint32_t)txv->n_tx, txd.reqs, txv->n_reqs,
+                                   txd.nodes, txv->n_nodes, txd.verdicts, txd.req_status, c->txvws.p, s),
+            "launch_tx_verdicts");
+  }
   HIP_TRY(hipEventRecord(c->tev[2], s), "hipEventRecord");
-  HIP_TRY(hipMemcpyAsync(status_out, ds, n_sigs, hipMemcpyDeviceToHost, s), "D2H status");
+  if (status_out) HIP_TRY(hipMemcpyAsync(status_out, ds, n_sigs, hipMemcpyDeviceToHost, s), "D2H status");
+  if (txv) HIP_TRY(txv_download(*txv, txd, s), "D2H verdicts");
   HIP_TRY(hipEventRecord(c->tev[3], s), "hipEventRecord");
   HIP_TRY(order_out(c, s), "hipEventRecord");
   const double h_enq = tr.ms();
@@ -1812,20 +1902,13 @@ int cg_verify_tx_signatures_device(cg_ctx* c, const cg_key* d_keys, uint32_t n_k
   return CG_OK;
 }
 
-int cg_verify_tx_signatures_packed_device(cg_ctx* c, const cg_key* d_keys, uint32_t n_keys, const uint8_t* d_ids,
-                                          uint64_t n_ids, const cg_txsig_packed* d_sigs, uint64_t n_sigs,
-                                          uint64_t sig_bytes_off, uint64_t sig_bytes_len,
-                                          const cg_signable_tmpl* tmpls, uint32_t n_tmpls, const uint8_t* d_arena,
-                                          uint64_t arena_len, uint32_t mode, uint8_t* d_status, void* hip_stream) {
-  const int a = txsig_args("cg_verify_tx_signatures_packed_device", c, n_keys, d_keys, n_ids, d_ids, n_sigs, d_sigs,
-                           d_status, n_tmpls, tmpls, mode);
-  if (a != CG_OK) return a;
-  if (sig_bytes_off > arena_len || sig_bytes_len > arena_len - sig_bytes_off)
-    return fail(CG_ERR_ARG, "cg_verify_tx_signatures_packed_device: the signature stream lies outside the arena");
-  if (n_sigs == 0) return CG_OK;
-  std::lock_guard<std::mutex> g(c->mu);
-  if (c->fault) return fail(CG_ERR_DEVICE, "cg_verify_tx_signatures_packed_device: device fault (injected)");
-  HIP_TRY(hipSetDevice(c->device), "hipSetDevice");
+// cg_verify_tx_signatures_packed_device with the ctx lock held and the device set, up to its last
+// kernel: *s_out is the stream the call runs on (stream_of), order_out is the caller's.
+static int txsig_packed_device_locked(cg_ctx* c, const cg_key* d_keys, uint32_t n_keys, const uint8_t* d_ids,
+                                      uint64_t n_ids, const cg_txsig_packed* d_sigs, uint64_t n_sigs,
+                                      uint64_t sig_bytes_off, uint64_t sig_bytes_len, const cg_signable_tmpl* tmpls,
+                                      uint32_t n_tmpls, const uint8_t* d_arena, uint64_t arena_len, uint32_t mode,
+                                      uint8_t* d_status, void* hip_stream, hipStream_t* s_out) {
   const uint64_t slot = tmpl_slot(tmpls, n_tmpls);
   // equal chunks rounded to the 256-record blocks whose stream offsets are computed once for the table
   uint64_t per = chunk_of(c, n_sigs);
@@ -1857,9 +1940,32 @@ int cg_verify_tx_signatures_packed_device(cg_ctx* c, const cg_key* d_keys, uint3
   p12.sig_region = sig_bytes_off;
   p12.sig_bytes_len = sig_bytes_len;
   p12.d_bases = (const uint64_t*)c->sig12ws.p;
+  *s_out = s;
   HIP_TRY(launch_txsig(c, d_keys, n_keys, d_ids, n_ids, nullptr, n_sigs, tmpls, n_tmpls, d_arena, arena_len, mode,
                        d_status, s, slot, uses, nullptr, &bounds, &p12),
           "launch_txsig");
+  return CG_OK;
+}
+
+int cg_verify_tx_signatures_packed_device(cg_ctx* c, const cg_key* d_keys, uint32_t n_keys, const uint8_t* d_ids,
+                                          uint64_t n_ids, const cg_txsig_packed* d_sigs, uint64_t n_sigs,
+                                          uint64_t sig_bytes_off, uint64_t sig_bytes_len,
+                                          const cg_signable_tmpl* tmpls, uint32_t n_tmpls, const uint8_t* d_arena,
+                                          uint64_t arena_len, uint32_t mode, uint8_t* d_status, void* hip_stream) {
+  const int a = txsig_args("cg_verify_tx_signatures_packed_device", c, n_keys, d_keys, n_ids, d_ids, n_sigs, d_sigs,
+                           d_status, n_tmpls, tmpls, mode);
+  if (a != CG_OK) return a;
+  if (sig_bytes_off > arena_len || sig_bytes_len > arena_len - sig_bytes_off)
+    return fail(CG_ERR_ARG, "cg_verify_tx_signatures_packed_device: the signature stream lies outside the arena");
+  if (n_sigs == 0) return CG_OK;
+  std::lock_guard<std::mutex> g(c->mu);
+  if (c->fault) return fail(CG_ERR_DEVICE, "cg_verify_tx_signatures_packed_device: device fault (injected)");
+  HIP_TRY(hipSetDevice(c->device), "hipSetDevice");
+  hipStream_t s = nullptr;
+  const int rc = txsig_packed_device_locked(c, d_keys, n_keys, d_ids, n_ids, d_sigs, n_sigs, sig_bytes_off,
+                                            sig_bytes_len, tmpls, n_tmpls, d_arena, arena_len, mode, d_status,
+                                            hip_stream, &s);
+  if (rc != CG_OK) return rc;
   HIP_TRY(order_out(c, s), "hipEventRecord");
   return CG_OK;
 }
@@ -1897,6 +2003,193 @@ int cg_verify_tx_signatures(cg_ctx* c, const cg_key* keys, uint32_t n_keys, cons
   const int rc = verify_txsig_host_locked(c, keys, n_keys, ids, n_ids, sigs, n_sigs, tmpls, n_tmpls, arena, arena_len,
                                           mode, status_out, stats);
   if (rc != CG_OK) memset(status_out, CG_NOT_RUN, n_sigs);
+  return rc;
+}
+
+// ---------------------------------------------------------------- per-transaction verdicts
+static int txv_args(const char* fn, uint32_t sig_stride, uint64_t n_sigs, const void* sig_table, const void* status,
+                    uint32_t n_keys, const void* keys, uint64_t n_tx, const void* checks, uint32_t n_reqs,
+                    const void* reqs, uint32_t n_nodes, const void* nodes, const void* verdicts,
+                    const void* req_status) {
+  if (sig_stride != sizeof(cg_txsig_packed) && sig_stride != sizeof(cg_txsig))
+    return fail(CG_ERR_ARG, "%s: sig_stride is neither 12 (cg_txsig_packed) nor 24 (cg_txsig)", fn);
+  if (n_sigs && (!sig_table || !status)) return fail(CG_ERR_ARG, "%s: NULL signature table / status", fn);
+  if (n_keys && !keys) return fail(CG_ERR_ARG, "%s: keys is NULL", fn);
+  if (n_tx && (!checks || !verdicts)) return fail(CG_ERR_ARG, "%s: NULL checks / verdicts", fn);
+  if (n_tx > 0xFFFFFFFFull) return fail(CG_ERR_ARG, "%s: more than 2^32 - 1 transactions", fn);
+  if (n_reqs && (!reqs || !req_status)) return fail(CG_ERR_ARG, "%s: NULL reqs / req_status", fn);
+  if (n_nodes && !nodes) return fail(CG_ERR_ARG, "%s: nodes is NULL", fn);
+  return CG_OK;
+}
+static int txv_reserved(const char* fn, const cg_tx_check* checks, uint64_t n_tx) {
+  for (uint64_t t = 0; t < n_tx; ++t)
+    if (checks[t].reserved != 0) return fail(CG_ERR_ARG, "%s: cg_tx_check.reserved must be 0", fn);
+  return CG_OK;
+}
+
+int cg_tx_verdicts_device(cg_ctx* c, const void* d_sig_table, uint32_t sig_stride, uint64_t n_sigs,
+                          const uint8_t* d_status, const cg_key* d_keys, uint32_t n_keys, const uint32_t* d_key_class,
+                          const cg_tx_check* d_checks, uint64_t n_tx, const uint32_t* d_reqs, uint32_t n_reqs,
+                          const cg_req_node* d_nodes, uint32_t n_nodes, cg_tx_verdict* d_verdicts,
+                          uint8_t* d_req_status, void* hip_stream) {
+  if (!c) return fail(CG_ERR_ARG, "cg_tx_verdicts_device: ctx is NULL");
+  const int a = txv_args("cg_tx_verdicts_device", sig_stride, n_sigs, d_sig_table, d_status, n_keys, d_keys, n_tx,
+                         d_checks, n_reqs, d_reqs, n_nodes, d_nodes, d_verdicts, d_req_status);
+  if (a != CG_OK) return a;
+  if (n_tx == 0 && n_reqs == 0) return CG_OK;
+  std::lock_guard<std::mutex> g(c->mu);
+  if (c->fault) return fail(CG_ERR_DEVICE, "cg_tx_verdicts_device: device fault (injected)");
+  HIP_TRY(hipSetDevice(c->device), "hipSetDevice");
+  HIP_TRY(ensure_txv_ws(c, n_tx), "hipMalloc(verdict workspace)");
+  hipStream_t s = stream_of(c, hip_stream);
+  HIP_TRY(order_in(c, s), "hipStreamWaitEvent");
+  HIP_TRY(cg::launch_tx_verdicts(d_sig_table, sig_stride, n_sigs, d_status, d_keys, n_keys, d_key_class, d_checks,
+                                 (uint32_t)n_tx, d_reqs, n_reqs, d_nodes, n_nodes, d_verdicts, d_req_status,
+                                 c->txvws.p, s),
+          "launch_tx_verdicts");
+  HIP_TRY(order_out(c, s), "hipEventRecord");
+  return CG_OK;
+}
+
+static int tx_verdicts_host_locked(cg_ctx* c, const void* sig_table, uint32_t sig_stride, uint64_t n_sigs,
+                                   const uint8_t* status, const cg_key* keys, uint32_t n_keys, const TxvHost& h) {
+  if (c->fault) return fail(CG_ERR_DEVICE, "cg_tx_verdicts: device fault (injected by cg_pool_inject_fault)");
+  HIP_TRY(hipSetDevice(c->device), "hipSetDevice");
+  TxvDev d;
+  HIP_TRY(txv_stage(c, h, n_keys, &d), "hipMalloc(verdict tables)");
+  if (c->h_sigs.cap < (size_t)sig_stride * n_sigs || c->status.cap < n_sigs || c->keys.cap < sizeof(cg_key) * n_keys) {
+    HIP_TRY(hipDeviceSynchronize(), "hipDeviceSynchronize");
+    HIP_TRY(c->h_sigs.ensure((size_t)sig_stride * n_sigs), "hipMalloc(sigs)");
+    HIP_TRY(c->status.ensure(n_sigs), "hipMalloc(status)");
+    HIP_TRY(c->keys.ensure(sizeof(cg_key) * (n_keys ? n_keys : 1)), "hipMalloc(keys)");
+  }
+  hipStream_t s = c->stream;
+  HIP_TRY(order_in(c, s), "hipStreamWaitEvent");
+  if (n_sigs) {
+    HIP_TRY(hipMemcpyAsync(c->h_sigs.p, sig_table, (size_t)sig_stride * n_sigs, hipMemcpyHostToDevice, s), "H2D sigs");
+    HIP_TRY(hipMemcpyAsync(c->status.p, status, n_sigs, hipMemcpyHostToDevice, s), "H2D status");
+  }
+  if (n_keys) HIP_TRY(hipMemcpyAsync(c->keys.p, keys, sizeof(cg_key) * n_keys, hipMemcpyHostToDevice, s), "H2D keys");
+  HIP_TRY(txv_upload(h, n_keys, d, s), "H2D verdict tables");
+  HIP_TRY(cg::launch_tx_verdicts(c->h_sigs.p, sig_stride, n_sigs, (const uint8_t*)c->status.p, (const cg_key*)c->keys.p,
+                                 n_keys, d.key_class, d.checks, (uint32_t)h.n_tx, d.reqs, h.n_reqs, d.nodes, h.n_nodes,
+                                 d.verdicts, d.req_status, c->txvws.p, s),
+          "launch_tx_verdicts");
+  HIP_TRY(txv_download(h, d, s), "D2H verdicts");
+  HIP_TRY(order_out(c, s), "hipEventRecord");
+  HIP_TRY(hipStreamSynchronize(s), "hipStreamSynchronize");
+  return CG_OK;
+}
+
+int cg_tx_verdicts(cg_ctx* c, const void* sig_table, uint32_t sig_stride, uint64_t n_sigs, const uint8_t* status,
+                   const cg_key* keys, uint32_t n_keys, const uint32_t* key_class, const cg_tx_check* checks,
+                   uint64_t n_tx, const uint32_t* reqs, uint32_t n_reqs, const cg_req_node* nodes, uint32_t n_nodes,
+                   cg_tx_verdict* verdicts_out, uint8_t* req_status_out) {
+  if (!c) return fail(CG_ERR_ARG, "cg_tx_verdicts: ctx is NULL");
+  int a = txv_args("cg_tx_verdicts", sig_stride, n_sigs, sig_table, status, n_keys, keys, n_tx, checks, n_reqs, reqs,
+                   n_nodes, nodes, verdicts_out, req_status_out);
+  if (a == CG_OK) a = txv_reserved("cg_tx_verdicts", checks, n_tx);
+  if (a != CG_OK) return a;
+  if (n_tx == 0 && n_reqs == 0) return CG_OK;
+  TxvHost h;
+  h.key_class = key_class;
+  h.checks = checks;
+  h.n_tx = n_tx;
+  h.reqs = reqs;
+  h.n_reqs = n_reqs;
+  h.nodes = nodes;
+  h.n_nodes = n_nodes;
+  h.verdicts_out = verdicts_out;
+  h.req_status_out = req_status_out;
+  std::lock_guard<std::mutex> g(c->mu);
+  const int rc = tx_verdicts_host_locked(c, sig_table, sig_stride, n_sigs, status, keys, n_keys, h);
+  if (rc != CG_OK) txv_fill_not_run(h);
+  return rc;
+}
+
+int cg_verify_required_signatures_packed_device(cg_ctx* c, const cg_key* d_keys, uint32_t n_keys,
+                                                const uint8_t* d_ids, uint64_t n_ids, const cg_txsig_packed* d_sigs,
+                                                uint64_t n_sigs, uint64_t sig_bytes_off, uint64_t sig_bytes_len,
+                                                const cg_signable_tmpl* tmpls, uint32_t n_tmpls,
+                                                const uint8_t* d_arena, uint64_t arena_len, uint32_t mode,
+                                                const uint32_t* d_key_class, const cg_tx_check* d_checks,
+                                                uint64_t n_tx, const uint32_t* d_reqs, uint32_t n_reqs,
+                                                const cg_req_node* d_nodes, uint32_t n_nodes, uint8_t* d_status,
+                                                cg_tx_verdict* d_verdicts, uint8_t* d_req_status, void* hip_stream) {
+  const char* fn = "cg_verify_required_signatures_packed_device";
+  int a = txsig_args(fn, c, n_keys, d_keys, n_ids, d_ids, n_sigs, d_sigs, d_status, n_tmpls, tmpls, mode);
+  if (a == CG_OK)
+    a = txv_args(fn, (uint32_t)sizeof(cg_txsig_packed), n_sigs, d_sigs, d_status, n_keys, d_keys, n_tx, d_checks,
+                 n_reqs, d_reqs, n_nodes, d_nodes, d_verdicts, d_req_status);
+  if (a != CG_OK) return a;
+  if (sig_bytes_off > arena_len || sig_bytes_len > arena_len - sig_bytes_off)
+    return fail(CG_ERR_ARG, "%s: the signature stream lies outside the arena", fn);
+  if (n_sigs == 0 && n_tx == 0 && n_reqs == 0) return CG_OK;
+  std::lock_guard<std::mutex> g(c->mu);
+  if (c->fault) return fail(CG_ERR_DEVICE, "%s: device fault (injected)", fn);
+  HIP_TRY(hipSetDevice(c->device), "hipSetDevice");
+  HIP_TRY(ensure_txv_ws(c, n_tx), "hipMalloc(verdict workspace)");
+  hipStream_t s = nullptr;
+  if (n_sigs) {
+    const int rc = txsig_packed_device_locked(c, d_keys, n_keys, d_ids, n_ids, d_sigs, n_sigs, sig_bytes_off,
+                                              sig_bytes_len, tmpls, n_tmpls, d_arena, arena_len, mode, d_status,
+                                              hip_stream, &s);
+    if (rc != CG_OK) return rc;
+  } else {
+    s = stream_of(c, hip_stream);
+    HIP_TRY(order_in(c, s), "hipStreamWaitEvent");
+  }
+  // launch_txsig has joined the side streams and run the mode guard on s: the statuses are final there
+  HIP_TRY(cg::launch_tx_verdicts(d_sigs, (uint32_t)sizeof(cg_txsig_packed), n_sigs, d_status, d_keys, n_keys,
+                                 d_key_class, d_checks, (uint32_t)n_tx, d_reqs, n_reqs, d_nodes, n_nodes, d_verdicts,
+                                 d_req_status, c->txvws.p, s),
+          "launch_tx_verdicts");
+  HIP_TRY(order_out(c, s), "hipEventRecord");
+  return CG_OK;
+}
+
+int cg_verify_required_signatures_packed(cg_ctx* c, const cg_key* keys, uint32_t n_keys, const uint8_t* ids,
+                                         uint64_t n_ids, const cg_txsig_packed* sigs, uint64_t n_sigs,
+                                         const uint8_t* sig_bytes, uint64_t sig_bytes_len,
+                                         const cg_signable_tmpl* tmpls, uint32_t n_tmpls, const uint8_t* arena,
+                                         uint64_t arena_len, uint32_t mode, const uint32_t* key_class,
+                                         const cg_tx_check* checks, uint64_t n_tx, const uint32_t* reqs,
+                                         uint32_t n_reqs, const cg_req_node* nodes, uint32_t n_nodes,
+                                         uint8_t* status_out, cg_tx_verdict* verdicts_out, uint8_t* req_status_out,
+                                         cg_stats* stats) {
+  const char* fn = "cg_verify_required_signatures_packed";
+  // status_out may be NULL: txsig_args only needs it to be there when there are signatures
+  int a = txsig_args(fn, c, n_keys, keys, n_ids, ids, n_sigs, sigs, status_out ? (const void*)status_out : (const void*)sigs,
+                     n_tmpls, tmpls, mode);
+  if (a == CG_OK)
+    a = txv_args(fn, (uint32_t)sizeof(cg_txsig_packed), n_sigs, sigs, sigs, n_keys, keys, n_tx, checks, n_reqs, reqs,
+                 n_nodes, nodes, verdicts_out, req_status_out);
+  if (a == CG_OK) a = txv_reserved(fn, checks, n_tx);
+  if (a != CG_OK) return a;
+  if (arena_len && !arena) return fail(CG_ERR_ARG, "%s: arena is NULL", fn);
+  if (sig_bytes_len && !sig_bytes) return fail(CG_ERR_ARG, "%s: sig_bytes is NULL", fn);
+  if (n_sigs && status_out) memset(status_out, CG_NOT_RUN, n_sigs);
+  if (n_sigs == 0 && n_tx == 0 && n_reqs == 0) return CG_OK;
+  TxvHost h;
+  h.key_class = key_class;
+  h.checks = checks;
+  h.n_tx = n_tx;
+  h.reqs = reqs;
+  h.n_reqs = n_reqs;
+  h.nodes = nodes;
+  h.n_nodes = n_nodes;
+  h.verdicts_out = verdicts_out;
+  h.req_status_out = req_status_out;
+  std::lock_guard<std::mutex> g(c->mu);
+  // without signatures the verify path has nothing to enqueue: the reduction alone
+  const int rc = n_sigs ? verify_txsig_host_locked(c, keys, n_keys, ids, n_ids, nullptr, n_sigs, tmpls, n_tmpls, arena,
+                                                   arena_len, mode, status_out, stats, sigs, sig_bytes, sig_bytes_len,
+                                                   &h)
+                        : tx_verdicts_host_locked(c, sigs, (uint32_t)sizeof(cg_txsig_packed), 0, nullptr, keys, n_keys, h);
+  if (rc != CG_OK) {
+    if (n_sigs && status_out) memset(status_out, CG_NOT_RUN, n_sigs);
+    txv_fill_not_run(h);
+  }
   return rc;
 }
 
@@ -2139,6 +2432,68 @@ int cg_pool_verify_tx_signatures_packed(cg_pool* p, const cg_key* keys, uint32_t
                                                      arena, arena_len, mode, status_out + first, nullptr, sigs + first,
                                                      sig_bytes + o, sig_bytes_len - o);
                    });
+}
+
+int cg_pool_verify_required_signatures_packed(cg_pool* p, const cg_key* keys, uint32_t n_keys, const uint8_t* ids,
+                                              uint64_t n_ids, const cg_txsig_packed* sigs, uint64_t n_sigs,
+                                              const uint8_t* sig_bytes, uint64_t sig_bytes_len,
+                                              const cg_signable_tmpl* tmpls, uint32_t n_tmpls, const uint8_t* arena,
+                                              uint64_t arena_len, uint32_t mode, const uint32_t* key_class,
+                                              const cg_tx_check* checks, uint64_t n_tx, const uint32_t* reqs,
+                                              uint32_t n_reqs, const cg_req_node* nodes, uint32_t n_nodes,
+                                              uint8_t* status_out, cg_tx_verdict* verdicts_out,
+                                              uint8_t* req_status_out, cg_pool_stats* stats) {
+  const char* fn = "cg_pool_verify_required_signatures_packed";
+  if (!p) return fail(CG_ERR_ARG, "%s: pool is NULL", fn);
+  if (p->ctx.empty()) return fail(CG_ERR_ARG, "%s: empty pool", fn);
+  int a = txv_args(fn, (uint32_t)sizeof(cg_txsig_packed), n_sigs, sigs, sigs, n_keys, keys, n_tx, checks, n_reqs, reqs,
+                   n_nodes, nodes, verdicts_out, req_status_out);
+  if (a == CG_OK) a = txv_reserved(fn, checks, n_tx);
+  if (a != CG_OK) return a;
+  std::vector<uint8_t> own;
+  if (!status_out && n_sigs) {
+    own.assign(n_sigs, CG_NOT_RUN);
+    status_out = own.data();
+  }
+  TxvHost h;
+  h.key_class = key_class;
+  h.checks = checks;
+  h.n_tx = n_tx;
+  h.reqs = reqs;
+  h.n_reqs = n_reqs;
+  h.nodes = nodes;
+  h.n_nodes = n_nodes;
+  h.verdicts_out = verdicts_out;
+  h.req_status_out = req_status_out;
+  // the existing pool call: shards, re-run on a fault; what no slot ran stays CG_NOT_RUN
+  const int rc = cg_pool_verify_tx_signatures_packed(p, keys, n_keys, ids, n_ids, sigs, n_sigs, sig_bytes, sig_bytes_len,
+                                                     tmpls, n_tmpls, arena, arena_len, mode, status_out, stats);
+  if (rc != CG_OK && rc != CG_ERR_DEVICE) {
+    txv_fill_not_run(h);
+    return rc;
+  }
+  if (n_tx == 0 && n_reqs == 0) return rc;
+  const std::string first_err = rc != CG_OK ? g_err : std::string();
+  // the reduction over the gathered statuses, on the first slot that runs it
+  int vr = CG_ERR_DEVICE;
+  {
+    std::lock_guard<std::mutex> g(p->mu);
+    for (size_t k = 0; k < p->ctx.size() && vr != CG_OK; ++k) {
+      if (!p->healthy[k]) continue;
+      cg_ctx* c = p->ctx[k];
+      std::lock_guard<std::mutex> gc(c->mu);
+      vr = tx_verdicts_host_locked(c, sigs, (uint32_t)sizeof(cg_txsig_packed), n_sigs, status_out, keys, n_keys, h);
+      if (vr == CG_ERR_DEVICE) p->healthy[k] = 0;
+      else if (vr != CG_OK) break;
+    }
+  }
+  if (vr != CG_OK) {
+    if (vr == CG_ERR_DEVICE && g_err.empty()) g_err = std::string(fn) + ": no healthy slot could run the reduction";
+    txv_fill_not_run(h);
+    return vr;
+  }
+  if (rc != CG_OK) g_err = first_err;
+  return rc;
 }
 
 int cg_pool_verify_batch(cg_pool* p, const cg_key* keys, uint32_t n_keys, const cg_item* items, uint64_t n_items,

@@ -338,4 +338,15 @@ hipError_t launch_filtered(const cg_filtered_tx* d_ftxs, uint64_t n_ftx, const c
                            const cg_filtered_leaf* d_leaves, uint64_t n_leaves, const uint8_t* d_arena,
                            uint64_t arena_len, uint8_t* d_status, uint8_t* d_ws, hipStream_t stream);
 
+
+// Per-transaction verdicts (txverdict.hip): req_status preset to CG_REQ_HOST, then the lane-per-transaction
+// kernel and the wave-per-transaction kernel over the list it leaves in d_ws (tx_verdicts_ws_bytes(n_tx)
+// bytes). sig_stride: sizeof(cg_txsig_packed) or sizeof(cg_txsig).
+size_t tx_verdicts_ws_bytes(uint64_t n_tx);
+hipError_t launch_tx_verdicts(const void* d_sig_table, uint32_t sig_stride, uint64_t n_sigs, const uint8_t* d_status,
+                              const cg_key* d_keys, uint32_t n_keys, const uint32_t* d_key_class,
+                              const cg_tx_check* d_checks, uint32_t n_tx, const uint32_t* d_reqs, uint32_t n_reqs,
+                              const cg_req_node* d_nodes, uint32_t n_nodes, cg_tx_verdict* d_verdicts,
+                              uint8_t* d_req_status, void* d_ws, hipStream_t stream);
+
 }  // namespace cg

@@ -11,6 +11,7 @@ import numpy as np
 
 from . import _lib
 from .batch import COMPONENT_DTYPE, FLEAF_DTYPE, FTX_DTYPE, KEY_DTYPE, PMT_NODE_DTYPE, MODE_DOVERIFY, SPAN_DTYPE, TMPL_DTYPE, TX_DTYPE, TXSIG_DTYPE
+from .batch import REQ_NODE_DTYPE, TX_CHECK_DTYPE, TX_VERDICT_DTYPE, TXSIG12_DTYPE
 
 
 def _p(a):
@@ -252,6 +253,70 @@ class Engine:
                                                        stream or None)
         _lib.check(rc, "cg_verify_tx_signatures_device")
 
+    # ------------------------------------------------------------------ per-transaction verdicts
+    def tx_verdicts(self, sig_table, status, keys, checks, reqs, nodes, key_class=None):
+        """cg_tx_verdicts: verifySignaturesExcept's two steps reduced on the device from one status byte
+        per record of ``sig_table`` (TXSIG12_DTYPE or TXSIG_DTYPE). Returns (verdicts TX_VERDICT_DTYPE
+        [n_tx], req_status uint8 [n_reqs])."""
+        return _tx_verdicts(self._h, sig_table, status, keys, checks, reqs, nodes, key_class)
+
+    def tx_verdicts_device(self, d_sig_table, sig_stride, n_sigs, d_status, d_keys, n_keys, d_key_class, d_checks,
+                           n_tx, d_reqs, n_reqs, d_nodes, n_nodes, d_verdicts, d_req_status, stream=0):
+        """Asynchronous device form of tx_verdicts (raw HBM pointers; d_key_class may be 0)."""
+        rc = _lib.lib().cg_tx_verdicts_device(self._h, d_sig_table, sig_stride, n_sigs, d_status, d_keys, n_keys,
+                                              d_key_class or None, d_checks, n_tx, d_reqs or None, n_reqs,
+                                              d_nodes or None, n_nodes, d_verdicts, d_req_status or None,
+                                              stream or None)
+        _lib.check(rc, "cg_tx_verdicts_device")
+
+    def verify_required_signatures_packed(self, pb, checks, reqs, nodes, key_class=None, mode=MODE_DOVERIFY,
+                                          want_status=False):
+        """cg_verify_required_signatures_packed: ``pb`` a batch.PackedTxSigBatch, verified as
+        verify_tx_signatures_packed does, and reduced per transaction behind the last verify chunk.
+        Returns (verdicts, req_status), and the per-signature statuses too with want_status."""
+        _check_tables(checks, reqs, nodes, key_class, len(pb.keys))
+        vd = np.zeros(len(checks), dtype=TX_VERDICT_DTYPE)
+        rs = np.full(len(reqs), 255, dtype=np.uint8)
+        st = np.full(pb.n, 255, dtype=np.uint8) if want_status else None
+        stats = _lib.cg_stats()
+        rc = _lib.lib().cg_verify_required_signatures_packed(
+            self._h, _p(pb.keys), len(pb.keys), _p(pb.ids), pb.n_ids, _p(pb.sigs), pb.n, _p(pb.stream), pb.stream.size,
+            _p(pb.tmpls), len(pb.tmpls), _p(pb.arena), pb.arena.size, mode, _p(key_class), _p(checks), len(checks),
+            _p(reqs), len(reqs), _p(nodes), len(nodes), _p(st), _p(vd), _p(rs), ctypes.byref(stats))
+        _lib.check(rc, "cg_verify_required_signatures_packed")
+        self.last_stats = {k: getattr(stats, k) for k, _ in _lib.cg_stats._fields_}
+        return (vd, rs, st) if want_status else (vd, rs)
+
+    def verify_required_signatures_packed_device(self, d_keys, n_keys, d_ids, n_ids, d_sigs, n_sigs, sig_bytes_off,
+                                                 sig_bytes_len, tmpls, d_arena, arena_len, d_key_class, d_checks, n_tx,
+                                                 d_reqs, n_reqs, d_nodes, n_nodes, d_status, d_verdicts, d_req_status,
+                                                 mode=MODE_DOVERIFY, stream=0):
+        """Asynchronous device form: verify_tx_signatures_packed_device, then the verdict kernels."""
+        assert tmpls.dtype == TMPL_DTYPE
+        rc = _lib.lib().cg_verify_required_signatures_packed_device(
+            self._h, d_keys, n_keys, d_ids, n_ids, d_sigs, n_sigs, sig_bytes_off, sig_bytes_len, _p(tmpls), len(tmpls),
+            d_arena, arena_len, mode, d_key_class or None, d_checks, n_tx, d_reqs or None, n_reqs, d_nodes or None,
+            n_nodes, d_status, d_verdicts, d_req_status or None, stream or None)
+        _lib.check(rc, "cg_verify_required_signatures_packed_device")
+
+
+def _check_tables(checks, reqs, nodes, key_class, n_keys):
+    assert checks.dtype == TX_CHECK_DTYPE and nodes.dtype == REQ_NODE_DTYPE and reqs.dtype == np.uint32
+    assert key_class is None or (key_class.dtype == np.uint32 and len(key_class) == n_keys)
+
+
+def _tx_verdicts(h, sig_table, status, keys, checks, reqs, nodes, key_class):
+    assert sig_table.dtype in (TXSIG12_DTYPE, TXSIG_DTYPE) and keys.dtype == KEY_DTYPE
+    assert status.dtype == np.uint8 and len(status) == len(sig_table)
+    _check_tables(checks, reqs, nodes, key_class, len(keys))
+    vd = np.zeros(len(checks), dtype=TX_VERDICT_DTYPE)
+    rs = np.full(len(reqs), 255, dtype=np.uint8)
+    rc = _lib.lib().cg_tx_verdicts(h, _p(sig_table), sig_table.dtype.itemsize, len(sig_table), _p(status), _p(keys),
+                                   len(keys), _p(key_class), _p(checks), len(checks), _p(reqs), len(reqs), _p(nodes),
+                                   len(nodes), _p(vd), _p(rs))
+    _lib.check(rc, "cg_tx_verdicts")
+    return vd, rs
+
 
 class EnginePool:
     """One process, several devices (cg_pool): ``verify(batch)`` shards the items over the healthy
@@ -327,6 +392,24 @@ class EnginePool:
         if rc != 0 and not allow_partial:
             _lib.check(rc, "cg_pool_verify_tx_signatures_packed")
         return st
+
+    def verify_required_signatures_packed(self, pb, checks, reqs, nodes, key_class=None, mode=MODE_DOVERIFY,
+                                          want_status=False, allow_partial=False):
+        """cg_pool_verify_required_signatures_packed: the sharded verify, then the reduction on one healthy
+        slot; signatures no slot ran surface as NOT_RUN verdicts."""
+        _check_tables(checks, reqs, nodes, key_class, len(pb.keys))
+        vd = np.zeros(len(checks), dtype=TX_VERDICT_DTYPE)
+        rs = np.full(len(reqs), 255, dtype=np.uint8)
+        st = np.full(pb.n, 255, dtype=np.uint8) if want_status else None
+        stats = _lib.cg_pool_stats()
+        rc = _lib.lib().cg_pool_verify_required_signatures_packed(
+            self._h, _p(pb.keys), len(pb.keys), _p(pb.ids), pb.n_ids, _p(pb.sigs), pb.n, _p(pb.stream), pb.stream.size,
+            _p(pb.tmpls), len(pb.tmpls), _p(pb.arena), pb.arena.size, mode, _p(key_class), _p(checks), len(checks),
+            _p(reqs), len(reqs), _p(nodes), len(nodes), _p(st), _p(vd), _p(rs), ctypes.byref(stats))
+        self.last_stats = {k: getattr(stats, k) for k, _ in _lib.cg_pool_stats._fields_ if k != "reserved"}
+        if rc != 0 and not allow_partial:
+            _lib.check(rc, "cg_pool_verify_required_signatures_packed")
+        return (vd, rs, st) if want_status else (vd, rs)
 
     def verify_transactions(self, txs, comps, keys, sigs, tmpls, arena, mode=MODE_DOVERIFY, allow_partial=False):
         """cg_pool_verify_transactions: the whole call on one healthy slot, the next one on a device

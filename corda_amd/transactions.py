@@ -320,3 +320,115 @@ def verify_chain(stxs, crypto=Crypto, check_sufficient_signatures=True, on_verif
         if on_verified is not None:
             on_verified(t, ids[t])
     return order
+
+
+# ---------------------------------------------------------------------------------------------
+# verifySignaturesExcept for a batch, reduced on the device (cg_verify_required_signatures_packed):
+# the engine hands back one verdict per TRANSACTION -- the first signature that does not verify and
+# the required keys the signers do not fulfil -- instead of one status byte per signature for the
+# host to walk.
+
+def pack_required_signatures(stxs, ids, allowed_to_be_missing=(), rsa=False):
+    """The tables of cg_verify_required_signatures_packed for ``stxs`` (transaction t = stxs[t], its id
+    ids[t]): returns (pb, checks, reqs, nodes, key_class, req_keys, req_errors). req_keys[t] lists the
+    required keys of transaction t in ``reqs`` order (minus ``allowed_to_be_missing``); req_errors[t]
+    is the exception CompositeKey.checkValidity raised for one of them (its requirements are then left
+    out: the host throws it, TransactionWithSignatures.kt:72-78 via CompositeKey.kt:186)."""
+    from .composite import CompositeKey, encoded_of
+    allowed = set(allowed_to_be_missing)
+    bld = B.TxSigBuilder()
+    bld._ids = [bytes(i) for i in ids]  # one id per transaction, equal ids not merged: tx_idx == t
+    rb = B.RequirementBuilder()
+    table_keys, tmpl_of = [], {}
+    checks = np.zeros(len(stxs), dtype=B.TX_CHECK_DTYPE)
+    req_keys, req_errors, pos = [], {}, 0
+    for t, stx in enumerate(stxs):
+        for s in stx.sigs:
+            by = s.by
+            on_gpu = not isinstance(by, CompositeKey) and _on_gpu(by, rsa)
+            k = bld.key(by.scheme, by.fmt, by.encoded if not isinstance(by, CompositeKey) else encoded_of(by))
+            if k == len(table_keys):
+                table_keys.append(by)
+            # a scheme the GPU does not run gets CG_UNSUPPORTED whatever its bytes: a 1-byte placeholder
+            sb = B.sig_field(by.scheme, s.bytes) if on_gpu else b"\x00"
+            mk = (s.platform_version, s.scheme_number_id)
+            if mk not in tmpl_of:
+                tmpl_of[mk] = bld.template(*signable.template(*mk))
+            bld.add_signature(k, t, tmpl_of[mk], sb)
+        needed = [k for k in stx.required_signing_keys if k not in allowed]
+        for k in needed:
+            if isinstance(k, CompositeKey) and not k._validated:
+                try:
+                    k.check_validity()
+                except Exception as e:  # noqa: BLE001 - mirrored JVM exception
+                    req_errors[t] = e
+                    break
+        if t in req_errors:
+            needed = []
+        first, n = rb.add_transaction(needed)
+        req_keys.append(needed)
+        checks[t] = (pos, len(stx.sigs), first, n, 0)
+        pos += len(stx.sigs)
+    tb = bld.build()
+    reqs, nodes = rb.build()
+    return tb.packed(), checks, reqs, nodes, rb.key_classes(table_keys), req_keys, req_errors
+
+
+def verify_signatures_except_batch(stxs, signable_or_ids=None, allowed_to_be_missing=(), crypto=Crypto):
+    """TransactionWithSignatures.verifySignaturesExcept (TransactionWithSignatures.kt:41-47) for every
+    transaction of ``stxs`` in one engine call: per transaction None, or the exception the serial
+    ``verify_signatures_except`` raises -- the first failing signature's (through raise_for_status), else
+    a SignaturesMissingException rebuilt from the requirement status bytes.
+
+    ``signable_or_ids``: the transactions' ids (default: ``stx.id``), or the ``signable_data(tx_id, sig)``
+    callable of the serial functions. The device always signs over SignableData(id, metadata) spliced
+    from corda_amd/signable.py's templates; the callable serves the host path, which is taken only
+    for the transactions the device hands back: a requirement it did not evaluate (CG_TXV_REQ_HOST, no
+    failing signature before it), a first failing status of UNSUPPORTED (a scheme or key the GPU does
+    not run: the host verifies that signature and goes on) or NOT_RUN, and a bad span."""
+    if callable(signable_or_ids) or signable_or_ids is None:
+        ids = [stx.id for stx in stxs]
+    else:
+        ids = list(signable_or_ids)
+    signable_data = signable_or_ids if callable(signable_or_ids) else (
+        lambda tx_id, s: signable.serialize(bytes(tx_id), s.platform_version, s.scheme_number_id))
+    if not stxs:
+        return []
+    eng = crypto.engine()
+    pb, checks, reqs, nodes, key_class, req_keys, req_errors = pack_required_signatures(
+        stxs, ids, allowed_to_be_missing, bool(getattr(eng, "rsa", False)))
+    verdicts, req_status = eng.verify_required_signatures_packed(pb, checks, reqs, nodes, key_class, B.MODE_DOVERIFY)
+    out = []
+    for t, stx in enumerate(stxs):
+        v = verdicts[t]
+        flags, st, fb = int(v["flags"]), int(v["status"]), int(v["first_bad"])
+        has_bad = fb != B.NO_BAD
+        if (flags & B.TXV_SPAN_BAD) or (has_bad and st in (B.UNSUPPORTED, B.NOT_RUN)) or \
+                (not has_bad and (flags & B.TXV_REQ_HOST)):
+            res = None
+            try:
+                one = stx if ids[t] == stx.id else SignedTransaction(ids[t], stx.sigs, stx.required_signing_keys,
+                                                                     getattr(stx, "commands", []),
+                                                                     getattr(stx, "notary", None))
+                verify_signatures_except(one, signable_data, allowed_to_be_missing, crypto)
+            except Exception as e:  # noqa: BLE001 - mirrored JVM exception
+                res = e
+            out.append(res)
+        elif has_bad:
+            s = stx.sigs[fb]
+            try:
+                crypto.raise_for_status(st, SCHEME_CODE_NAMES.get(s.by.scheme, ""), do_verify=True, key=s.by)
+                out.append(RuntimeError(f"status {st} of a failing signature raised nothing"))
+            except Exception as e:  # noqa: BLE001 - mirrored JVM exception
+                out.append(e)
+        elif t in req_errors:
+            out.append(req_errors[t])
+        elif int(v["n_missing"]):
+            first = int(checks[t]["first_req"])
+            found = {k for r, k in enumerate(req_keys[t]) if req_status[first + r] == B.REQ_MISSING}
+            # built as the serial path builds it, so that the set (and the message) lists the keys in its order
+            missing = {k for k in stx.required_signing_keys if k in found} - set(allowed_to_be_missing)
+            out.append(SignaturesMissingException(missing, get_key_descriptions(stx, missing), ids[t]))
+        else:
+            out.append(None)
+    return out

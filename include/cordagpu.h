@@ -459,6 +459,119 @@ int cg_verify_tx_signatures_packed_device(cg_ctx* ctx, const cg_key* d_keys, uin
                                           const cg_signable_tmpl* tmpls, uint32_t n_tmpls, const uint8_t* d_arena,
                                           uint64_t arena_len, uint32_t mode, uint8_t* d_status, void* hip_stream);
 
+/* ---- Per-transaction verdicts: TransactionWithSignatures.verifySignaturesExcept as one call
+ *   (core/.../transactions/TransactionWithSignatures.kt:41-47, 58-62, 72-78):
+ *   1. the first signature, in list order, that does not verify (its exception is what escapes);
+ *   2. otherwise the required keys the signers do not fulfil; isFulfilledBy is composite-aware
+ *      (CompositeKey.kt:186-209, CryptoUtils.kt:88-92).
+ * The per-signature status bytes are reduced on the device, right behind the kernels that wrote them.
+ *
+ * Fulfilment is computed from the keys of ALL signatures of the span, whatever their statuses
+ * (sigs.map { it.by }.toSet()). A composite node is fulfilled when the wrapping int32 sum of its
+ * fulfilled children's weights is >= its threshold (a signed compare, List<Int>.sum()). With a signer
+ * whose key entry has scheme CG_COMPOSITE_KEY every composite requirement is unfulfilled
+ * (CompositeKey.kt:186-189); leaf requirements still compare classes. The first non-VALID status
+ * includes CG_UNSUPPORTED and CG_NOT_RUN: the caller resolves those on the host for that transaction,
+ * or re-queues it. Keys allowed to be missing are left out of `reqs` by the caller; CompositeKey
+ * constraint and cycle validation (checkValidity) stays on the host, where it throws.
+ *
+ * Key classes: the key table's identity is (scheme, fmt, bytes), PublicKey.equals is not (the raw and
+ * the SPKI form of one key are equal), so key_class[k] (uint32_t[n_keys]; NULL: the identity) gives key
+ * entry k its equality class, assigned by the packer from its own equals. A leaf requirement names a
+ * class; a required key that never signed is a class no signer has and needs no key-table entry.
+ *
+ * The device treats every table as untrusted data: each index is bounds-checked before the load
+ * that uses it. A composite node's children must lie at indices greater than its own (else
+ * CG_REQ_BAD); the walk is an explicit stack of at most CG_REQ_MAX_DEPTH composite nodes (a composite
+ * nested deeper: CG_REQ_HOST), and one requirement visits at most CG_REQ_MAX_VISITS nodes (counting
+ * a shared subtree once per path that reaches it; then CG_REQ_HOST). These two bounds make every loop
+ * of the kernels finite for any input. */
+#define CG_REQ_MAX_DEPTH 8
+#define CG_REQ_MAX_VISITS 4096
+
+typedef struct cg_tx_check {   /* one per transaction t (t indexes ids / cg_tx) */
+  uint64_t first_sig;          /* its signatures are records [first_sig, first_sig + n_sigs) of the signature table, */
+  uint32_t n_sigs;             /* in sigs-list order; each must carry tx_idx == t */
+  uint32_t first_req;          /* its required keys are reqs[first_req .. first_req + n_req) */
+  uint32_t n_req;
+  uint32_t reserved;           /* must be 0 */
+} cg_tx_check;                 /* 24 bytes */
+
+typedef struct cg_req_node {   /* a required key: leaf or CompositeKey node */
+  uint32_t a;                  /* leaf: key class; composite: index of its first child node */
+  uint32_t n_children;         /* 0 = leaf; else children are nodes[a .. a + n_children) */
+  int32_t  weight;             /* weight inside the parent (ignored for a root) */
+  int32_t  threshold;          /* composite only */
+} cg_req_node;                 /* 16 bytes */
+
+typedef struct cg_tx_verdict {
+  uint32_t first_bad;          /* ordinal inside the span of the first signature whose status != CG_VALID; 0xFFFFFFFF: none */
+  uint8_t  status;             /* that signature's status (CG_VALID when none) */
+  uint8_t  flags;              /* CG_TXV_* */
+  uint16_t n_missing;          /* required keys not fulfilled, saturating */
+} cg_tx_verdict;               /* 8 bytes */
+
+/* req_status: one byte per `reqs` entry (an array of root node indices; node tables are shared between
+ * transactions, requirement ranges are not: two transactions must not claim the same reqs entry).
+ * Entries no transaction claims are CG_REQ_HOST. */
+enum {
+  CG_REQ_FULFILLED = 0,
+  CG_REQ_MISSING = 1,
+  CG_REQ_HOST = 2,   /* not evaluated, the caller walks it itself (deeper than CG_REQ_MAX_DEPTH, over the
+                        visit budget, or its transaction's span is bad) */
+  CG_REQ_BAD = 255   /* malformed table: a root or child range outside the node table, or children at
+                        indices not greater than their parent's */
+};
+/* cg_tx_verdict.flags */
+#define CG_TXV_SPAN_BAD 1u         /* the span leaves the signature table, a record in it has another tx_idx, or (device
+                                      tables) cg_tx_check.reserved != 0: status = CG_NOT_RUN, first_bad = 0xFFFFFFFF,
+                                      requirements not evaluated (CG_REQ_HOST) */
+#define CG_TXV_REQ_HOST 2u         /* some requirement came back CG_REQ_HOST or CG_REQ_BAD, or the requirement range
+                                      leaves `reqs` (then no req_status byte is written for it) */
+#define CG_TXV_COMPOSITE_SIGNER 4u /* a signer's key entry has scheme CG_COMPOSITE_KEY */
+
+/* The reduction alone, over any status array the engine produced (d_status[i] belongs to record i of the
+ * signature table: the 12-byte cg_txsig_packed or the 24-byte cg_txsig, sig_stride says which; it
+ * serves cg_verify_tx_signatures(_device) and cg_verify_transactions too). A signature whose key_idx
+ * is outside the key table signs for no class. n_tx < 2^32. Device buffers in HBM, asynchronous on
+ * hip_stream (bridged like every device call). Two kernels: one lane per transaction of up to 32
+ * signatures, one wave per longer one. Errors: CG_ERR_ARG for a stride other than 12 / 24 or a NULL
+ * table with a non-zero count (key_class may be NULL). */
+int cg_tx_verdicts_device(cg_ctx* ctx, const void* d_sig_table, uint32_t sig_stride, uint64_t n_sigs,
+                          const uint8_t* d_status, const cg_key* d_keys, uint32_t n_keys, const uint32_t* d_key_class,
+                          const cg_tx_check* d_checks, uint64_t n_tx, const uint32_t* d_reqs, uint32_t n_reqs,
+                          const cg_req_node* d_nodes, uint32_t n_nodes, cg_tx_verdict* d_verdicts,
+                          uint8_t* d_req_status, void* hip_stream);
+/* The same over host buffers (copies through the ctx); also CG_ERR_ARG for a non-zero
+ * cg_tx_check.reserved. */
+int cg_tx_verdicts(cg_ctx* ctx, const void* sig_table, uint32_t sig_stride, uint64_t n_sigs, const uint8_t* status,
+                   const cg_key* keys, uint32_t n_keys, const uint32_t* key_class, const cg_tx_check* checks,
+                   uint64_t n_tx, const uint32_t* reqs, uint32_t n_reqs, const cg_req_node* nodes, uint32_t n_nodes,
+                   cg_tx_verdict* verdicts_out, uint8_t* req_status_out);
+
+/* cg_verify_tx_signatures_packed(_device) followed by the verdict kernels on the same stream, after the
+ * last verify chunk, with no host round trip: SignedTransaction.verifyRequiredSignatures for a batch.
+ * Host form: status_out may be NULL, then the per-signature statuses are not copied back; the verdicts
+ * and req_status always are. On an error every verdict is {0xFFFFFFFF, CG_NOT_RUN, CG_TXV_SPAN_BAD, 0}. */
+int cg_verify_required_signatures_packed(cg_ctx* ctx, const cg_key* keys, uint32_t n_keys, const uint8_t* ids,
+                                         uint64_t n_ids, const cg_txsig_packed* sigs, uint64_t n_sigs,
+                                         const uint8_t* sig_bytes, uint64_t sig_bytes_len,
+                                         const cg_signable_tmpl* tmpls, uint32_t n_tmpls, const uint8_t* arena,
+                                         uint64_t arena_len, uint32_t mode, const uint32_t* key_class,
+                                         const cg_tx_check* checks, uint64_t n_tx, const uint32_t* reqs,
+                                         uint32_t n_reqs, const cg_req_node* nodes, uint32_t n_nodes,
+                                         uint8_t* status_out, cg_tx_verdict* verdicts_out, uint8_t* req_status_out,
+                                         cg_stats* stats_opt);
+int cg_verify_required_signatures_packed_device(cg_ctx* ctx, const cg_key* d_keys, uint32_t n_keys,
+                                                const uint8_t* d_ids, uint64_t n_ids, const cg_txsig_packed* d_sigs,
+                                                uint64_t n_sigs, uint64_t sig_bytes_off, uint64_t sig_bytes_len,
+                                                const cg_signable_tmpl* tmpls, uint32_t n_tmpls,
+                                                const uint8_t* d_arena, uint64_t arena_len, uint32_t mode,
+                                                const uint32_t* d_key_class, const cg_tx_check* d_checks,
+                                                uint64_t n_tx, const uint32_t* d_reqs, uint32_t n_reqs,
+                                                const cg_req_node* d_nodes, uint32_t n_nodes, uint8_t* d_status,
+                                                cg_tx_verdict* d_verdicts, uint8_t* d_req_status, void* hip_stream);
+
 /* ---- Tear-offs: FilteredTransaction.verify / PartialMerkleTree.verify.
  * Replaces, for a batch of filtered transactions (the non-validating notary's input,
  * NonValidatingNotaryFlow.kt:22-27), the serial
@@ -560,6 +673,19 @@ int cg_pool_verify_tx_signatures_packed(cg_pool* pool, const cg_key* keys, uint3
                                         const cg_signable_tmpl* tmpls, uint32_t n_tmpls, const uint8_t* arena,
                                         uint64_t arena_len, uint32_t mode, uint8_t* status_out,
                                         cg_pool_stats* stats_opt);
+/* cg_verify_required_signatures_packed on a pool: cg_pool_verify_tx_signatures_packed (shards, re-run
+ * on a fault), then cg_tx_verdicts on a healthy slot over the gathered statuses. Signatures no slot
+ * could run stay CG_NOT_RUN and surface as status = CG_NOT_RUN verdicts (the call then returns
+ * CG_ERR_DEVICE like the pool call, with the verdicts written). status_out may be NULL. */
+int cg_pool_verify_required_signatures_packed(cg_pool* pool, const cg_key* keys, uint32_t n_keys, const uint8_t* ids,
+                                              uint64_t n_ids, const cg_txsig_packed* sigs, uint64_t n_sigs,
+                                              const uint8_t* sig_bytes, uint64_t sig_bytes_len,
+                                              const cg_signable_tmpl* tmpls, uint32_t n_tmpls, const uint8_t* arena,
+                                              uint64_t arena_len, uint32_t mode, const uint32_t* key_class,
+                                              const cg_tx_check* checks, uint64_t n_tx, const uint32_t* reqs,
+                                              uint32_t n_reqs, const cg_req_node* nodes, uint32_t n_nodes,
+                                              uint8_t* status_out, cg_tx_verdict* verdicts_out,
+                                              uint8_t* req_status_out, cg_pool_stats* stats_opt);
 /* Failure drill: make every later call on `slot` fail as a device fault would (fail = 1), or
  * clear it and mark the slot healthy again (fail = 0). For tests and operational drills. */
 int cg_pool_inject_fault(cg_pool* pool, uint32_t slot, int fail);

@@ -109,6 +109,31 @@ JNIEXPORT jint JNICALL Java_net_corda_core_crypto_CryptoBatch_nativeVerifyTxSign
                                         (uint8_t*)ADDR(status), (cg_stats*)ADDR(stats));
 }
 
+/* SignedTransaction.verifyRequiredSignatures over many transactions: the packed tx-signature call followed
+ * by the per-transaction verdict kernels (cg_verify_required_signatures_packed; pool != 0:
+ * cg_pool_verify_required_signatures_packed). key_class and status may be null buffers (ADDR gives 0). */
+JNIEXPORT jint JNICALL Java_net_corda_core_crypto_CryptoBatch_nativeVerifyRequiredPacked(
+    JNIEnv* env, jobject self, jlong ctx, jlong pool, jobject keys, jint n_keys, jobject ids, jlong n_ids,
+    jobject sigs, jlong n_sigs, jobject sig_bytes, jlong sig_bytes_len, jobject tmpls, jint n_tmpls, jobject arena,
+    jlong arena_len, jint mode, jobject key_class, jobject checks, jlong n_tx, jobject reqs, jint n_reqs,
+    jobject nodes, jint n_nodes, jobject status, jobject verdicts, jobject req_status) {
+  if (pool)
+    return cg_pool_verify_required_signatures_packed(
+        (cg_pool*)(intptr_t)pool, (const cg_key*)ADDR(keys), (uint32_t)n_keys, (const uint8_t*)ADDR(ids),
+        (uint64_t)n_ids, (const cg_txsig_packed*)ADDR(sigs), (uint64_t)n_sigs, (const uint8_t*)ADDR(sig_bytes),
+        (uint64_t)sig_bytes_len, (const cg_signable_tmpl*)ADDR(tmpls), (uint32_t)n_tmpls, (const uint8_t*)ADDR(arena),
+        (uint64_t)arena_len, (uint32_t)mode, (const uint32_t*)ADDR(key_class), (const cg_tx_check*)ADDR(checks),
+        (uint64_t)n_tx, (const uint32_t*)ADDR(reqs), (uint32_t)n_reqs, (const cg_req_node*)ADDR(nodes),
+        (uint32_t)n_nodes, (uint8_t*)ADDR(status), (cg_tx_verdict*)ADDR(verdicts), (uint8_t*)ADDR(req_status), 0);
+  return cg_verify_required_signatures_packed(
+      (cg_ctx*)(intptr_t)ctx, (const cg_key*)ADDR(keys), (uint32_t)n_keys, (const uint8_t*)ADDR(ids), (uint64_t)n_ids,
+      (const cg_txsig_packed*)ADDR(sigs), (uint64_t)n_sigs, (const uint8_t*)ADDR(sig_bytes), (uint64_t)sig_bytes_len,
+      (const cg_signable_tmpl*)ADDR(tmpls), (uint32_t)n_tmpls, (const uint8_t*)ADDR(arena), (uint64_t)arena_len,
+      (uint32_t)mode, (const uint32_t*)ADDR(key_class), (const cg_tx_check*)ADDR(checks), (uint64_t)n_tx,
+      (const uint32_t*)ADDR(reqs), (uint32_t)n_reqs, (const cg_req_node*)ADDR(nodes), (uint32_t)n_nodes,
+      (uint8_t*)ADDR(status), (cg_tx_verdict*)ADDR(verdicts), (uint8_t*)ADDR(req_status), 0);
+}
+
 /* WireTransaction ids + every signature (cg_verify_transactions; pool != 0: cg_pool_verify_transactions,
  * the whole call on one healthy device, the next one on a device fault). */
 JNIEXPORT jint JNICALL Java_net_corda_core_crypto_CryptoBatch_nativeVerifyTransactions(

@@ -8,6 +8,7 @@ package net.corda.core.crypto
 import com.codahale.metrics.Gauge
 import com.codahale.metrics.MetricRegistry
 import com.typesafe.config.Config
+import net.corda.core.crypto.composite.CompositeKey
 import net.corda.core.serialization.serialize
 import net.corda.core.transactions.SignedTransaction
 import java.nio.ByteBuffer
@@ -93,6 +94,13 @@ object CryptoBatch {
                                                         status: ByteBuffer, stats: ByteBuffer): Int
     /** cg_host_register / cg_host_unregister: a direct buffer the node keeps for many calls, pinned
      *  once so that its bytes reach the device by DMA without the runtime's CPU staging copy. */
+    private external fun nativeVerifyRequiredPacked(ctx: Long, pool: Long, keys: ByteBuffer, nKeys: Int,
+                                                    ids: ByteBuffer, nIds: Long, sigs: ByteBuffer, nSigs: Long,
+                                                    sigBytes: ByteBuffer, sigBytesLen: Long, tmpls: ByteBuffer,
+                                                    nTmpls: Int, arena: ByteBuffer, arenaLen: Long, mode: Int,
+                                                    keyClass: ByteBuffer, checks: ByteBuffer, nTx: Long,
+                                                    reqs: ByteBuffer, nReqs: Int, nodes: ByteBuffer, nNodes: Int,
+                                                    status: ByteBuffer?, verdicts: ByteBuffer, reqStatus: ByteBuffer): Int
     private external fun nativeHostRegister(buf: ByteBuffer, len: Long): Int
     private external fun nativeHostUnregister(buf: ByteBuffer): Int
 
@@ -109,6 +117,19 @@ object CryptoBatch {
     const val CG_EMPTY = 5
     const val CG_NOT_RUN = 255
     // include/cordagpu.h return codes
+    // per-transaction verdicts (include/cordagpu.h cg_tx_verdict.flags, req_status codes, struct sizes)
+    const val CG_TXV_SPAN_BAD = 1
+    const val CG_TXV_REQ_HOST = 2
+    const val CG_TXV_COMPOSITE_SIGNER = 4
+    const val CG_REQ_FULFILLED = 0
+    const val CG_REQ_MISSING = 1
+    const val CG_REQ_HOST = 2
+    const val CG_REQ_BAD = 255
+    private const val TX_CHECK_BYTES = 24
+    private const val REQ_NODE_BYTES = 16
+    private const val TX_VERDICT_BYTES = 8
+    private const val NO_BAD = -1                          // cg_tx_verdict.first_bad == 0xFFFFFFFF
+
     private const val CG_OK = 0
     private const val CG_ERR_DEVICE = -2
 
@@ -492,6 +513,135 @@ object CryptoBatch {
             val s = st[k++]
             if (s.toInt() != CG_VALID) raiseForStatus(s, BatchItem(sig.by, sig.bytes,
                                                       SignableData(stx.id, sig.signatureMetadata).serialize().bytes))
+        }
+    }
+
+    /** The cg_req_node table of a batch: the required keys' roots first, then every distinct CompositeKey's
+     *  children as one block, higher trees first, so that a child's index is always greater than its
+     *  parent's (the device walk refuses anything else). Equal CompositeKeys share a block, equal
+     *  required keys a root. Mirrors corda_amd/batch.py RequirementBuilder. */
+    private class Requirements(val classOf: (PublicKey) -> Int) {
+        val roots = LinkedHashMap<PublicKey, Int>()
+        val reqs = ArrayList<Int>()
+        fun add(keys: Collection<PublicKey>): Pair<Int, Int> {
+            val first = reqs.size
+            for (k in keys) reqs.add(roots.getOrPut(k) { roots.size })
+            return first to keys.size
+        }
+        fun nodes(): ByteBuffer {
+            val height = LinkedHashMap<CompositeKey, Int>()
+            fun visit(k: CompositeKey): Int = height[k] ?: (1 + (k.children.map { it.node }.filterIsInstance<CompositeKey>()
+                                                                  .map { visit(it) }.max() ?: 0)).also { height[k] = it }
+            roots.keys.filterIsInstance<CompositeKey>().forEach { visit(it) }
+            val block = LinkedHashMap<CompositeKey, Int>()
+            var at = roots.size
+            for (k in height.keys.sortedByDescending { height[it]!! }) { block[k] = at; at += k.children.size }
+            val out = ByteBuffer.allocateDirect(REQ_NODE_BYTES * maxOf(at, 1)).order(ByteOrder.LITTLE_ENDIAN)
+            fun fill(i: Int, k: PublicKey, weight: Int) {
+                out.position(REQ_NODE_BYTES * i)
+                if (k is CompositeKey) out.putInt(block[k]!!).putInt(k.children.size).putInt(weight).putInt(k.threshold)
+                else out.putInt(classOf(k)).putInt(0).putInt(weight).putInt(0)
+            }
+            roots.keys.forEachIndexed { i, k -> fill(i, k, 0) }
+            for ((k, first) in block) k.children.forEachIndexed { j, c -> fill(first + j, c.node, c.weight) }
+            out.position(REQ_NODE_BYTES * at)
+            return out
+        }
+    }
+
+    /** SignedTransaction.verifyRequiredSignatures / verifySignaturesExcept(allowedToBeMissing)
+     *  (TransactionWithSignatures.kt:41-47) for many transactions in one call: the signatures are verified and
+     *  reduced per transaction on the device (cg_verify_required_signatures_packed: the first failing
+     *  signature, then the required keys the signers do not fulfil, composite-aware). The first transaction
+     *  in list order that fails throws what its serial call throws. Key classes come from
+     *  PublicKey.equals / hashCode (a HashMap); CompositeKeys are validated here (checkValidity throws on the
+     *  host) and flattened. A transaction the device hands back -- CG_TXV_SPAN_BAD, CG_TXV_REQ_HOST without a
+     *  failing signature before it, or a first failing status of CG_UNSUPPORTED / CG_NOT_RUN (a scheme the
+     *  GPU does not run, a device fault) -- runs the reference's own verifySignaturesExcept.
+     *  Below gpuVerifier.minBatch signatures the serial calls run unchanged. */
+    fun verifyRequiredSignaturesAll(stxs: List<SignedTransaction>, allowedToBeMissing: Set<PublicKey> = emptySet()) {
+        val allowed = allowedToBeMissing.toTypedArray()
+        if (stxs.sumOf { it.sigs.size } < config.minBatch) {
+            for (stx in stxs) stx.verifySignaturesExcept(*allowed)
+            return
+        }
+        val all = stxs.flatMap { it.sigs }
+        val metas = LinkedHashMap<SignatureMetadata, Int>()
+        all.forEach { metas.getOrPut(it.signatureMetadata) { metas.size } }
+        val split = metas.keys.map { signableTemplate(it) }
+        val arena = direct(split.sumOf { it.first.size + it.second.size + 8 } +
+                           all.map { it.by }.distinct().sumOf { it.encoded.size + 4 } + 16)
+        val keys = Keys(all.map { it.by }, arena)
+        val tmpls = direct(24 * split.size)
+        for ((pre, suf) in split) {
+            arena.align4(); val p = arena.position().toLong(); arena.put(pre)
+            arena.align4(); val s = arena.position().toLong(); arena.put(suf)
+            tmpls.putLong(p).putLong(s).putInt(pre.size).putInt(suf.size)
+        }
+        // classes from PublicKey.equals: the key table's entries first (entry k has class k: Keys already merges
+        // equal keys), then every required leaf that never signed
+        val classes = HashMap<PublicKey, Int>()
+        keys.index.forEach { (k, i) -> classes[k] = i }
+        val keyClass = direct(4 * keys.index.size)
+        for (i in 0 until keys.index.size) keyClass.putInt(i)
+        val req = Requirements { k -> classes.getOrPut(k) { classes.size } }
+        val ids = direct(32 * stxs.size)
+        val sigs = direct(12 * all.size)
+        val stream = direct(all.sumOf { minOf(it.bytes.size, SIG_LEN_MAX) + 4 })
+        val checks = direct(TX_CHECK_BYTES * stxs.size)
+        val needed = ArrayList<List<PublicKey>>()
+        var pos = 0L
+        stxs.forEachIndexed { t, stx ->
+            ids.put(stx.id.bytes)
+            for (sig in stx.sigs) {
+                val k = keys.index[sig.by]!!
+                val bytes = sigField(keys.schemes[k], sig.bytes)
+                stream.put(bytes).align4()
+                sigs.putInt(t).putInt(k).putShort(bytes.size.toShort()).putShort(metas[sig.signatureMetadata]!!.toShort())
+            }
+            val want = stx.requiredSigningKeys.filter { it !in allowedToBeMissing }
+            want.filterIsInstance<CompositeKey>().forEach { it.checkValidity() }   // throws as isFulfilledBy would
+            val (first, n) = req.add(want)
+            needed.add(want)
+            checks.putLong(pos).putInt(stx.sigs.size).putInt(first).putInt(n).putInt(0)
+            pos += stx.sigs.size
+        }
+        val nodes = req.nodes()
+        val reqs = direct(4 * req.reqs.size)
+        req.reqs.forEach { reqs.putInt(it) }
+        val verdicts = direct(TX_VERDICT_BYTES * stxs.size)
+        val reqStatus = direct(req.reqs.size)
+        val rc = timed(all.size) {
+            withHandles { c, p ->
+                nativeVerifyRequiredPacked(c, p, keys.table, keys.index.size, ids, stxs.size.toLong(), sigs,
+                                           all.size.toLong(), stream, stream.position().toLong(), tmpls, split.size,
+                                           arena, arena.position().toLong(), MODE_DOVERIFY, keyClass, checks,
+                                           stxs.size.toLong(), reqs, req.reqs.size, nodes,
+                                           nodes.position() / REQ_NODE_BYTES, null, verdicts, reqStatus)
+            }
+        }
+        // a device fault leaves NOT_RUN verdicts (handled per transaction below); anything else is a bug
+        check(rc == CG_OK || rc == CG_ERR_DEVICE) { "cg_verify_required_signatures_packed failed ($rc)" }
+        stxs.forEachIndexed { t, stx ->
+            val firstBad = verdicts.getInt(TX_VERDICT_BYTES * t)
+            val status = verdicts.get(TX_VERDICT_BYTES * t + 4).toInt() and 0xff
+            val flags = verdicts.get(TX_VERDICT_BYTES * t + 5).toInt() and 0xff
+            val nMissing = verdicts.getShort(TX_VERDICT_BYTES * t + 6).toInt() and 0xffff
+            val hasBad = firstBad != NO_BAD
+            if ((flags and CG_TXV_SPAN_BAD) != 0 || (hasBad && (status == CG_UNSUPPORTED || status == CG_NOT_RUN)) ||
+                (!hasBad && (flags and CG_TXV_REQ_HOST) != 0)) {
+                stx.verifySignaturesExcept(*allowed)
+            } else if (hasBad) {
+                val sig = stx.sigs[firstBad]
+                raiseForStatus(status.toByte(), BatchItem(sig.by, sig.bytes,
+                                                          SignableData(stx.id, sig.signatureMetadata).serialize().bytes))
+            } else if (nMissing != 0) {
+                val first = checks.getInt(TX_CHECK_BYTES * t + 12)
+                val found = needed[t].filterIndexed { r, _ -> (reqStatus.get(first + r).toInt() and 0xff) == CG_REQ_MISSING }.toSet()
+                // built as getMissingSignatures builds it, so the exception lists the keys in its order
+                val missing = stx.requiredSigningKeys.filter { it in found }.toSet() - allowedToBeMissing
+                throw SignedTransaction.SignaturesMissingException(missing, stx.getKeyDescriptions(missing), stx.id)
+            }
         }
     }
 }
