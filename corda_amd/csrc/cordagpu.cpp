@@ -13,6 +13,7 @@
 #include <cstdio>
 #include <cstring>
 #include <functional>
+#include <initializer_list>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -20,6 +21,7 @@
 #include <vector>
 
 #include "../../include/cordagpu.h"
+#include "call_scope.h"
 #include "engine.h"
 #include "host_budget.h"
 #include "host_pool.h"
@@ -75,24 +77,13 @@ uint64_t env_u64(const char* name, uint64_t dflt) {
 struct DevBuf {
   void* p = nullptr;
   size_t cap = 0;
-  hipError_t ensure(size_t bytes) {
-    if (bytes <= cap) return hipSuccess;
-    if (p) hipFree(p);
-    p = nullptr;
-    cap = 0;
-    size_t want = bytes + bytes / 4 + 256;
-    hipError_t e = hipMalloc(&p, want);
-    if (e == hipSuccess) cap = want;
-    return e;
-  }
+  hipError_t ensure(size_t bytes) { return bytes <= cap ? hipSuccess : replace(bytes + bytes / 4 + 256); }
   // exactly `bytes` (no growth margin): for the multi-GB wide-table pools
-  hipError_t ensure_exact(size_t bytes) {
-    if (bytes <= cap) return hipSuccess;
-    if (p) hipFree(p);
-    p = nullptr;
-    cap = 0;
-    hipError_t e = hipMalloc(&p, bytes);
-    if (e == hipSuccess) cap = bytes;
+  hipError_t ensure_exact(size_t bytes) { return bytes <= cap ? hipSuccess : replace(bytes); }
+  hipError_t replace(size_t want) {
+    release();
+    const hipError_t e = hipMalloc(&p, want);
+    if (e == hipSuccess) cap = want;
     return e;
   }
   void release() {
@@ -102,14 +93,52 @@ struct DevBuf {
   }
 };
 
+// Grows whichever of the buffers are short, after waiting for the device: an earlier call's kernels
+// may still be using them (cg_reserve ahead of time avoids the wait).
+struct Need {
+  DevBuf* buf;
+  size_t bytes;
+};
+hipError_t ensure_all(std::initializer_list<Need> needs) {
+  bool grow = false;
+  for (const Need& n : needs) grow = grow || n.buf->cap < n.bytes;
+  if (!grow) return hipSuccess;
+  hipError_t e = hipDeviceSynchronize();
+  for (const Need& n : needs)
+    if (e == hipSuccess) e = n.buf->ensure(n.bytes);
+  return e;
+}
+
+// A host form's table to its device buffer: room for `room` bytes (at least the table, never nothing),
+// then the copy, if there is anything to copy.
+hipError_t stage(DevBuf& b, const void* src, size_t bytes, hipStream_t s, size_t room = 0) {
+  hipError_t e = b.ensure(std::max<size_t>({bytes, room, 1}));
+  if (e == hipSuccess && bytes) e = hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, s);
+  return e;
+}
+// A whole arena on the device: rounded up to the kernels' aligned dword loads, plus slack.
+size_t arena_room(uint64_t arena_len) { return ((arena_len + 3) & ~(uint64_t)3) + 16; }
+
+// The stream API of call_scope.h over HIP.
+struct HipStreams {
+  using Stream = hipStream_t;
+  using Event = hipEvent_t;
+  using Error = hipError_t;
+  static constexpr Error kOk = hipSuccess;
+  Error record(Event e, Stream s) { return hipEventRecord(e, s); }
+  Error wait(Stream s, Event e) { return hipStreamWaitEvent(s, e, 0); }
+  Error sync(Stream s) { return hipStreamSynchronize(s); }
+};
+
 }  // namespace
 
-struct cg_ctx {
+// cg::CallState: the context's stream and copy stream (the host forms' H2D of chunk k + 1 overlaps
+// the verify of chunk k), and the ordering of its calls (call_scope.h: done, bridge, caller)
+struct cg_ctx : cg::CallState<HipStreams> {
   int device = 0;
   uint64_t chunk = CG_DEFAULT_CHUNK_ITEMS;  // items per verify chunk (cg_config.chunk_items)
   bool chunk_set = false;                   // the caller chose it (else the host tx-signature path pipelines finer)
-  bool fault = false;                       // cg_pool_inject_fault drill: every call fails
-  hipStream_t stream = nullptr;
+  bool fault = false;                       // cg_pool_inject_fault drill: every call fails (enter)
   cg::Fork fork = {{nullptr, nullptr, nullptr}, nullptr, {nullptr, nullptr}, {nullptr, nullptr, nullptr}, nullptr,
                    {nullptr, nullptr, nullptr}, nullptr};
   std::mutex mu;
@@ -150,9 +179,7 @@ struct cg_ctx {
   DevBuf txvws, txvio;
   // tear-offs: leaf-hash workspace
   DevBuf ftxws;
-  // host-buffer verify: a copy stream and one event per pipeline chunk (H2D of chunk k+1 overlaps
-  // the verify of chunk k); timing events for cg_stats
-  hipStream_t copy = nullptr;
+  // host-buffer verify: one event per pipeline chunk (seg); timing events for cg_stats (tev)
   // a second stream on a hardware queue of its own, idle in every default schedule: the
   // CG_HOST_TRACE marker "tables built" waits there (launch_chunked), and CG_DEV_FRONT_STREAM runs a
   // device call's second front on it
@@ -175,13 +202,7 @@ struct cg_ctx {
   std::vector<hipEvent_t> fbt;  // CG_HOST_TRACE: per chunk, the main stream reaching its front / its back's end
   std::vector<double> fbh;      // host ms at which chunk k's front kernels were enqueued
   bool htrace = false;
-  // the end of the last call's device work, whatever stream it ran on: the next call waits for it
-  // before touching the shared workspace (async calls on different streams)
-  hipEvent_t done = nullptr;
-  bool done_rec = false;
-  hipEvent_t bridge = nullptr;  // a caller stream's point of entry (stream_of)
   hipEvent_t fs[2] = {nullptr, nullptr};  // the device forms' front stream (launch_chunked)
-  hipStream_t caller = nullptr; // the caller's stream the current device call is bridged from
   cg::StageTimer timer;  // used when opened with CG_FLAG_STAGE_TIMING
 };
 
@@ -290,32 +311,26 @@ void host_par(cg_ctx* c, uint64_t m, const std::function<void(uint64_t)>& fn) {
   }
 }
 
-hipError_t order_in(cg_ctx* c, hipStream_t s) { return c->done_rec ? hipStreamWaitEvent(s, c->done, 0) : hipSuccess; }
-hipError_t order_out(cg_ctx* c, hipStream_t s) {
-  hipError_t e = hipEventRecord(c->done, s);
-  if (e == hipSuccess) c->done_rec = true;
-  if (e == hipSuccess && c->caller) e = hipStreamWaitEvent(c->caller, c->done, 0);  // the bridge back
-  c->caller = nullptr;
-  return e;
-}
-// The stream a device call runs on. A caller's stream is bridged to the context's own stream: HIP
-// multiplexes streams onto GPU_MAX_HW_QUEUES (4) hardware queues in creation order, and a stream
-// created elsewhere (torch's, the JVM's) can share an in-order queue with one of the side streams,
-// whose milliseconds-long chains and table builds then run ahead of the call's main-stream kernels
-// (round 6: the device-resident headline on torch's stream sat ~3.5 ms per step behind side stream
-// 0's wide chain and rows, profiles/r06/bridge). The context's stream, created first, has a queue of
-// its own; it waits for everything the caller enqueued before the call, and order_out makes the
-// caller's stream wait for the call's end, so the call stays ordered on the caller's stream.
-// CG_STREAM_BRIDGE=0: run on the caller's stream itself (A/B).
-hipStream_t stream_of(cg_ctx* c, void* hip_stream) {
-  static const bool bridge = env_flag("CG_STREAM_BRIDGE", true);
-  c->caller = nullptr;
-  if (!hip_stream || (hipStream_t)hip_stream == c->stream) return c->stream;
-  if (!bridge || !c->bridge || hipEventRecord(c->bridge, (hipStream_t)hip_stream) != hipSuccess ||
-      hipStreamWaitEvent(c->stream, c->bridge, 0) != hipSuccess)
-    return (hipStream_t)hip_stream;
-  c->caller = (hipStream_t)hip_stream;
-  return c->stream;
+// One C-ABI call's ordering on its context (call_scope.h), declared with the ctx lock held and after
+// every host buffer the call copies from. A device form opens it on the caller's stream and runs on
+// stream(). A caller's stream is bridged to the context's own stream: HIP multiplexes streams onto
+// GPU_MAX_HW_QUEUES (4) hardware queues in creation order, and a stream created elsewhere (torch's,
+// the JVM's) can share an in-order queue with one of the side streams, whose milliseconds-long
+// chains and table builds then run ahead of the call's main-stream kernels (round 6: the
+// device-resident headline on torch's stream sat ~3.5 ms per step behind side stream 0's wide chain
+// and rows, profiles/r06/bridge). The context's stream, created first, has a queue of its own.
+// CG_STREAM_BRIDGE=0: run on the caller's stream itself (A/B; read at cg_open).
+HipStreams g_hip;
+struct Call : cg::CallScope<HipStreams> {
+  Call(cg_ctx* c, Form form) : CallScope(g_hip, *c, form) {}
+  hipError_t open(void* hip_stream = nullptr) { return CallScope::open((hipStream_t)hip_stream); }
+};
+
+// Every entry point's first step under the ctx lock: the drill fault fails the call, else its device.
+int enter(cg_ctx* c, const char* fn) {
+  if (c->fault) return fail(CG_ERR_DEVICE, "%s: device fault (injected by cg_pool_inject_fault)", fn);
+  HIP_TRY(hipSetDevice(c->device), "hipSetDevice");
+  return CG_OK;
 }
 
 // Equal chunks of at most c->chunk items.
@@ -330,12 +345,7 @@ size_t item_half_bytes(const cg_ctx* c, uint64_t ws_items) { return (c->eng->ite
 // The RSA workspace (contexts with CG_FLAG_RSA only): key records and the item list. Grows like keyprep.
 hipError_t ensure_rsa(cg_ctx* c, uint32_t n_keys, uint64_t n_items) {
   if (!c->rsa) return hipSuccess;
-  const size_t kb = cg::rsa_keys_bytes(n_keys), lb = cg::rsa_list_bytes(n_items);
-  if (c->rsakeys.cap >= kb && c->rsalist.cap >= lb) return hipSuccess;
-  hipError_t e = hipDeviceSynchronize();
-  if (e == hipSuccess) e = c->rsakeys.ensure(kb);
-  if (e == hipSuccess) e = c->rsalist.ensure(lb);
-  return e;
+  return ensure_all({{&c->rsakeys, cg::rsa_keys_bytes(n_keys)}, {&c->rsalist, cg::rsa_list_bytes(n_items)}});
 }
 // The RSA halves of a call, on the stream of its other launches: the key records before any item
 // stage, the item pass after the last chunk's back (the item table, the arena window, the tx items
@@ -610,6 +620,17 @@ hipError_t copy_missing(cg::Resident& have, const Extent& e, const uint8_t* aren
   return hipSuccess;
 }
 
+// At least n events without timing in v.
+hipError_t ensure_events(std::vector<hipEvent_t>& v, uint64_t n) {
+  while (v.size() < n) {
+    hipEvent_t e;
+    const hipError_t r = hipEventCreateWithFlags(&e, hipEventDisableTiming);
+    if (r != hipSuccess) return r;
+    v.push_back(e);
+  }
+  return hipSuccess;
+}
+
 // The device timings of a host call (tev[0..3]: start, first chunk ready, verify done, verdicts back).
 void fill_stats(cg_ctx* c, cg_stats* stats, uint64_t n_items, uint32_t n_keys, double ms_key_prep,
                 std::chrono::steady_clock::time_point t0) {
@@ -631,8 +652,7 @@ void fill_stats(cg_ctx* c, cg_stats* stats, uint64_t n_items, uint32_t n_keys, d
 int verify_host_locked(cg_ctx* c, const cg_key* keys, uint32_t n_keys, const cg_item* items, uint64_t n_items,
                        const uint8_t* arena, uint64_t arena_len, uint32_t mode, uint8_t* status_out, cg_stats* stats) {
   const auto t0 = std::chrono::steady_clock::now();
-  if (c->fault) return fail(CG_ERR_DEVICE, "cg_verify_batch: device fault (injected by cg_pool_inject_fault)");
-  HIP_TRY(hipSetDevice(c->device), "hipSetDevice");
+  if (const int rc = enter(c, "cg_verify_batch")) return rc;
   const uint64_t pipe = c->chunk < CG_PIPELINE_CHUNK_ITEMS ? c->chunk : CG_PIPELINE_CHUNK_ITEMS;
   HostPlan P;
   plan_host(c, keys, n_keys, items, n_items, arena_len, pipe, P);
@@ -643,16 +663,13 @@ int verify_host_locked(cg_ctx* c, const cg_key* keys, uint32_t n_keys, const cg_
   HIP_TRY(c->arena.ensure((P.win.hi - P.win.lo) + 16), "hipMalloc(arena window)");
   HIP_TRY(c->status.ensure(n_items), "hipMalloc(status)");
   HIP_TRY(ensure_ws(c, n_keys, per_max, n_items), "hipMalloc(workspace)");
-  while (c->seg.size() < nch) {
-    hipEvent_t e;
-    HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming), "hipEventCreate");
-    c->seg.push_back(e);
-  }
+  HIP_TRY(ensure_events(c->seg, nch), "hipEventCreate");
   hipStream_t s = c->stream;
   uint8_t* dwin = (uint8_t*)c->arena.p;
   // the kernels index the arena by absolute offsets: hand them the window's base shifted back
   const uint8_t* dbase = dwin - P.win.lo;
-  HIP_TRY(order_in(c, s), "hipStreamWaitEvent");
+  Call call(c, Call::kHost);
+  HIP_TRY(call.open(), "hipStreamWaitEvent");
   HIP_TRY(hipEventRecord(c->tev[0], s), "hipEventRecord");
   HIP_TRY(hipStreamWaitEvent(c->copy, c->tev[0], 0), "hipStreamWaitEvent");
   cg::Resident have;
@@ -684,7 +701,7 @@ int verify_host_locked(cg_ctx* c, const cg_key* keys, uint32_t n_keys, const cg_
   HIP_TRY(hipEventRecord(c->tev[2], s), "hipEventRecord");
   HIP_TRY(hipMemcpyAsync(status_out, ds, n_items, hipMemcpyDeviceToHost, s), "D2H status");
   HIP_TRY(hipEventRecord(c->tev[3], s), "hipEventRecord");
-  HIP_TRY(order_out(c, s), "hipEventRecord");
+  HIP_TRY(call.close(), "hipEventRecord");
   HIP_TRY(hipStreamSynchronize(s), "hipStreamSynchronize");
   fill_stats(c, stats, n_items, n_keys, 0, t0);
   return CG_OK;
@@ -861,6 +878,7 @@ int cg_open(cg_ctx** out, const cg_config* cfg) {
   for (int k = 0; k < 4 && e == hipSuccess; ++k) e = hipEventCreate(&c->tev[k]);
   if (e == hipSuccess) e = hipEventCreateWithFlags(&c->done, hipEventDisableTiming);
   if (e == hipSuccess) e = hipEventCreateWithFlags(&c->bridge, hipEventDisableTiming);
+  c->bridged = env_flag("CG_STREAM_BRIDGE", true);
   for (int k = 0; k < 2 && e == hipSuccess; ++k) e = hipEventCreateWithFlags(&c->fs[k], hipEventDisableTiming);
   int var = 0;
   if (e == hipSuccess) e = acquire_tables(c->device, c->stream, tab_budget, &c->btab, &var);
@@ -982,7 +1000,7 @@ int cg_context_info(const cg_ctx* c, cg_info* out) {
 int cg_stage_times(cg_ctx* c, double* ms_out, uint32_t* launches_out, uint32_t n) {
   if (!c || (n && (!ms_out || !launches_out))) return fail(CG_ERR_ARG, "cg_stage_times: NULL argument");
   std::lock_guard<std::mutex> g(c->mu);
-  HIP_TRY(hipSetDevice(c->device), "hipSetDevice");
+  if (const int rc = enter(c, "cg_stage_times")) return rc;
   const uint32_t m = n < CG_STAGES ? n : CG_STAGES;
   for (uint32_t k = 0; k < m; ++k) {
     ms_out[k] = 0;
@@ -1005,7 +1023,7 @@ int cg_stage_times(cg_ctx* c, double* ms_out, uint32_t* launches_out, uint32_t n
 int cg_reserve(cg_ctx* c, uint32_t max_keys, uint64_t max_items) {
   if (!c) return fail(CG_ERR_ARG, "cg_reserve: ctx is NULL");
   std::lock_guard<std::mutex> g(c->mu);
-  HIP_TRY(hipSetDevice(c->device), "hipSetDevice");
+  if (const int rc = enter(c, "cg_reserve")) return rc;
   HIP_TRY(ensure_ws(c, max_keys, chunk_of(c, max_items), max_items), "hipMalloc(workspace)");
   return CG_OK;
 }
@@ -1013,7 +1031,7 @@ int cg_reserve(cg_ctx* c, uint32_t max_keys, uint64_t max_items) {
 int cg_key_cache_stats(cg_ctx* c, cg_key_cache_info* out) {
   if (!c || !out) return fail(CG_ERR_ARG, "cg_key_cache_stats: NULL argument");
   std::lock_guard<std::mutex> g(c->mu);
-  HIP_TRY(hipSetDevice(c->device), "hipSetDevice");
+  if (const int rc = enter(c, "cg_key_cache_stats")) return rc;
   memset(out, 0, sizeof *out);
   out->enabled = c->kc_on ? 1u : 0u;
   out->slots = c->wide_slots;
@@ -1038,13 +1056,13 @@ int cg_verify_batch_device(cg_ctx* c, const cg_key* d_keys, uint32_t n_keys, con
   if (n_items && (!d_items || !d_status)) return fail(CG_ERR_ARG, "cg_verify_batch_device: NULL buffer");
   if (mode > CG_MODE_ISVALID) return fail(CG_ERR_ARG, "cg_verify_batch_device: bad mode");
   std::lock_guard<std::mutex> g(c->mu);
-  if (c->fault) return fail(CG_ERR_DEVICE, "cg_verify_batch_device: device fault (injected)");
-  HIP_TRY(hipSetDevice(c->device), "hipSetDevice");
+  if (const int rc = enter(c, "cg_verify_batch_device")) return rc;
   HIP_TRY(ensure_ws(c, n_keys, chunk_of(c, n_items), n_items), "hipMalloc(workspace)");
-  hipStream_t s = stream_of(c, hip_stream);
-  HIP_TRY(order_in(c, s), "hipStreamWaitEvent");
-  HIP_TRY(launch_chunked(c, d_keys, n_keys, d_items, n_items, d_arena, arena_len, mode, d_status, s), "launch_verify");
-  HIP_TRY(order_out(c, s), "hipEventRecord");
+  Call call(c, Call::kDevice);
+  HIP_TRY(call.open(hip_stream), "hipStreamWaitEvent");
+  HIP_TRY(launch_chunked(c, d_keys, n_keys, d_items, n_items, d_arena, arena_len, mode, d_status, call.stream()),
+          "launch_verify");
+  HIP_TRY(call.close(), "hipEventRecord");
   return CG_OK;
 }
 
@@ -1053,21 +1071,16 @@ int cg_prepare_keys_device(cg_ctx* c, const cg_key* d_keys, uint32_t n_keys, con
   if (!c) return fail(CG_ERR_ARG, "cg_prepare_keys_device: ctx is NULL");
   if (n_keys && !d_keys) return fail(CG_ERR_ARG, "cg_prepare_keys_device: keys is NULL");
   std::lock_guard<std::mutex> g(c->mu);
-  HIP_TRY(hipSetDevice(c->device), "hipSetDevice");
-  if (c->keyprep.cap < c->eng->keyprep_bytes(n_keys)) {
-    HIP_TRY(hipDeviceSynchronize(), "hipDeviceSynchronize");
-    HIP_TRY(c->keyprep.ensure(c->eng->keyprep_bytes(n_keys)), "hipMalloc(keyprep)");
-  }
+  if (const int rc = enter(c, "cg_prepare_keys_device")) return rc;
+  HIP_TRY(ensure_all({{&c->keyprep, c->eng->keyprep_bytes(n_keys)}}), "hipMalloc(keyprep)");
   HIP_TRY(ensure_rsa(c, n_keys, 0), "hipMalloc(RSA workspace)");
-  hipStream_t s = stream_of(c, hip_stream);
-  HIP_TRY(order_in(c, s), "hipStreamWaitEvent");
-  {  // one guarded region for both launches: no early return of its own between them (stream_of's bridge)
-    hipError_t e = c->eng->launch_keyprep(d_keys, n_keys, d_arena, arena_len, c->keyprep.p, s, &c->fork, nullptr, 0,
-                                          nullptr, nullptr);
-    if (e == hipSuccess) e = rsa_keyprep(c, d_keys, n_keys, d_arena, arena_len, s);
-    HIP_TRY(e, "launch_keyprep");
-  }
-  HIP_TRY(order_out(c, s), "hipEventRecord");
+  Call call(c, Call::kDevice);
+  HIP_TRY(call.open(hip_stream), "hipStreamWaitEvent");
+  hipStream_t s = call.stream();
+  HIP_TRY(c->eng->launch_keyprep(d_keys, n_keys, d_arena, arena_len, c->keyprep.p, s, &c->fork, nullptr, 0, nullptr,
+                                 nullptr), "launch_keyprep");
+  HIP_TRY(rsa_keyprep(c, d_keys, n_keys, d_arena, arena_len, s), "launch_rsa_keyprep");
+  HIP_TRY(call.close(), "hipEventRecord");
   return CG_OK;
 }
 
@@ -1082,21 +1095,20 @@ int cg_verify_items_device(cg_ctx* c, const cg_key* d_keys, uint32_t n_keys, con
     return fail(CG_ERR_ARG, "cg_verify_items_device: keys were not prepared (call cg_prepare_keys_device)");
   if (c->rsa && c->rsakeys.cap < cg::rsa_keys_bytes(n_keys))
     return fail(CG_ERR_ARG, "cg_verify_items_device: RSA keys were not prepared (call cg_prepare_keys_device)");
-  HIP_TRY(hipSetDevice(c->device), "hipSetDevice");
+  if (const int rc = enter(c, "cg_verify_items_device")) return rc;
   HIP_TRY(ensure_ws(c, n_keys, chunk_of(c, n_items)), "hipMalloc(item workspace)");
   HIP_TRY(ensure_rsa(c, n_keys, n_items), "hipMalloc(RSA workspace)");
-  hipStream_t s = stream_of(c, hip_stream);
-  HIP_TRY(order_in(c, s), "hipStreamWaitEvent");
+  Call call(c, Call::kDevice);
+  HIP_TRY(call.open(hip_stream), "hipStreamWaitEvent");
+  hipStream_t s = call.stream();
   const uint64_t per = chunk_of(c, n_items);
-  hipError_t le = hipSuccess;  // the chunks and the RSA pass in one guarded region (stream_of's bridge)
-  for (uint64_t f = 0; f < n_items && le == hipSuccess; f += per) {
+  for (uint64_t f = 0; f < n_items; f += per) {
     const uint64_t cnt = per < n_items - f ? per : n_items - f;
-    le = c->eng->launch_items(d_keys, n_keys, d_items + f, cnt, d_arena, arena_len, mode, d_status + f, c->keyprep.p,
-                              c->itemws.p, c->btab, s, nullptr, 0, &c->fork, nullptr);
+    HIP_TRY(c->eng->launch_items(d_keys, n_keys, d_items + f, cnt, d_arena, arena_len, mode, d_status + f, c->keyprep.p,
+                                 c->itemws.p, c->btab, s, nullptr, 0, &c->fork, nullptr), "launch_items");
   }
-  if (le == hipSuccess) le = rsa_items(c, d_keys, n_keys, d_items, n_items, d_arena, arena_len, mode, d_status, s);
-  HIP_TRY(le, "launch_items");
-  HIP_TRY(order_out(c, s), "hipEventRecord");
+  HIP_TRY(rsa_items(c, d_keys, n_keys, d_items, n_items, d_arena, arena_len, mode, d_status, s), "launch_rsa_items");
+  HIP_TRY(call.close(), "hipEventRecord");
   return CG_OK;
 }
 
@@ -1120,11 +1132,11 @@ int cg_sha256_batch_device(cg_ctx* c, const cg_span* d_spans, uint64_t n, const 
                            uint64_t arena_len, uint8_t* d_digests, void* hip_stream) {
   if (!c) return fail(CG_ERR_ARG, "cg_sha256_batch_device: ctx is NULL");
   std::lock_guard<std::mutex> g(c->mu);
-  HIP_TRY(hipSetDevice(c->device), "hipSetDevice");
-  hipStream_t s = stream_of(c, hip_stream);
-  HIP_TRY(order_in(c, s), "hipStreamWaitEvent");
-  HIP_TRY(cg::launch_sha256(d_spans, n, d_arena, arena_len, d_digests, s), "launch_sha256");
-  HIP_TRY(order_out(c, s), "hipEventRecord");
+  if (const int rc = enter(c, "cg_sha256_batch_device")) return rc;
+  Call call(c, Call::kDevice);
+  HIP_TRY(call.open(hip_stream), "hipStreamWaitEvent");
+  HIP_TRY(cg::launch_sha256(d_spans, n, d_arena, arena_len, d_digests, call.stream()), "launch_sha256");
+  HIP_TRY(call.close(), "hipEventRecord");
   return CG_OK;
 }
 
@@ -1135,21 +1147,17 @@ static int hash_batch(cg_ctx* c, const cg_span* spans, uint64_t n, const uint8_t
   if (n == 0) return CG_OK;
   const size_t dlen = which == 256 ? 32 : 64;
   std::lock_guard<std::mutex> g(c->mu);
-  HIP_TRY(hipSetDevice(c->device), "hipSetDevice");
+  if (const int rc = enter(c, which == 256 ? "cg_sha256_batch" : "cg_sha512_batch")) return rc;
   hipStream_t s = c->stream;
-  HIP_TRY(order_in(c, s), "hipStreamWaitEvent");
-  HIP_TRY(c->items.ensure(sizeof(cg_span) * n), "hipMalloc(spans)");
-  HIP_TRY(c->arena.ensure(((arena_len + 3) & ~(uint64_t)3) + 16), "hipMalloc(arena)");
+  Call call(c, Call::kHost);
+  HIP_TRY(call.open(), "hipStreamWaitEvent");
+  HIP_TRY(stage(c->items, spans, sizeof(cg_span) * n, s), "H2D spans");
+  HIP_TRY(stage(c->arena, arena, arena_len, s, arena_room(arena_len)), "H2D arena");
   HIP_TRY(c->aux0.ensure(dlen * n), "hipMalloc(digests)");
-  HIP_TRY(hipMemcpyAsync(c->items.p, spans, sizeof(cg_span) * n, hipMemcpyHostToDevice, s), "H2D spans");
-  if (arena_len) HIP_TRY(hipMemcpyAsync(c->arena.p, arena, arena_len, hipMemcpyHostToDevice, s), "H2D arena");
-  if (which == 256)
-    HIP_TRY(cg::launch_sha256((const cg_span*)c->items.p, n, (const uint8_t*)c->arena.p, arena_len,
-                              (uint8_t*)c->aux0.p, s), "launch_sha256");
-  else
-    HIP_TRY(cg::launch_sha512((const cg_span*)c->items.p, n, (const uint8_t*)c->arena.p, arena_len,
-                              (uint8_t*)c->aux0.p, s), "launch_sha512");
+  HIP_TRY((which == 256 ? cg::launch_sha256 : cg::launch_sha512)((const cg_span*)c->items.p, n, (const uint8_t*)c->arena.p,
+                                                                 arena_len, (uint8_t*)c->aux0.p, s), "launch_sha");
   HIP_TRY(hipMemcpyAsync(out, c->aux0.p, dlen * n, hipMemcpyDeviceToHost, s), "D2H digests");
+  HIP_TRY(call.close(), "hipEventRecord");
   HIP_TRY(hipStreamSynchronize(s), "hipStreamSynchronize");
   return CG_OK;
 }
@@ -1168,16 +1176,13 @@ int cg_tx_ids_device(cg_ctx* c, const cg_tx* d_txs, uint64_t n_tx, const cg_comp
                      void* hip_stream) {
   if (!c) return fail(CG_ERR_ARG, "cg_tx_ids_device: ctx is NULL");
   std::lock_guard<std::mutex> g(c->mu);
-  HIP_TRY(hipSetDevice(c->device), "hipSetDevice");
-  if (c->aux2.cap < cg::tx_ws_bytes(n_comps)) {
-    HIP_TRY(hipDeviceSynchronize(), "hipDeviceSynchronize");
-    HIP_TRY(c->aux2.ensure(cg::tx_ws_bytes(n_comps)), "hipMalloc(leaf ws)");
-  }
-  hipStream_t s = stream_of(c, hip_stream);
-  HIP_TRY(order_in(c, s), "hipStreamWaitEvent");
+  if (const int rc = enter(c, "cg_tx_ids_device")) return rc;
+  HIP_TRY(ensure_all({{&c->aux2, cg::tx_ws_bytes(n_comps)}}), "hipMalloc(leaf ws)");
+  Call call(c, Call::kDevice);
+  HIP_TRY(call.open(hip_stream), "hipStreamWaitEvent");
   HIP_TRY(cg::launch_tx_ids(d_txs, n_tx, d_comps, n_comps, d_arena, arena_len, d_ids, d_status,
-                            (uint8_t*)c->aux2.p, s), "launch_tx_ids");
-  HIP_TRY(order_out(c, s), "hipEventRecord");
+                            (uint8_t*)c->aux2.p, call.stream()), "launch_tx_ids");
+  HIP_TRY(call.close(), "hipEventRecord");
   return CG_OK;
 }
 
@@ -1187,24 +1192,22 @@ int cg_tx_ids(cg_ctx* c, const cg_tx* txs, uint64_t n_tx, const cg_component* co
   if (n_tx && (!txs || !ids_out || !status_out)) return fail(CG_ERR_ARG, "cg_tx_ids: NULL buffer");
   if (n_tx == 0) return CG_OK;
   std::lock_guard<std::mutex> g(c->mu);
-  HIP_TRY(hipSetDevice(c->device), "hipSetDevice");
+  if (const int rc = enter(c, "cg_tx_ids")) return rc;
   hipStream_t s = c->stream;
-  HIP_TRY(order_in(c, s), "hipStreamWaitEvent");
-  HIP_TRY(c->keys.ensure(sizeof(cg_tx) * n_tx), "hipMalloc(txs)");
-  HIP_TRY(c->items.ensure(sizeof(cg_component) * (n_comps ? n_comps : 1)), "hipMalloc(comps)");
-  HIP_TRY(c->arena.ensure(((arena_len + 3) & ~(uint64_t)3) + 16), "hipMalloc(arena)");
+  Call call(c, Call::kHost);
+  HIP_TRY(call.open(), "hipStreamWaitEvent");
+  HIP_TRY(stage(c->keys, txs, sizeof(cg_tx) * n_tx, s), "H2D txs");
+  HIP_TRY(stage(c->items, comps, sizeof(cg_component) * n_comps, s), "H2D comps");
+  HIP_TRY(stage(c->arena, arena, arena_len, s, arena_room(arena_len)), "H2D arena");
   HIP_TRY(c->aux0.ensure(32 * n_tx), "hipMalloc(ids)");
   HIP_TRY(c->status.ensure(n_tx), "hipMalloc(status)");
   HIP_TRY(c->aux2.ensure(cg::tx_ws_bytes(n_comps)), "hipMalloc(leaf ws)");
-  HIP_TRY(hipMemcpyAsync(c->keys.p, txs, sizeof(cg_tx) * n_tx, hipMemcpyHostToDevice, s), "H2D txs");
-  if (n_comps)
-    HIP_TRY(hipMemcpyAsync(c->items.p, comps, sizeof(cg_component) * n_comps, hipMemcpyHostToDevice, s), "H2D comps");
-  if (arena_len) HIP_TRY(hipMemcpyAsync(c->arena.p, arena, arena_len, hipMemcpyHostToDevice, s), "H2D arena");
   HIP_TRY(cg::launch_tx_ids((const cg_tx*)c->keys.p, n_tx, (const cg_component*)c->items.p, n_comps,
                             (const uint8_t*)c->arena.p, arena_len, (uint8_t*)c->aux0.p, (uint8_t*)c->status.p,
                             (uint8_t*)c->aux2.p, s), "launch_tx_ids");
   HIP_TRY(hipMemcpyAsync(ids_out, c->aux0.p, 32 * n_tx, hipMemcpyDeviceToHost, s), "D2H ids");
   HIP_TRY(hipMemcpyAsync(status_out, c->status.p, n_tx, hipMemcpyDeviceToHost, s), "D2H status");
+  HIP_TRY(call.close(), "hipEventRecord");
   HIP_TRY(hipStreamSynchronize(s), "hipStreamSynchronize");
   return CG_OK;
 }
@@ -1222,56 +1225,53 @@ int cg_merkle_roots(cg_ctx* c, const uint8_t* leaves, const uint64_t* first, con
     ws += count[j];
   }
   std::lock_guard<std::mutex> g(c->mu);
-  HIP_TRY(hipSetDevice(c->device), "hipSetDevice");
+  if (const int rc = enter(c, "cg_merkle_roots")) return rc;
   hipStream_t s = c->stream;
-  HIP_TRY(order_in(c, s), "hipStreamWaitEvent");
-  HIP_TRY(c->arena.ensure(32 * (total ? total : 1)), "hipMalloc(leaves)");
-  HIP_TRY(c->keys.ensure(8 * n), "hipMalloc(first)");
-  HIP_TRY(c->items.ensure(4 * n), "hipMalloc(count)");
+  Call call(c, Call::kHost);
+  HIP_TRY(call.open(), "hipStreamWaitEvent");
+  HIP_TRY(stage(c->arena, leaves, 32 * total, s), "H2D leaves");
+  HIP_TRY(stage(c->keys, first, 8 * n, s), "H2D first");
+  HIP_TRY(stage(c->items, count, 4 * n, s), "H2D count");
+  HIP_TRY(stage(c->aux2, wsoff.data(), 8 * n, s), "H2D wsoff");
   HIP_TRY(c->aux0.ensure(32 * n), "hipMalloc(roots)");
   HIP_TRY(c->status.ensure(n), "hipMalloc(status)");
   HIP_TRY(c->aux1.ensure(32 * (ws ? ws : 1)), "hipMalloc(ws)");
-  HIP_TRY(c->aux2.ensure(8 * n), "hipMalloc(wsoff)");
-  if (total) HIP_TRY(hipMemcpyAsync(c->arena.p, leaves, 32 * total, hipMemcpyHostToDevice, s), "H2D leaves");
-  HIP_TRY(hipMemcpyAsync(c->keys.p, first, 8 * n, hipMemcpyHostToDevice, s), "H2D first");
-  HIP_TRY(hipMemcpyAsync(c->items.p, count, 4 * n, hipMemcpyHostToDevice, s), "H2D count");
-  HIP_TRY(hipMemcpyAsync(c->aux2.p, wsoff.data(), 8 * n, hipMemcpyHostToDevice, s), "H2D wsoff");
   HIP_TRY(cg::launch_merkle_roots((const uint8_t*)c->arena.p, (const uint64_t*)c->keys.p, (const uint32_t*)c->items.p,
                                   n, (uint8_t*)c->aux0.p, (uint8_t*)c->status.p, (uint8_t*)c->aux1.p,
                                   (const uint64_t*)c->aux2.p, s),
           "launch_merkle_roots");
   HIP_TRY(hipMemcpyAsync(roots_out, c->aux0.p, 32 * n, hipMemcpyDeviceToHost, s), "D2H roots");
   HIP_TRY(hipMemcpyAsync(status_out, c->status.p, n, hipMemcpyDeviceToHost, s), "D2H status");
+  HIP_TRY(call.close(), "hipEventRecord");
   HIP_TRY(hipStreamSynchronize(s), "hipStreamSynchronize");
   return CG_OK;
 }
 
-// cg_verify_transactions_device with the ctx lock held
-static int verify_transactions_locked(cg_ctx* c, const cg_tx* d_txs, uint64_t n_tx, const cg_component* d_comps,
-                                      uint64_t n_comps, const cg_key* d_keys, uint32_t n_keys, const cg_txsig* d_sigs,
-                                      uint64_t n_sigs, const cg_signable_tmpl* tmpls, uint32_t n_tmpls,
-                                      const uint8_t* d_arena, uint64_t arena_len, uint32_t mode, uint8_t* d_ids,
-                                      uint8_t* d_tx_status, uint8_t* d_sig_status, hipStream_t s) {
+// The spliced-message slot of a template set: the longest prefix || id || suffix, 16-aligned.
+static uint64_t tmpl_slot(const cg_signable_tmpl* tmpls, uint32_t n_tmpls) {
   uint64_t maxlen = 0;
   for (uint32_t k = 0; k < n_tmpls; ++k) {
     const uint64_t l = (uint64_t)tmpls[k].prefix_len + 32u + tmpls[k].suffix_len;
     if (l > maxlen) maxlen = l;
   }
-  uint64_t slot = (maxlen + 15) & ~(uint64_t)15;
-  if (slot == 0) slot = 16;
-  const uint64_t msgs_len = cg::tx_msgs_head(n_tmpls, slot);
-  const size_t need_leaf = cg::tx_ws_bytes(n_comps), need_items = sizeof(cg_item) * (n_sigs ? n_sigs : 1),
-               need_msgs = msgs_len ? msgs_len : 16, need_tmpl = sizeof(cg_signable_tmpl) * (n_tmpls ? n_tmpls : 1);
-  if (c->aux2.cap < need_leaf || c->txitems.cap < need_items || c->msgs.cap < need_msgs ||
-      c->tmpls.cap < need_tmpl) {
-    HIP_TRY(hipDeviceSynchronize(), "hipDeviceSynchronize");
-    HIP_TRY(c->aux2.ensure(need_leaf), "hipMalloc(leaf ws)");
-    HIP_TRY(c->txitems.ensure(need_items), "hipMalloc(tx items)");
-    HIP_TRY(c->msgs.ensure(need_msgs), "hipMalloc(spliced messages)");
-    HIP_TRY(c->tmpls.ensure(need_tmpl), "hipMalloc(templates)");
-  }
+  const uint64_t slot = (maxlen + 15) & ~(uint64_t)15;
+  return slot ? slot : 16;
+}
+
+// The launches of cg_verify_transactions(_device) on `s`, inside the caller's open call (the ctx lock
+// held): grows the workspace (waiting for the device), then ids, verify items and the chunked verify.
+static int verify_transactions_locked(cg_ctx* c, const cg_tx* d_txs, uint64_t n_tx, const cg_component* d_comps,
+                                      uint64_t n_comps, const cg_key* d_keys, uint32_t n_keys, const cg_txsig* d_sigs,
+                                      uint64_t n_sigs, const cg_signable_tmpl* tmpls, uint32_t n_tmpls,
+                                      const uint8_t* d_arena, uint64_t arena_len, uint32_t mode, uint8_t* d_ids,
+                                      uint8_t* d_tx_status, uint8_t* d_sig_status, hipStream_t s) {
+  const uint64_t slot = tmpl_slot(tmpls, n_tmpls), msgs_len = cg::tx_msgs_head(n_tmpls, slot);
+  HIP_TRY(ensure_all({{&c->aux2, cg::tx_ws_bytes(n_comps)},
+                      {&c->txitems, sizeof(cg_item) * (n_sigs ? n_sigs : 1)},
+                      {&c->msgs, msgs_len ? msgs_len : 16},
+                      {&c->tmpls, sizeof(cg_signable_tmpl) * (n_tmpls ? n_tmpls : 1)}}),
+          "hipMalloc(transaction workspace)");
   HIP_TRY(ensure_ws(c, n_keys, chunk_of(c, n_sigs), n_sigs), "hipMalloc(workspace)");
-  HIP_TRY(order_in(c, s), "hipStreamWaitEvent");
   if (n_tmpls)
     HIP_TRY(hipMemcpyAsync(c->tmpls.p, tmpls, sizeof(cg_signable_tmpl) * n_tmpls, hipMemcpyHostToDevice, s),
             "H2D templates");
@@ -1285,7 +1285,6 @@ static int verify_transactions_locked(cg_ctx* c, const cg_tx* d_txs, uint64_t n_
                            d_sig_status, s, (const uint8_t*)c->msgs.p, msgs_len),
             "launch_verify");
   }
-  HIP_TRY(order_out(c, s), "hipEventRecord");
   return CG_OK;
 }
 
@@ -1300,17 +1299,49 @@ int cg_verify_transactions_device(cg_ctx* c, const cg_tx* d_txs, uint64_t n_tx, 
   if (n_tmpls && !tmpls) return fail(CG_ERR_ARG, "cg_verify_transactions_device: templates is NULL");
   if (mode > CG_MODE_ISVALID) return fail(CG_ERR_ARG, "cg_verify_transactions_device: bad mode");
   std::lock_guard<std::mutex> g(c->mu);
-  HIP_TRY(hipSetDevice(c->device), "hipSetDevice");
-  hipStream_t s = stream_of(c, hip_stream);
-  return verify_transactions_locked(c, d_txs, n_tx, d_comps, n_comps, d_keys, n_keys, d_sigs, n_sigs, tmpls, n_tmpls,
-                                    d_arena, arena_len, mode, d_ids, d_tx_status, d_sig_status, s);
+  if (const int rc = enter(c, "cg_verify_transactions_device")) return rc;
+  Call call(c, Call::kDevice);
+  HIP_TRY(call.open(hip_stream), "hipStreamWaitEvent");
+  if (const int rc = verify_transactions_locked(c, d_txs, n_tx, d_comps, n_comps, d_keys, n_keys, d_sigs, n_sigs, tmpls,
+                                                n_tmpls, d_arena, arena_len, mode, d_ids, d_tx_status, d_sig_status,
+                                                call.stream()))
+    return rc;
+  HIP_TRY(call.close(), "hipEventRecord");
+  return CG_OK;
 }
 
+// cg_verify_transactions with the arguments checked and the ctx lock held (also a cg_pool slot's call)
 static int verify_transactions_host_locked(cg_ctx* c, const cg_tx* txs, uint64_t n_tx, const cg_component* comps,
                                            uint64_t n_comps, const cg_key* keys, uint32_t n_keys, const cg_txsig* sigs,
                                            uint64_t n_sigs, const cg_signable_tmpl* tmpls, uint32_t n_tmpls,
                                            const uint8_t* arena, uint64_t arena_len, uint32_t mode, uint8_t* ids_out,
-                                           uint8_t* tx_status_out, uint8_t* sig_status_out);
+                                           uint8_t* tx_status_out, uint8_t* sig_status_out) {
+  if (const int rc = enter(c, "cg_verify_transactions")) return rc;
+  hipStream_t s = c->stream;
+  Call call(c, Call::kHost);
+  HIP_TRY(call.open(), "hipStreamWaitEvent");
+  HIP_TRY(stage(c->h_txs, txs, sizeof(cg_tx) * n_tx, s), "H2D txs");
+  HIP_TRY(stage(c->h_comps, comps, sizeof(cg_component) * n_comps, s), "H2D comps");
+  HIP_TRY(stage(c->keys, keys, sizeof(cg_key) * n_keys, s), "H2D keys");
+  HIP_TRY(stage(c->h_sigs, sigs, sizeof(cg_txsig) * n_sigs, s), "H2D sigs");
+  HIP_TRY(stage(c->arena, arena, arena_len, s, arena_room(arena_len)), "H2D arena");
+  HIP_TRY(c->h_ids.ensure(32 * (n_tx ? n_tx : 1)), "hipMalloc(ids)");
+  HIP_TRY(c->h_txst.ensure(n_tx ? n_tx : 1), "hipMalloc(tx status)");
+  HIP_TRY(c->status.ensure(n_sigs ? n_sigs : 1), "hipMalloc(sig status)");
+  if (const int rc = verify_transactions_locked(
+          c, (const cg_tx*)c->h_txs.p, n_tx, (const cg_component*)c->h_comps.p, n_comps, (const cg_key*)c->keys.p, n_keys,
+          (const cg_txsig*)c->h_sigs.p, n_sigs, tmpls, n_tmpls, (const uint8_t*)c->arena.p, arena_len, mode,
+          (uint8_t*)c->h_ids.p, (uint8_t*)c->h_txst.p, (uint8_t*)c->status.p, s))
+    return rc;
+  if (n_tx) {
+    HIP_TRY(hipMemcpyAsync(ids_out, c->h_ids.p, 32 * n_tx, hipMemcpyDeviceToHost, s), "D2H ids");
+    HIP_TRY(hipMemcpyAsync(tx_status_out, c->h_txst.p, n_tx, hipMemcpyDeviceToHost, s), "D2H tx status");
+  }
+  if (n_sigs) HIP_TRY(hipMemcpyAsync(sig_status_out, c->status.p, n_sigs, hipMemcpyDeviceToHost, s), "D2H sig status");
+  HIP_TRY(call.close(), "hipEventRecord");
+  HIP_TRY(hipStreamSynchronize(s), "hipStreamSynchronize");
+  return CG_OK;
+}
 
 int cg_verify_transactions(cg_ctx* c, const cg_tx* txs, uint64_t n_tx, const cg_component* comps, uint64_t n_comps,
                            const cg_key* keys, uint32_t n_keys, const cg_txsig* sigs, uint64_t n_sigs,
@@ -1332,70 +1363,13 @@ int cg_verify_transactions(cg_ctx* c, const cg_tx* txs, uint64_t n_tx, const cg_
                                          arena, arena_len, mode, ids_out, tx_status_out, sig_status_out);
 }
 
-// cg_verify_transactions with the arguments checked and the ctx lock held (also a cg_pool slot's call)
-static int verify_transactions_host_locked(cg_ctx* c, const cg_tx* txs, uint64_t n_tx, const cg_component* comps,
-                                           uint64_t n_comps, const cg_key* keys, uint32_t n_keys, const cg_txsig* sigs,
-                                           uint64_t n_sigs, const cg_signable_tmpl* tmpls, uint32_t n_tmpls,
-                                           const uint8_t* arena, uint64_t arena_len, uint32_t mode, uint8_t* ids_out,
-                                           uint8_t* tx_status_out, uint8_t* sig_status_out) {
-  if (c->fault) return fail(CG_ERR_DEVICE, "cg_verify_transactions: device fault (injected by cg_pool_inject_fault)");
-  HIP_TRY(hipSetDevice(c->device), "hipSetDevice");
-  hipStream_t s = c->stream;
-  HIP_TRY(order_in(c, s), "hipStreamWaitEvent");
-  HIP_TRY(c->h_txs.ensure(sizeof(cg_tx) * (n_tx ? n_tx : 1)), "hipMalloc(txs)");
-  HIP_TRY(c->h_comps.ensure(sizeof(cg_component) * (n_comps ? n_comps : 1)), "hipMalloc(comps)");
-  HIP_TRY(c->keys.ensure(sizeof(cg_key) * (n_keys ? n_keys : 1)), "hipMalloc(keys)");
-  HIP_TRY(c->h_sigs.ensure(sizeof(cg_txsig) * (n_sigs ? n_sigs : 1)), "hipMalloc(sigs)");
-  HIP_TRY(c->arena.ensure(((arena_len + 3) & ~(uint64_t)3) + 16), "hipMalloc(arena)");
-  HIP_TRY(c->h_ids.ensure(32 * (n_tx ? n_tx : 1)), "hipMalloc(ids)");
-  HIP_TRY(c->h_txst.ensure(n_tx ? n_tx : 1), "hipMalloc(tx status)");
-  HIP_TRY(c->status.ensure(n_sigs ? n_sigs : 1), "hipMalloc(sig status)");
-  if (n_tx) HIP_TRY(hipMemcpyAsync(c->h_txs.p, txs, sizeof(cg_tx) * n_tx, hipMemcpyHostToDevice, s), "H2D txs");
-  if (n_comps)
-    HIP_TRY(hipMemcpyAsync(c->h_comps.p, comps, sizeof(cg_component) * n_comps, hipMemcpyHostToDevice, s),
-            "H2D comps");
-  if (n_keys) HIP_TRY(hipMemcpyAsync(c->keys.p, keys, sizeof(cg_key) * n_keys, hipMemcpyHostToDevice, s), "H2D keys");
-  if (n_sigs)
-    HIP_TRY(hipMemcpyAsync(c->h_sigs.p, sigs, sizeof(cg_txsig) * n_sigs, hipMemcpyHostToDevice, s), "H2D sigs");
-  if (arena_len) HIP_TRY(hipMemcpyAsync(c->arena.p, arena, arena_len, hipMemcpyHostToDevice, s), "H2D arena");
-  int rc = verify_transactions_locked(c, (const cg_tx*)c->h_txs.p, n_tx, (const cg_component*)c->h_comps.p, n_comps,
-                                      (const cg_key*)c->keys.p, n_keys, (const cg_txsig*)c->h_sigs.p, n_sigs, tmpls,
-                                      n_tmpls, (const uint8_t*)c->arena.p, arena_len, mode, (uint8_t*)c->h_ids.p,
-                                      (uint8_t*)c->h_txst.p, (uint8_t*)c->status.p, s);
-  if (rc != CG_OK) return rc;
-  if (n_tx) {
-    HIP_TRY(hipMemcpyAsync(ids_out, c->h_ids.p, 32 * n_tx, hipMemcpyDeviceToHost, s), "D2H ids");
-    HIP_TRY(hipMemcpyAsync(tx_status_out, c->h_txst.p, n_tx, hipMemcpyDeviceToHost, s), "D2H tx status");
-  }
-  if (n_sigs) HIP_TRY(hipMemcpyAsync(sig_status_out, c->status.p, n_sigs, hipMemcpyDeviceToHost, s), "D2H sig status");
-  HIP_TRY(hipStreamSynchronize(s), "hipStreamSynchronize");
-  return CG_OK;
-}
-
 // ---------------------------------------------------------------- signatures over known tx ids
-// The spliced-message slot of a template set: the longest prefix || id || suffix, 16-aligned.
-static uint64_t tmpl_slot(const cg_signable_tmpl* tmpls, uint32_t n_tmpls) {
-  uint64_t maxlen = 0;
-  for (uint32_t k = 0; k < n_tmpls; ++k) {
-    const uint64_t l = (uint64_t)tmpls[k].prefix_len + 32u + tmpls[k].suffix_len;
-    if (l > maxlen) maxlen = l;
-  }
-  const uint64_t slot = (maxlen + 15) & ~(uint64_t)15;
-  return slot ? slot : 16;
-}
-
 // Verify items, spliced messages and the template table of n_sigs signatures (waits for the device
 // when a buffer grows).
 static hipError_t ensure_txsig_ws(cg_ctx* c, uint64_t n_sigs, uint32_t n_tmpls, uint64_t slot) {
-  const size_t need_items = sizeof(cg_item) * (n_sigs ? n_sigs : 1),
-               need_msgs = cg::tx_msgs_head(n_tmpls, slot),
-               need_tmpl = sizeof(cg_signable_tmpl) * (n_tmpls ? n_tmpls : 1);
-  if (c->txitems.cap >= need_items && c->msgs.cap >= need_msgs && c->tmpls.cap >= need_tmpl) return hipSuccess;
-  hipError_t e = hipDeviceSynchronize();
-  if (e == hipSuccess) e = c->txitems.ensure(need_items);
-  if (e == hipSuccess) e = c->msgs.ensure(need_msgs);
-  if (e == hipSuccess) e = c->tmpls.ensure(need_tmpl);
-  return e;
+  return ensure_all({{&c->txitems, sizeof(cg_item) * (n_sigs ? n_sigs : 1)},
+                     {&c->msgs, cg::tx_msgs_head(n_tmpls, slot)},
+                     {&c->tmpls, sizeof(cg_signable_tmpl) * (n_tmpls ? n_tmpls : 1)}});
 }
 
 // Templates to the device (midstates + images), then the chunked verify: key tables sized from
@@ -1636,17 +1610,6 @@ struct TxsigFeed {
   }
 };
 
-// At least n events without timing in v.
-static hipError_t ensure_events(std::vector<hipEvent_t>& v, uint64_t n) {
-  while (v.size() < n) {
-    hipEvent_t e;
-    const hipError_t r = hipEventCreateWithFlags(&e, hipEventDisableTiming);
-    if (r != hipSuccess) return r;
-    v.push_back(e);
-  }
-  return hipSuccess;
-}
-
 // ---- per-transaction verdicts (txverdict.hip): the host forms' tables, staged in one buffer
 struct TxvHost {
   const uint32_t* key_class = nullptr;
@@ -1667,13 +1630,6 @@ struct TxvDev {
   cg_tx_verdict* verdicts = nullptr;
   uint8_t* req_status = nullptr;
 };
-static hipError_t ensure_txv_ws(cg_ctx* c, uint64_t n_tx) {
-  const size_t need = cg::tx_verdicts_ws_bytes(n_tx);
-  if (c->txvws.cap >= need) return hipSuccess;
-  hipError_t e = hipDeviceSynchronize();
-  if (e == hipSuccess) e = c->txvws.ensure(need);
-  return e;
-}
 // Carves c->txvio for the tables of `h` (waits for the device when it grows), and the list workspace.
 static hipError_t txv_stage(cg_ctx* c, const TxvHost& h, uint32_t n_keys, TxvDev* d) {
   auto up = [](size_t x) { return (x + 15) & ~(size_t)15; };
@@ -1682,11 +1638,7 @@ static hipError_t txv_stage(cg_ctx* c, const TxvHost& h, uint32_t n_keys, TxvDev
                o_reqs = o_verd + up(sizeof(cg_tx_verdict) * h.n_tx),
                o_class = o_reqs + up(sizeof(uint32_t) * h.n_reqs),
                o_rst = o_class + up(h.key_class ? sizeof(uint32_t) * n_keys : 0), need = o_rst + up(h.n_reqs) + 16;
-  hipError_t e = ensure_txv_ws(c, h.n_tx);
-  if (e == hipSuccess && c->txvio.cap < need) {
-    e = hipDeviceSynchronize();
-    if (e == hipSuccess) e = c->txvio.ensure(need);
-  }
+  const hipError_t e = ensure_all({{&c->txvws, cg::tx_verdicts_ws_bytes(h.n_tx)}, {&c->txvio, need}});
   if (e != hipSuccess) return e;
   uint8_t* b = (uint8_t*)c->txvio.p;
   d->checks = (cg_tx_check*)(b + o_checks);
@@ -1749,8 +1701,7 @@ static int verify_txsig_host_locked(cg_ctx* c, const cg_key* keys, uint32_t n_ke
     if (!keys_fix.empty()) keys = keys_fix.data();
     if (!tmpls_fix.empty()) tmpls = tmpls_fix.data();
   }
-  if (c->fault) return fail(CG_ERR_DEVICE, "cg_verify_tx_signatures: device fault (injected by cg_pool_inject_fault)");
-  HIP_TRY(hipSetDevice(c->device), "hipSetDevice");
+  if (const int rc = enter(c, "cg_verify_tx_signatures")) return rc;
   // chunk bounds (txsig_plan.h); `per`, the largest chunk, sizes the item workspaces
   static const uint64_t first_div = env_u64("CG_TXSIG_FIRST_DIV", cg::kTxsigFirstDiv);
   const std::vector<uint64_t> bounds = cg::txsig_bounds(n_sigs, c->chunk, c->chunk_set, first_div);
@@ -1782,7 +1733,8 @@ static int verify_txsig_host_locked(cg_ctx* c, const cg_key* keys, uint32_t n_ke
   HIP_TRY(tr.begin(nch), "hipEventCreate");
   hipStream_t s = c->stream;
   const uint8_t* dbase = (const uint8_t*)c->arena.p;  // kernels index the arena by absolute offsets
-  HIP_TRY(order_in(c, s), "hipStreamWaitEvent");
+  Call call(c, Call::kHost);
+  HIP_TRY(call.open(), "hipStreamWaitEvent");
   HIP_TRY(hipEventRecord(c->tev[0], s), "hipEventRecord");
   HIP_TRY(hipStreamWaitEvent(c->copy, c->tev[0], 0), "hipStreamWaitEvent");
   TxsigFeed feed(c, tr, bounds);
@@ -1854,7 +1806,7 @@ static int verify_txsig_host_locked(cg_ctx* c, const cg_key* keys, uint32_t n_ke
   if (status_out) HIP_TRY(hipMemcpyAsync(status_out, ds, n_sigs, hipMemcpyDeviceToHost, s), "D2H status");
   if (txv) HIP_TRY(txv_download(*txv, txd, s), "D2H verdicts");
   HIP_TRY(hipEventRecord(c->tev[3], s), "hipEventRecord");
-  HIP_TRY(order_out(c, s), "hipEventRecord");
+  HIP_TRY(call.close(), "hipEventRecord");
   const double h_enq = tr.ms();
   HIP_TRY(hipStreamSynchronize(s), "hipStreamSynchronize");
   tr.report(nch, h_enq);
@@ -1885,35 +1837,30 @@ int cg_verify_tx_signatures_device(cg_ctx* c, const cg_key* d_keys, uint32_t n_k
   if (a != CG_OK) return a;
   if (n_sigs == 0) return CG_OK;
   std::lock_guard<std::mutex> g(c->mu);
-  if (c->fault) return fail(CG_ERR_DEVICE, "cg_verify_tx_signatures_device: device fault (injected)");
-  HIP_TRY(hipSetDevice(c->device), "hipSetDevice");
+  if (const int rc = enter(c, "cg_verify_tx_signatures_device")) return rc;
   const uint64_t slot = tmpl_slot(tmpls, n_tmpls);
   HIP_TRY(ensure_txsig_ws(c, n_sigs, n_tmpls, slot), "hipMalloc(tx signature workspace)");
   HIP_TRY(ensure_ws(c, n_keys, chunk_of(c, n_sigs), n_sigs), "hipMalloc(workspace)");
-  hipStream_t s = stream_of(c, hip_stream);
-  HIP_TRY(order_in(c, s), "hipStreamWaitEvent");
+  Call call(c, Call::kDevice);
+  HIP_TRY(call.open(hip_stream), "hipStreamWaitEvent");
   cg::KeyUses uses;
   uses.sigs = d_sigs;
   uses.n = n_sigs;
   HIP_TRY(launch_txsig(c, d_keys, n_keys, d_ids, n_ids, d_sigs, n_sigs, tmpls, n_tmpls, d_arena, arena_len, mode,
-                       d_status, s, slot, uses, nullptr),
+                       d_status, call.stream(), slot, uses, nullptr),
           "launch_txsig");
-  HIP_TRY(order_out(c, s), "hipEventRecord");
+  HIP_TRY(call.close(), "hipEventRecord");
   return CG_OK;
 }
 
-// cg_verify_tx_signatures_packed_device with the ctx lock held and the device set, up to its last
-// kernel: *s_out is the stream the call runs on (stream_of), order_out is the caller's.
-static int txsig_packed_device_locked(cg_ctx* c, const cg_key* d_keys, uint32_t n_keys, const uint8_t* d_ids,
-                                      uint64_t n_ids, const cg_txsig_packed* d_sigs, uint64_t n_sigs,
-                                      uint64_t sig_bytes_off, uint64_t sig_bytes_len, const cg_signable_tmpl* tmpls,
-                                      uint32_t n_tmpls, const uint8_t* d_arena, uint64_t arena_len, uint32_t mode,
-                                      uint8_t* d_status, void* hip_stream, hipStream_t* s_out) {
-  const uint64_t slot = tmpl_slot(tmpls, n_tmpls);
+// The two halves of a packed device call, with the ctx lock held and the device set: the chunk bounds
+// and the workspace before the call opens, then every launch up to the last chunk's back on `s`.
+static hipError_t txsig_packed_device_ws(cg_ctx* c, uint32_t n_keys, uint64_t n_sigs, uint32_t n_tmpls, uint64_t slot,
+                                         std::vector<uint64_t>& bounds) {
+  if (n_sigs == 0) return hipSuccess;
   // equal chunks rounded to the 256-record blocks whose stream offsets are computed once for the table
   uint64_t per = chunk_of(c, n_sigs);
   per = (per + 255) & ~(uint64_t)255;
-  std::vector<uint64_t> bounds;
   for (uint64_t f = 0; f < n_sigs; f += per) bounds.push_back(f);
   bounds.push_back(n_sigs);
   // CG_DEV_FIRST_PCT=<p> (A/B): a two-chunk call's first chunk p% of the call instead of half; 50 / 60
@@ -1926,12 +1873,20 @@ static int txsig_packed_device_locked(cg_ctx* c, const cg_key* d_keys, uint32_t 
     bounds[1] = std::min<uint64_t>(((n_sigs * first_pct / 100) + 255) & ~(uint64_t)255, n_sigs);
     per = std::max(bounds[1], n_sigs - bounds[1]);
   }
-  HIP_TRY(ensure_txsig_ws(c, n_sigs, n_tmpls, slot), "hipMalloc(tx signature workspace)");
-  HIP_TRY(ensure_ws(c, n_keys, per, n_sigs), "hipMalloc(workspace)");
-  HIP_TRY(c->sig12ws.ensure(cg::tx_sig12_scratch_bytes(n_sigs)), "hipMalloc(signature offsets)");
-  hipStream_t s = stream_of(c, hip_stream);
-  HIP_TRY(order_in(c, s), "hipStreamWaitEvent");
-  HIP_TRY(cg::launch_tx_sig12_bases(d_sigs, 0, n_sigs, 0, (uint64_t*)c->sig12ws.p, s), "launch_tx_sig12_bases");
+  hipError_t e = ensure_txsig_ws(c, n_sigs, n_tmpls, slot);
+  if (e == hipSuccess) e = ensure_ws(c, n_keys, per, n_sigs);
+  if (e == hipSuccess) e = c->sig12ws.ensure(cg::tx_sig12_scratch_bytes(n_sigs));
+  return e;
+}
+static hipError_t launch_txsig_packed_device(cg_ctx* c, const cg_key* d_keys, uint32_t n_keys, const uint8_t* d_ids,
+                                             uint64_t n_ids, const cg_txsig_packed* d_sigs, uint64_t n_sigs,
+                                             uint64_t sig_bytes_off, uint64_t sig_bytes_len,
+                                             const cg_signable_tmpl* tmpls, uint32_t n_tmpls, const uint8_t* d_arena,
+                                             uint64_t arena_len, uint32_t mode, uint8_t* d_status, uint64_t slot,
+                                             const std::vector<uint64_t>& bounds, hipStream_t s) {
+  if (n_sigs == 0) return hipSuccess;
+  const hipError_t e = cg::launch_tx_sig12_bases(d_sigs, 0, n_sigs, 0, (uint64_t*)c->sig12ws.p, s);
+  if (e != hipSuccess) return e;
   cg::KeyUses uses;
   uses.sigs12 = d_sigs;
   uses.n = n_sigs;
@@ -1940,11 +1895,8 @@ static int txsig_packed_device_locked(cg_ctx* c, const cg_key* d_keys, uint32_t 
   p12.sig_region = sig_bytes_off;
   p12.sig_bytes_len = sig_bytes_len;
   p12.d_bases = (const uint64_t*)c->sig12ws.p;
-  *s_out = s;
-  HIP_TRY(launch_txsig(c, d_keys, n_keys, d_ids, n_ids, nullptr, n_sigs, tmpls, n_tmpls, d_arena, arena_len, mode,
-                       d_status, s, slot, uses, nullptr, &bounds, &p12),
-          "launch_txsig");
-  return CG_OK;
+  return launch_txsig(c, d_keys, n_keys, d_ids, n_ids, nullptr, n_sigs, tmpls, n_tmpls, d_arena, arena_len, mode,
+                      d_status, s, slot, uses, nullptr, &bounds, &p12);
 }
 
 int cg_verify_tx_signatures_packed_device(cg_ctx* c, const cg_key* d_keys, uint32_t n_keys, const uint8_t* d_ids,
@@ -1959,14 +1911,16 @@ int cg_verify_tx_signatures_packed_device(cg_ctx* c, const cg_key* d_keys, uint3
     return fail(CG_ERR_ARG, "cg_verify_tx_signatures_packed_device: the signature stream lies outside the arena");
   if (n_sigs == 0) return CG_OK;
   std::lock_guard<std::mutex> g(c->mu);
-  if (c->fault) return fail(CG_ERR_DEVICE, "cg_verify_tx_signatures_packed_device: device fault (injected)");
-  HIP_TRY(hipSetDevice(c->device), "hipSetDevice");
-  hipStream_t s = nullptr;
-  const int rc = txsig_packed_device_locked(c, d_keys, n_keys, d_ids, n_ids, d_sigs, n_sigs, sig_bytes_off,
-                                            sig_bytes_len, tmpls, n_tmpls, d_arena, arena_len, mode, d_status,
-                                            hip_stream, &s);
-  if (rc != CG_OK) return rc;
-  HIP_TRY(order_out(c, s), "hipEventRecord");
+  if (const int rc = enter(c, "cg_verify_tx_signatures_packed_device")) return rc;
+  const uint64_t slot = tmpl_slot(tmpls, n_tmpls);
+  std::vector<uint64_t> bounds;
+  HIP_TRY(txsig_packed_device_ws(c, n_keys, n_sigs, n_tmpls, slot, bounds), "hipMalloc(tx signature workspace)");
+  Call call(c, Call::kDevice);
+  HIP_TRY(call.open(hip_stream), "hipStreamWaitEvent");
+  HIP_TRY(launch_txsig_packed_device(c, d_keys, n_keys, d_ids, n_ids, d_sigs, n_sigs, sig_bytes_off, sig_bytes_len, tmpls,
+                                     n_tmpls, d_arena, arena_len, mode, d_status, slot, bounds, call.stream()),
+          "launch_txsig");
+  HIP_TRY(call.close(), "hipEventRecord");
   return CG_OK;
 }
 
@@ -2038,45 +1992,36 @@ int cg_tx_verdicts_device(cg_ctx* c, const void* d_sig_table, uint32_t sig_strid
   if (a != CG_OK) return a;
   if (n_tx == 0 && n_reqs == 0) return CG_OK;
   std::lock_guard<std::mutex> g(c->mu);
-  if (c->fault) return fail(CG_ERR_DEVICE, "cg_tx_verdicts_device: device fault (injected)");
-  HIP_TRY(hipSetDevice(c->device), "hipSetDevice");
-  HIP_TRY(ensure_txv_ws(c, n_tx), "hipMalloc(verdict workspace)");
-  hipStream_t s = stream_of(c, hip_stream);
-  HIP_TRY(order_in(c, s), "hipStreamWaitEvent");
+  if (const int rc = enter(c, "cg_tx_verdicts_device")) return rc;
+  HIP_TRY(ensure_all({{&c->txvws, cg::tx_verdicts_ws_bytes(n_tx)}}), "hipMalloc(verdict workspace)");
+  Call call(c, Call::kDevice);
+  HIP_TRY(call.open(hip_stream), "hipStreamWaitEvent");
   HIP_TRY(cg::launch_tx_verdicts(d_sig_table, sig_stride, n_sigs, d_status, d_keys, n_keys, d_key_class, d_checks,
                                  (uint32_t)n_tx, d_reqs, n_reqs, d_nodes, n_nodes, d_verdicts, d_req_status,
-                                 c->txvws.p, s),
+                                 c->txvws.p, call.stream()),
           "launch_tx_verdicts");
-  HIP_TRY(order_out(c, s), "hipEventRecord");
+  HIP_TRY(call.close(), "hipEventRecord");
   return CG_OK;
 }
 
 static int tx_verdicts_host_locked(cg_ctx* c, const void* sig_table, uint32_t sig_stride, uint64_t n_sigs,
                                    const uint8_t* status, const cg_key* keys, uint32_t n_keys, const TxvHost& h) {
-  if (c->fault) return fail(CG_ERR_DEVICE, "cg_tx_verdicts: device fault (injected by cg_pool_inject_fault)");
-  HIP_TRY(hipSetDevice(c->device), "hipSetDevice");
+  if (const int rc = enter(c, "cg_tx_verdicts")) return rc;
   TxvDev d;
   HIP_TRY(txv_stage(c, h, n_keys, &d), "hipMalloc(verdict tables)");
-  if (c->h_sigs.cap < (size_t)sig_stride * n_sigs || c->status.cap < n_sigs || c->keys.cap < sizeof(cg_key) * n_keys) {
-    HIP_TRY(hipDeviceSynchronize(), "hipDeviceSynchronize");
-    HIP_TRY(c->h_sigs.ensure((size_t)sig_stride * n_sigs), "hipMalloc(sigs)");
-    HIP_TRY(c->status.ensure(n_sigs), "hipMalloc(status)");
-    HIP_TRY(c->keys.ensure(sizeof(cg_key) * (n_keys ? n_keys : 1)), "hipMalloc(keys)");
-  }
   hipStream_t s = c->stream;
-  HIP_TRY(order_in(c, s), "hipStreamWaitEvent");
-  if (n_sigs) {
-    HIP_TRY(hipMemcpyAsync(c->h_sigs.p, sig_table, (size_t)sig_stride * n_sigs, hipMemcpyHostToDevice, s), "H2D sigs");
-    HIP_TRY(hipMemcpyAsync(c->status.p, status, n_sigs, hipMemcpyHostToDevice, s), "H2D status");
-  }
-  if (n_keys) HIP_TRY(hipMemcpyAsync(c->keys.p, keys, sizeof(cg_key) * n_keys, hipMemcpyHostToDevice, s), "H2D keys");
+  Call call(c, Call::kHost);
+  HIP_TRY(call.open(), "hipStreamWaitEvent");
+  HIP_TRY(stage(c->h_sigs, sig_table, (size_t)sig_stride * n_sigs, s), "H2D sigs");
+  HIP_TRY(stage(c->status, status, n_sigs, s), "H2D status");
+  HIP_TRY(stage(c->keys, keys, sizeof(cg_key) * n_keys, s), "H2D keys");
   HIP_TRY(txv_upload(h, n_keys, d, s), "H2D verdict tables");
   HIP_TRY(cg::launch_tx_verdicts(c->h_sigs.p, sig_stride, n_sigs, (const uint8_t*)c->status.p, (const cg_key*)c->keys.p,
                                  n_keys, d.key_class, d.checks, (uint32_t)h.n_tx, d.reqs, h.n_reqs, d.nodes, h.n_nodes,
                                  d.verdicts, d.req_status, c->txvws.p, s),
           "launch_tx_verdicts");
   HIP_TRY(txv_download(h, d, s), "D2H verdicts");
-  HIP_TRY(order_out(c, s), "hipEventRecord");
+  HIP_TRY(call.close(), "hipEventRecord");
   HIP_TRY(hipStreamSynchronize(s), "hipStreamSynchronize");
   return CG_OK;
 }
@@ -2091,16 +2036,7 @@ int cg_tx_verdicts(cg_ctx* c, const void* sig_table, uint32_t sig_stride, uint64
   if (a == CG_OK) a = txv_reserved("cg_tx_verdicts", checks, n_tx);
   if (a != CG_OK) return a;
   if (n_tx == 0 && n_reqs == 0) return CG_OK;
-  TxvHost h;
-  h.key_class = key_class;
-  h.checks = checks;
-  h.n_tx = n_tx;
-  h.reqs = reqs;
-  h.n_reqs = n_reqs;
-  h.nodes = nodes;
-  h.n_nodes = n_nodes;
-  h.verdicts_out = verdicts_out;
-  h.req_status_out = req_status_out;
+  const TxvHost h{key_class, checks, n_tx, reqs, n_reqs, nodes, n_nodes, verdicts_out, req_status_out};
   std::lock_guard<std::mutex> g(c->mu);
   const int rc = tx_verdicts_host_locked(c, sig_table, sig_stride, n_sigs, status, keys, n_keys, h);
   if (rc != CG_OK) txv_fill_not_run(h);
@@ -2126,25 +2062,23 @@ int cg_verify_required_signatures_packed_device(cg_ctx* c, const cg_key* d_keys,
     return fail(CG_ERR_ARG, "%s: the signature stream lies outside the arena", fn);
   if (n_sigs == 0 && n_tx == 0 && n_reqs == 0) return CG_OK;
   std::lock_guard<std::mutex> g(c->mu);
-  if (c->fault) return fail(CG_ERR_DEVICE, "%s: device fault (injected)", fn);
-  HIP_TRY(hipSetDevice(c->device), "hipSetDevice");
-  HIP_TRY(ensure_txv_ws(c, n_tx), "hipMalloc(verdict workspace)");
-  hipStream_t s = nullptr;
-  if (n_sigs) {
-    const int rc = txsig_packed_device_locked(c, d_keys, n_keys, d_ids, n_ids, d_sigs, n_sigs, sig_bytes_off,
-                                              sig_bytes_len, tmpls, n_tmpls, d_arena, arena_len, mode, d_status,
-                                              hip_stream, &s);
-    if (rc != CG_OK) return rc;
-  } else {
-    s = stream_of(c, hip_stream);
-    HIP_TRY(order_in(c, s), "hipStreamWaitEvent");
-  }
+  if (const int rc = enter(c, fn)) return rc;
+  HIP_TRY(ensure_all({{&c->txvws, cg::tx_verdicts_ws_bytes(n_tx)}}), "hipMalloc(verdict workspace)");
+  const uint64_t slot = tmpl_slot(tmpls, n_tmpls);
+  std::vector<uint64_t> bounds;
+  HIP_TRY(txsig_packed_device_ws(c, n_keys, n_sigs, n_tmpls, slot, bounds), "hipMalloc(tx signature workspace)");
+  Call call(c, Call::kDevice);
+  HIP_TRY(call.open(hip_stream), "hipStreamWaitEvent");
+  hipStream_t s = call.stream();
+  HIP_TRY(launch_txsig_packed_device(c, d_keys, n_keys, d_ids, n_ids, d_sigs, n_sigs, sig_bytes_off, sig_bytes_len, tmpls,
+                                     n_tmpls, d_arena, arena_len, mode, d_status, slot, bounds, s),
+          "launch_txsig");
   // launch_txsig has joined the side streams and run the mode guard on s: the statuses are final there
   HIP_TRY(cg::launch_tx_verdicts(d_sigs, (uint32_t)sizeof(cg_txsig_packed), n_sigs, d_status, d_keys, n_keys,
                                  d_key_class, d_checks, (uint32_t)n_tx, d_reqs, n_reqs, d_nodes, n_nodes, d_verdicts,
                                  d_req_status, c->txvws.p, s),
           "launch_tx_verdicts");
-  HIP_TRY(order_out(c, s), "hipEventRecord");
+  HIP_TRY(call.close(), "hipEventRecord");
   return CG_OK;
 }
 
@@ -2170,16 +2104,7 @@ int cg_verify_required_signatures_packed(cg_ctx* c, const cg_key* keys, uint32_t
   if (sig_bytes_len && !sig_bytes) return fail(CG_ERR_ARG, "%s: sig_bytes is NULL", fn);
   if (n_sigs && status_out) memset(status_out, CG_NOT_RUN, n_sigs);
   if (n_sigs == 0 && n_tx == 0 && n_reqs == 0) return CG_OK;
-  TxvHost h;
-  h.key_class = key_class;
-  h.checks = checks;
-  h.n_tx = n_tx;
-  h.reqs = reqs;
-  h.n_reqs = n_reqs;
-  h.nodes = nodes;
-  h.n_nodes = n_nodes;
-  h.verdicts_out = verdicts_out;
-  h.req_status_out = req_status_out;
+  const TxvHost h{key_class, checks, n_tx, reqs, n_reqs, nodes, n_nodes, verdicts_out, req_status_out};
   std::lock_guard<std::mutex> g(c->mu);
   // without signatures the verify path has nothing to enqueue: the reduction alone
   const int rc = n_sigs ? verify_txsig_host_locked(c, keys, n_keys, ids, n_ids, nullptr, n_sigs, tmpls, n_tmpls, arena,
@@ -2200,16 +2125,13 @@ int cg_verify_filtered_device(cg_ctx* c, const cg_filtered_tx* d_ftxs, uint64_t 
   if (n_ftx && (!d_ftxs || !d_status)) return fail(CG_ERR_ARG, "cg_verify_filtered_device: NULL buffer");
   if (n_ftx == 0) return CG_OK;
   std::lock_guard<std::mutex> g(c->mu);
-  HIP_TRY(hipSetDevice(c->device), "hipSetDevice");
-  if (c->ftxws.cap < cg::ftx_ws_bytes(n_leaves)) {
-    HIP_TRY(hipDeviceSynchronize(), "hipDeviceSynchronize");
-    HIP_TRY(c->ftxws.ensure(cg::ftx_ws_bytes(n_leaves)), "hipMalloc(filtered ws)");
-  }
-  hipStream_t s = stream_of(c, hip_stream);
-  HIP_TRY(order_in(c, s), "hipStreamWaitEvent");
+  if (const int rc = enter(c, "cg_verify_filtered_device")) return rc;
+  HIP_TRY(ensure_all({{&c->ftxws, cg::ftx_ws_bytes(n_leaves)}}), "hipMalloc(filtered ws)");
+  Call call(c, Call::kDevice);
+  HIP_TRY(call.open(hip_stream), "hipStreamWaitEvent");
   HIP_TRY(cg::launch_filtered(d_ftxs, n_ftx, d_nodes, n_nodes, d_leaves, n_leaves, d_arena, arena_len, d_status,
-                              (uint8_t*)c->ftxws.p, s), "launch_filtered");
-  HIP_TRY(order_out(c, s), "hipEventRecord");
+                              (uint8_t*)c->ftxws.p, call.stream()), "launch_filtered");
+  HIP_TRY(call.close(), "hipEventRecord");
   return CG_OK;
 }
 
@@ -2222,26 +2144,21 @@ int cg_verify_filtered(cg_ctx* c, const cg_filtered_tx* ftxs, uint64_t n_ftx, co
     return fail(CG_ERR_ARG, "cg_verify_filtered: NULL table");
   if (n_ftx == 0) return CG_OK;
   std::lock_guard<std::mutex> g(c->mu);
-  HIP_TRY(hipSetDevice(c->device), "hipSetDevice");
+  if (const int rc = enter(c, "cg_verify_filtered")) return rc;
   hipStream_t s = c->stream;
-  HIP_TRY(order_in(c, s), "hipStreamWaitEvent");
-  HIP_TRY(c->h_txs.ensure(sizeof(cg_filtered_tx) * n_ftx), "hipMalloc(filtered txs)");
-  HIP_TRY(c->h_comps.ensure(sizeof(cg_pmt_node) * (n_nodes ? n_nodes : 1)), "hipMalloc(nodes)");
-  HIP_TRY(c->h_sigs.ensure(sizeof(cg_filtered_leaf) * (n_leaves ? n_leaves : 1)), "hipMalloc(leaves)");
-  HIP_TRY(c->arena.ensure(((arena_len + 3) & ~(uint64_t)3) + 16), "hipMalloc(arena)");
+  Call call(c, Call::kHost);
+  HIP_TRY(call.open(), "hipStreamWaitEvent");
+  HIP_TRY(stage(c->h_txs, ftxs, sizeof(cg_filtered_tx) * n_ftx, s), "H2D ftxs");
+  HIP_TRY(stage(c->h_comps, nodes, sizeof(cg_pmt_node) * n_nodes, s), "H2D nodes");
+  HIP_TRY(stage(c->h_sigs, leaves, sizeof(cg_filtered_leaf) * n_leaves, s), "H2D leaves");
+  HIP_TRY(stage(c->arena, arena, arena_len, s, arena_room(arena_len)), "H2D arena");
   HIP_TRY(c->status.ensure(n_ftx), "hipMalloc(status)");
   HIP_TRY(c->ftxws.ensure(cg::ftx_ws_bytes(n_leaves)), "hipMalloc(filtered ws)");
-  HIP_TRY(hipMemcpyAsync(c->h_txs.p, ftxs, sizeof(cg_filtered_tx) * n_ftx, hipMemcpyHostToDevice, s), "H2D ftxs");
-  if (n_nodes)
-    HIP_TRY(hipMemcpyAsync(c->h_comps.p, nodes, sizeof(cg_pmt_node) * n_nodes, hipMemcpyHostToDevice, s), "H2D nodes");
-  if (n_leaves)
-    HIP_TRY(hipMemcpyAsync(c->h_sigs.p, leaves, sizeof(cg_filtered_leaf) * n_leaves, hipMemcpyHostToDevice, s),
-            "H2D leaves");
-  if (arena_len) HIP_TRY(hipMemcpyAsync(c->arena.p, arena, arena_len, hipMemcpyHostToDevice, s), "H2D arena");
   HIP_TRY(cg::launch_filtered((const cg_filtered_tx*)c->h_txs.p, n_ftx, (const cg_pmt_node*)c->h_comps.p, n_nodes,
                               (const cg_filtered_leaf*)c->h_sigs.p, n_leaves, (const uint8_t*)c->arena.p, arena_len,
                               (uint8_t*)c->status.p, (uint8_t*)c->ftxws.p, s), "launch_filtered");
   HIP_TRY(hipMemcpyAsync(status_out, c->status.p, n_ftx, hipMemcpyDeviceToHost, s), "D2H status");
+  HIP_TRY(call.close(), "hipEventRecord");
   HIP_TRY(hipStreamSynchronize(s), "hipStreamSynchronize");
   return CG_OK;
 }
@@ -2455,16 +2372,7 @@ int cg_pool_verify_required_signatures_packed(cg_pool* p, const cg_key* keys, ui
     own.assign(n_sigs, CG_NOT_RUN);
     status_out = own.data();
   }
-  TxvHost h;
-  h.key_class = key_class;
-  h.checks = checks;
-  h.n_tx = n_tx;
-  h.reqs = reqs;
-  h.n_reqs = n_reqs;
-  h.nodes = nodes;
-  h.n_nodes = n_nodes;
-  h.verdicts_out = verdicts_out;
-  h.req_status_out = req_status_out;
+  const TxvHost h{key_class, checks, n_tx, reqs, n_reqs, nodes, n_nodes, verdicts_out, req_status_out};
   // the existing pool call: shards, re-run on a fault; what no slot ran stays CG_NOT_RUN
   const int rc = cg_pool_verify_tx_signatures_packed(p, keys, n_keys, ids, n_ids, sigs, n_sigs, sig_bytes, sig_bytes_len,
                                                      tmpls, n_tmpls, arena, arena_len, mode, status_out, stats);

@@ -292,7 +292,8 @@ int cg_verify_batch(cg_ctx* ctx, const cg_key* keys, uint32_t n_keys, const cg_i
  * hardware queue of its own), which waits for the work already on the caller's stream, and the
  * caller's stream waits for the call's end, so the call is ordered on the caller's stream as if it
  * ran there (a stream created elsewhere can share an in-order hardware queue with the context's
- * side streams: round 6, cordagpu.cpp stream_of).
+ * side streams: round 6, corda_amd/csrc/call_scope.h). A call that fails after it began to enqueue
+ * still makes the caller's stream wait for what it left in flight.
  * The arena of every *_device form (this one and cg_prepare_keys_device, cg_verify_items_device,
  * cg_sha256_batch_device, cg_tx_ids_device, cg_verify_transactions_device,
  * cg_verify_tx_signatures_device, cg_verify_tx_signatures_packed_device, cg_verify_filtered_device):

@@ -5,7 +5,8 @@
     path): every occurrence of a pool item gets the pool item's verdict, and the pool's verdicts
     equal the C oracle's;
   * async device calls on two streams sharing one context (ordered by the context);
-  * cg_pool on one GPU (two contexts on device 0), including a drill fault and its re-run."""
+  * cg_pool on one GPU (two contexts on device 0), including a drill fault and its re-run;
+  * every other device form on a caller's stream, behind two calls the library refuses."""
 import numpy as np
 import pytest
 
@@ -131,3 +132,109 @@ def test_pool_two_contexts_and_drill_fault(pool):
         ep.inject_fault(1, False)
         assert ep.healthy() == [True, True]
         assert np.array_equal(ep.verify(b), ref)
+
+
+def test_device_forms_on_a_caller_stream():
+    """Every device form no other test runs on a caller's stream: cg_prepare_keys_device +
+    cg_verify_items_device, cg_sha256_batch_device, cg_tx_ids_device, cg_verify_transactions_device,
+    cg_verify_tx_signatures_device (24-byte table) and cg_verify_filtered_device, each on a torch side
+    stream with a clone() of its result enqueued on that stream right behind it and no synchronisation
+    in between; every result equals the host form's and the oracle's. chunk_items=1500: a call over the
+    2^12-item pool has three chunks and uses both item workspaces. Before them, two calls the library
+    refuses (CG_ERR_ARG) on the same stream, which must leave the stream and the context usable."""
+    import hashlib
+    import torch
+    import test_filtered
+    from corda_amd import _lib, merkle as M, signable
+    from corda_amd.engine import Engine
+    from oracle import corda as ocorda
+    from tools.workload import wl
+    pool, _, schemes = wl.notary_pool(1 << 12, ed_keys=24, ec_keys=12, seed=515, nthreads=16, sig_group=4)
+    ref = c_oracle.verify_batch(pool, B.MODE_DOVERIFY, 16)
+    assert (ref == B.VALID).any() and (ref == B.INVALID).any()
+    ids, id_idx = wl.pool_ids(pool, len(signable.template(1, 4)[0]))
+    idx = np.random.default_rng(516).permutation(pool.n)
+    tb = wl.tx_sig_stream(pool, schemes, idx, ids, id_idx, nthreads=16)
+    pb = tb.packed()
+    w = wl.tx_pipeline(300, n_keys=37, seed=517, corrupt_permille=80, nthreads=16)
+    ftxs, fwant = test_filtered.random_tearoffs(300)
+    ft, fn, fl, fa = M.pack_filtered(ftxs)
+    msgs = [np.random.default_rng(518).integers(0, 256, n, dtype=np.uint8).tobytes() for n in range(0, 400)]
+    spans, sarena = Engine._spans(msgs)
+
+    dev = torch.device("cuda", 0)
+    up = lambda x: torch.from_numpy(np.ascontiguousarray(x).view(np.uint8)).to(dev)  # noqa: E731
+    out = lambda n: torch.full((n,), 255, dtype=torch.uint8, device=dev)  # noqa: E731
+    L = _lib.lib()
+    got = {}
+    d = {k: up(v) for k, v in dict(
+        keys=pool.keys, items=pool.items, arena=pool.arena, spans=spans, sarena=sarena, txs=w.txs, comps=w.comps,
+        wkeys=w.keys, wsigs=w.sigs, warena=w.arena, tkeys=tb.keys, tids=tb.ids, tsigs=tb.sigs, tarena=tb.arena,
+        psigs=pb.sigs, ft=ft, fn=fn, fl=fl, fa=fa).items()}
+    o = dict(ist=out(pool.n), sha=out(32 * len(msgs)), ids=out(32 * len(w.txs)), idst=out(len(w.txs)),
+             wids=out(32 * len(w.txs)), wtx=out(len(w.txs)), wsig=out(len(w.sigs)), tsig=out(tb.n), psig=out(pb.n),
+             ftx=out(len(ft)))
+    p = {k: v.data_ptr() for k, v in {**d, **o}.items()}
+    s = torch.cuda.Stream(device=dev)
+    st = s.cuda_stream
+    torch.cuda.synchronize()
+    with Engine(0, chunk_items=1500) as eng:
+        with torch.cuda.stream(s):
+            # refused: items before any prepare on this context; a signature stream outside the arena
+            with pytest.raises(_lib.EngineUnavailable, match=r"\(-1\).*not prepared"):
+                eng.verify_items_device(p["keys"], len(pool.keys), p["items"], pool.n, p["arena"], pool.arena.size,
+                                        o["ist"].data_ptr(), stream=st)
+            with pytest.raises(_lib.EngineUnavailable, match=r"\(-1\).*outside the arena"):
+                eng.verify_tx_signatures_packed_device(p["tkeys"], len(pb.keys), p["tids"], pb.n_ids, p["psigs"], pb.n,
+                                                       tb.arena.size - 8, pb.stream.size, pb.tmpls, p["tarena"],
+                                                       tb.arena.size, p["psig"], stream=st)
+            # the good call behind them: exact verdicts
+            eng.verify_tx_signatures_packed_device(p["tkeys"], len(pb.keys), p["tids"], pb.n_ids, p["psigs"], pb.n,
+                                                   pb.arena.size, pb.stream.size, pb.tmpls, p["tarena"], tb.arena.size,
+                                                   p["psig"], stream=st)
+            got["psig"] = o["psig"].clone()
+            eng.prepare_keys_device(p["keys"], len(pool.keys), p["arena"], pool.arena.size, stream=st)
+            eng.verify_items_device(p["keys"], len(pool.keys), p["items"], pool.n, p["arena"], pool.arena.size,
+                                    o["ist"].data_ptr(), stream=st)
+            got["items"] = o["ist"].clone()
+            _lib.check(L.cg_sha256_batch_device(eng._h, p["spans"], len(msgs), p["sarena"], sarena.size - 8, p["sha"], st),
+                       "cg_sha256_batch_device")
+            got["sha"] = o["sha"].clone()
+            _lib.check(L.cg_tx_ids_device(eng._h, p["txs"], len(w.txs), p["comps"], len(w.comps), p["warena"],
+                                          w.arena.size, p["ids"], p["idst"], st), "cg_tx_ids_device")
+            got["ids"], got["idst"] = o["ids"].clone(), o["idst"].clone()
+            eng.verify_transactions_device(p["txs"], len(w.txs), p["comps"], len(w.comps), p["wkeys"], len(w.keys),
+                                           p["wsigs"], len(w.sigs), w.tmpls, p["warena"], w.arena.size, p["wids"],
+                                           p["wtx"], p["wsig"], stream=st)
+            got["wids"], got["wtx"], got["wsig"] = o["wids"].clone(), o["wtx"].clone(), o["wsig"].clone()
+            eng.verify_tx_signatures_device(p["tkeys"], len(tb.keys), p["tids"], tb.n_ids, p["tsigs"], tb.n, tb.tmpls,
+                                            p["tarena"], tb.arena.size, p["tsig"], stream=st)
+            got["tsig"] = o["tsig"].clone()
+            eng.verify_filtered_device(p["ft"], len(ft), p["fn"], len(fn), p["fl"], len(fl), p["fa"], fa.size, p["ftx"],
+                                       stream=st)
+            got["ftx"] = o["ftx"].clone()
+        torch.cuda.synchronize()
+        got = {k: v.cpu().numpy() for k, v in got.items()}
+        # the host forms, on the same context
+        h_items = eng.verify(pool)
+        h_sha = eng.sha256(msgs)
+        h_ids, h_idst = eng.tx_ids(w.txs, w.comps, w.arena)
+        h_wids, h_wtx, h_wsig = eng.verify_transactions(w.txs, w.comps, w.keys, w.sigs, w.tmpls, w.arena)
+        h_tsig = eng.verify_tx_signatures(tb)
+        h_ftx = eng.verify_filtered(ft, fn, fl, fa)
+    for name, host, oracle in (("psig", h_tsig, ref[idx]), ("items", h_items, ref), ("tsig", h_tsig, ref[idx]),
+                               ("ftx", h_ftx, fwant), ("idst", h_idst, np.zeros(len(w.txs), np.uint8)),
+                               ("wtx", h_wtx, np.zeros(len(w.txs), np.uint8)),
+                               ("ids", h_ids.reshape(-1), w.ids.reshape(-1)),
+                               ("wids", h_wids.reshape(-1), w.ids.reshape(-1)),
+                               ("wsig", h_wsig, np.where(w.labels == 0, B.VALID, B.INVALID).astype(np.uint8))):
+        assert np.array_equal(got[name], oracle), f"{name}: {np.count_nonzero(got[name] != oracle)} differ from the oracle"
+        assert np.array_equal(got[name], host), f"{name}: {np.count_nonzero(got[name] != host)} differ from the host form"
+    assert [got["sha"][32 * i:32 * i + 32].tobytes() for i in range(len(msgs))] == h_sha == \
+        [hashlib.sha256(m).digest() for m in msgs]
+    a = w.arena.tobytes()
+    for t in range(0, len(w.txs), 29):  # the generator's ids are the oracle's
+        r = w.txs[t]
+        blobs = [a[c["off"]:c["off"] + c["len"]] for c in w.comps[r["first"]:r["first"] + r["n"]]]
+        assert ocorda.tx_id(blobs[:-1], a[r["salt_off"]:r["salt_off"] + 32], blobs[-1]) == w.ids[t].tobytes()
+    assert np.count_nonzero(w.labels) > 0 and len(np.unique(fwant)) == 3
