@@ -139,7 +139,7 @@ struct cg_ctx : cg::CallState<HipStreams> {
   uint64_t chunk = CG_DEFAULT_CHUNK_ITEMS;  // items per verify chunk (cg_config.chunk_items)
   bool chunk_set = false;                   // the caller chose it (else the host tx-signature path pipelines finer)
   bool fault = false;                       // cg_pool_inject_fault drill: every call fails (enter)
-  cg::Fork fork = {{nullptr, nullptr, nullptr}, nullptr, {nullptr, nullptr}, {nullptr, nullptr, nullptr}, nullptr,
+  cg::Fork fork = {{nullptr, nullptr, nullptr}, nullptr, {nullptr, nullptr, nullptr}, nullptr,
                    {nullptr, nullptr, nullptr}, nullptr};
   std::mutex mu;
   DevBuf keyprep, itemws, keys, items, arena, status, aux0, aux1, aux2;
@@ -180,9 +180,8 @@ struct cg_ctx : cg::CallState<HipStreams> {
   // tear-offs: leaf-hash workspace
   DevBuf ftxws;
   // host-buffer verify: one event per pipeline chunk (seg); timing events for cg_stats (tev)
-  // a second stream on a hardware queue of its own, idle in every default schedule: the
-  // CG_HOST_TRACE marker "tables built" waits there (launch_chunked), and CG_DEV_FRONT_STREAM runs a
-  // device call's second front on it
+  // a second stream on a hardware queue of its own, idle in every schedule: the CG_HOST_TRACE marker
+  // "tables built" waits there (launch_chunked)
   hipStream_t copy2 = nullptr;
   // the exact key-use count's per-thread byte counters (txsig_plan.h), kept across calls so a call
   // does not page-fault 16 fresh arrays in
@@ -202,7 +201,6 @@ struct cg_ctx : cg::CallState<HipStreams> {
   std::vector<hipEvent_t> fbt;  // CG_HOST_TRACE: per chunk, the main stream reaching its front / its back's end
   std::vector<double> fbh;      // host ms at which chunk k's front kernels were enqueued
   bool htrace = false;
-  hipEvent_t fs[2] = {nullptr, nullptr};  // the device forms' front stream (launch_chunked)
   cg::StageTimer timer;  // used when opened with CG_FLAG_STAGE_TIMING
 };
 
@@ -411,8 +409,7 @@ hipError_t ensure_ws(cg_ctx* c, uint32_t n_keys, uint64_t ws_items, uint64_t cal
 
 // The wide pools a call may use: what ensure_ws reserved for it (none if the buffer is short).
 cg::WidePool wide_for(cg_ctx* c, uint32_t n_keys, uint64_t n_items) {
-  static const bool off = env_flag("CG_NO_WIDE_TABLES", false);  // =1: never build wide tables (A/B runs)
-  if (off || c->wide.cap < c->eng->wide_bytes(n_keys, n_items, c->wide_max)) return cg::WidePool{};
+  if (c->wide.cap < c->eng->wide_bytes(n_keys, n_items, c->wide_max)) return cg::WidePool{};
   cg::WidePool p = c->eng->make_wide_pool(c->wide.p, n_keys, n_items, c->wide_max, c->wide_slots);
   if (c->kc_on && p.cap_ed && c->kcache.p && c->kcache.cap >= c->eng->key_cache_bytes(p.slots)) {
     if (c->kc_open) {  // the last call failed between claim and commit: whatever it left on the streams ends first
@@ -446,7 +443,7 @@ hipError_t launch_chunked(cg_ctx* c, const cg_key* d_keys, uint32_t n_keys, cons
   // any chunk is prepared (so they overlap the host copies).
   if (n_items == 0) return hipSuccess;
   const cg::WidePool wp = wide_for(c, n_keys, n_items);
-  hipError_t e = c->eng->launch_keyprep(d_keys, n_keys, d_arena, arena_len, c->keyprep.p, s, &c->fork,
+  hipError_t e = c->eng->launch_keyprep(d_keys, n_keys, d_arena, arena_len, c->keyprep.p, s, c->fork,
                                     uses ? nullptr : d_items, n_items, &wp, uses);
   if (e == hipSuccess) e = rsa_keyprep(c, d_keys, n_keys, d_arena, arena_len, s);
   // the RSA pass over the whole call, after the last chunk's back
@@ -470,11 +467,17 @@ hipError_t launch_chunked(cg_ctx* c, const cg_key* d_keys, uint32_t n_keys, cons
   };
   // chunk k's item workspace: half k % 2 when the buffer holds two (ensure_ws), else the one
   const bool two = nch > 1 && c->itemws.cap >= 2 * item_half_bytes(c, per);
-  auto ws = [&](uint64_t k) { return (void*)((uint8_t*)c->itemws.p + (two ? (k & 1) * item_half_bytes(c, per) : 0)); };
-  auto plan = [&](uint64_t k) {
-    return c->eng->launch_items_plan(d_keys, n_keys, d_items + at(k), cnt(k), d_status + at(k), c->keyprep.p, ws(k), s,
-                                 &c->fork, &wp);
+  const cg::ItemArgs call = {d_keys, n_keys, d_items, n_items, d_arena, arena_len, mode, d_status, c->keyprep.p,
+                             c->itemws.p, c->btab, d_msgs, msgs_len, &wp};
+  auto chunk = [&](uint64_t k) {
+    cg::ItemArgs a = call;
+    a.d_items = d_items + at(k);
+    a.n_items = cnt(k);
+    a.d_status = d_status + at(k);
+    a.d_item_ws = (uint8_t*)c->itemws.p + (two ? (k & 1) * item_half_bytes(c, per) : 0);
+    return a;
   };
+  auto plan = [&](uint64_t k) { return c->eng->launch_items_plan(chunk(k), s, c->fork); };
   // (the device tx-signature forms with both first chunks' items and plans before the table builds,
   // as pre_plan does for the batch forms, measured slower: 388.3 vs 392.1 M sigs/s over 3 pairs,
   // profiles/r06/preplan: chunk 0's Ed25519 ladder then starts earlier but shares the chip with chunk
@@ -488,8 +491,7 @@ hipError_t launch_chunked(cg_ctx* c, const cg_key* d_keys, uint32_t n_keys, cons
       prep_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - p0).count();
       if (w != hipSuccess) return w;
     }
-    return c->eng->launch_items_front(d_keys, n_keys, d_items + at(k), cnt(k), d_arena, arena_len, mode, d_status + at(k),
-                                  c->keyprep.p, ws(k), s, d_msgs, msgs_len, &c->fork, &wp, pre_plan && k < 2);
+    return c->eng->launch_items_front(chunk(k), s, c->fork, pre_plan && k < 2);
   };
   // chunk k + 1's front (plan, hashes, ECDSA prep) before chunk k's back (ladders): the first
   // chunk's wait for the key tables is spent on the next chunk's fronts. Without a prepare hook the
@@ -499,17 +501,8 @@ hipError_t launch_chunked(cg_ctx* c, const cg_key* d_keys, uint32_t n_keys, cons
   if (e == hipSuccess && pre_plan) e = plan(1);
   // The host forms start the table builds now, so that they overlap the first chunk's copies. The
   // device forms have no copy to hide: their builds start after the first chunk's plan
-  // (launch_items_front), whose onesweep look-back otherwise stalls behind the builds (round 6,
-  // device-resident headline: the first plan's last pass 0.2 -> 2.7 ms in some steps,
-  // profiles/r06/bridge timeline). CG_DEV_TABS_FIRST=1: start them now in the device forms too (A/B).
-  static const bool dev_tabs_first = env_flag("CG_DEV_TABS_FIRST", false);
-  if (e == hipSuccess && prepare && (prepare_blocks || dev_tabs_first)) e = c->eng->launch_key_tables(&c->fork, s);
-  // CG_FRONT_AFTER_TABLES=1 (A/B): the first chunk's front waits for every key table, instead of
-  // sharing the chip with the builds (both run at about half speed together:
-  // profiles/r03/env_chains timelines)
-  static const bool after_tables = env_flag("CG_FRONT_AFTER_TABLES", false);
-  if (e == hipSuccess && prepare && after_tables)
-    for (int k = 0; k < 3 && e == hipSuccess; ++k) e = hipStreamWaitEvent(s, c->fork.ready[k], 0);
+  // (launch_items_front), whose onesweep look-back otherwise stalls behind the builds.
+  if (e == hipSuccess && prepare && prepare_blocks) e = c->eng->launch_key_tables(c->fork, s);
   auto back = [&](uint64_t k) {
     if (k == 0 && c->htrace && c->backt[0]) {  // chunk 0's front done; every table family built
       hipEventRecord(c->backt[0], s);
@@ -518,8 +511,7 @@ hipError_t launch_chunked(cg_ctx* c, const cg_key* d_keys, uint32_t n_keys, cons
       hipEventRecord(c->backt[1], t);
     }
     c->fork.mark = c->htrace && 3 * k + 2 < c->fbt.size() ? c->fbt[3 * k + 2] : nullptr;  // before the joins
-    const hipError_t r = c->eng->launch_items_back(d_keys, n_keys, d_items + at(k), cnt(k), d_arena, arena_len,
-                                               d_status + at(k), c->keyprep.p, ws(k), c->btab, s, &c->fork, &wp);
+    const hipError_t r = c->eng->launch_items_back(chunk(k), s, c->fork);
     c->fork.mark = nullptr;
     if (c->htrace && 3 * k + 1 < c->fbt.size()) hipEventRecord(c->fbt[3 * k + 1], s);  // back k ends
     return r;
@@ -528,8 +520,6 @@ hipError_t launch_chunked(cg_ctx* c, const cg_key* d_keys, uint32_t n_keys, cons
     // host copies in the prepare hook block the enqueuing thread: chunk k's back goes in before
     // chunk k + 1's copy, so the device runs chunk k's ladders during it (with chunk k + 1's front
     // first, chunk k's ladders waited for chunk k + 1's copy: profiles/r03/v5 timeline)
-    // (a front stream of its own, chunk k + 1's front beside chunk k's back, measured neutral twice:
-    // +1% in round 4, 315.4 -> 314.1 M sigs/s with the host pool, profiles/r04/fstr; removed in round 5)
     for (uint64_t k = 0; k < nch && e == hipSuccess; ++k) {
       const auto h0 = std::chrono::steady_clock::now();
       e = front(k);
@@ -540,31 +530,6 @@ hipError_t launch_chunked(cg_ctx* c, const cg_key* d_keys, uint32_t n_keys, cons
                 (unsigned long long)k, std::chrono::duration<double, std::milli>(h1 - h0).count(), prep_ms,
                 std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - h1).count());
     }
-    return rsa_pass(e);
-  }
-  // CG_DEV_FRONT_STREAM=1 (A/B, a two-chunk device tx-signature call): chunk 1's items and plan on the
-  // caller's stream right after chunk 0's front, its hashes and ECDSA fronts on a stream of their own
-  // (copy2: a hardware queue of its own, idle in the device forms), so that chunk 0's ladders start
-  // as soon as the key tables are built instead of after chunk 1's hashes; chunk 1's ladders wait for
-  // that front stream. Measured +0.9% (391.2 -> 394.6 M sigs/s, 3 of 3 pairs, profiles/r06/fstream), but
-  // chunk 0's Ed25519 ladder then shares the chip with chunk 1's hashes (12.1 -> 13.3-13.9 ms of ladder
-  // per step), so its launch time no longer measures the kernel: off by default
-  static const bool dev_front_stream = env_flag("CG_DEV_FRONT_STREAM", false);
-  if (e == hipSuccess && dev_front_stream && two && nch == 2 && prepare && !prepare_blocks && c->copy2 &&
-      c->fs[0] && c->fs[1]) {
-    hipStream_t fs = c->copy2;
-    e = front(0);
-    if (e == hipSuccess) e = (*prepare)(1, at(1), cnt(1));
-    if (e == hipSuccess) e = plan(1);
-    if (e == hipSuccess) e = hipEventRecord(c->fs[0], s);
-    if (e == hipSuccess) e = hipStreamWaitEvent(fs, c->fs[0], 0);
-    if (e == hipSuccess)
-      e = c->eng->launch_items_front(d_keys, n_keys, d_items + at(1), cnt(1), d_arena, arena_len, mode,
-                                     d_status + at(1), c->keyprep.p, ws(1), fs, d_msgs, msgs_len, &c->fork, &wp, true);
-    if (e == hipSuccess) e = hipEventRecord(c->fs[1], fs);
-    if (e == hipSuccess) e = back(0);
-    if (e == hipSuccess) e = hipStreamWaitEvent(s, c->fs[1], 0);
-    if (e == hipSuccess) e = back(1);
     return rsa_pass(e);
   }
   if (e == hipSuccess) e = front(0);
@@ -684,17 +649,19 @@ int verify_host_locked(cg_ctx* c, const cg_key* keys, uint32_t n_keys, const cg_
   const cg_item* di = (const cg_item*)c->items.p;
   uint8_t* ds = (uint8_t*)c->status.p;
   const cg::WidePool wp = wide_for(c, n_keys, n_items);
-  HIP_TRY(c->eng->launch_keyprep(dk, n_keys, dbase, arena_len, c->keyprep.p, s, &c->fork, di, n_items, &wp, nullptr),
+  HIP_TRY(c->eng->launch_keyprep(dk, n_keys, dbase, arena_len, c->keyprep.p, s, c->fork, di, n_items, &wp, nullptr),
           "launch_keyprep");
+  cg::ItemArgs a = {dk, n_keys, di, n_items, dbase, arena_len, mode, ds, c->keyprep.p, c->itemws.p, c->btab, nullptr, 0, &wp};
   HIP_TRY(rsa_keyprep(c, dk, n_keys, dbase, arena_len, s), "launch_rsa_keyprep");
   for (uint64_t k = 0; k < nch; ++k) {
     HIP_TRY(copy_missing(have, P.ext[k], arena, dwin, P.win.lo, c->copy), "H2D arena");
     HIP_TRY(hipEventRecord(c->seg[k], c->copy), "hipEventRecord");
     HIP_TRY(hipStreamWaitEvent(s, c->seg[k], 0), "hipStreamWaitEvent");
     if (k == 0) HIP_TRY(hipEventRecord(c->tev[1], s), "hipEventRecord");
-    const uint64_t f = P.first[k], cnt = P.first[k + 1] - f;
-    HIP_TRY(c->eng->launch_items(dk, n_keys, di + f, cnt, dbase, arena_len, mode, ds + f, c->keyprep.p, c->itemws.p,
-                             c->btab, s, nullptr, 0, &c->fork, &wp), "launch_items");
+    a.d_items = di + P.first[k];
+    a.n_items = P.first[k + 1] - P.first[k];
+    a.d_status = ds + P.first[k];
+    HIP_TRY(c->eng->launch_items(a, s, c->fork), "launch_items");
   }
   c->kc_open = false;  // every kernel of the call is enqueued, the wide-table cache's commits among them
   HIP_TRY(rsa_items(c, dk, n_keys, di, n_items, dbase, arena_len, mode, ds, s), "launch_rsa_items");
@@ -813,16 +780,7 @@ int cg_open(cg_ctx** out, const cg_config* cfg) {
   c->kc_on = !(cfg && (cfg->flags & CG_FLAG_NO_KEY_CACHE)) && env_flag("CG_KEY_CACHE", true);
   c->wide_slots_max = (uint32_t)std::min<uint64_t>(env_u64("CG_TEST_WIDE_SLOTS", cg::kKeyWideMax), cg::kKeyWideMax);
   c->kc_bits = (uint32_t)std::min<uint64_t>(env_u64("CG_TEST_KEY_CACHE_BITS", 32), 32);
-  // CG_STREAM_PRIORITY=1 (A/B): the context's stream at the device's highest priority, so its
-  // blocks (the plan sort's decoupled look-back above all) dispatch ahead of the side streams'
-  // table builds
-  static const bool prio = env_flag("CG_STREAM_PRIORITY", false);
-  int lo_pri = 0, hi_pri = 0;
-  hipError_t e = hipSuccess;
-  if (prio && hipDeviceGetStreamPriorityRange(&lo_pri, &hi_pri) == hipSuccess)
-    e = hipStreamCreateWithPriority(&c->stream, hipStreamNonBlocking, hi_pri);
-  else
-    e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
+  hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
   if (e != hipSuccess) {
     delete c;
     return hip_fail(e, "hipStreamCreate");
@@ -832,29 +790,12 @@ int cg_open(cg_ctx** out, const cg_config* cfg) {
   // caller gets with hip_stream = NULL) and the three side streams sit on four distinct queues;
   // a caller stream created elsewhere may share one with a side stream, whose latency-bound table
   // chain (milliseconds) then runs ahead of that caller's hashes (profiles/r02/wide_v2).
-  // CG_MASKED_SIDE_STREAMS=1: side streams with an all-CU mask, which HIP backs with queues of
-  // their own; measured slower (their chains and tables take CU share from the plan sort and the
-  // hashes: gpurun_out/ab_mask), kept for A/B runs.
-  {
-    hipDeviceProp_t prop;
-    const bool masked = env_flag("CG_MASKED_SIDE_STREAMS", false) && hipGetDeviceProperties(&prop, c->device) == hipSuccess &&
-                        prop.multiProcessorCount > 0;
-    std::vector<uint32_t> mask(masked ? (prop.multiProcessorCount + 31) / 32 : 0, 0u);
-    for (int cu = 0; masked && cu < prop.multiProcessorCount; ++cu) mask[cu / 32] |= 1u << (cu % 32);
-    for (int k = 0; k < 3 && e == hipSuccess; ++k) {
-      e = masked ? hipExtStreamCreateWithCUMask(&c->fork.side[k], (uint32_t)mask.size(), mask.data())
-                 : hipStreamCreateWithFlags(&c->fork.side[k], hipStreamNonBlocking);
-    }
-  }
+  for (int k = 0; k < 3 && e == hipSuccess; ++k) e = hipStreamCreateWithFlags(&c->fork.side[k], hipStreamNonBlocking);
   if (e == hipSuccess) e = hipEventCreateWithFlags(&c->fork.start, hipEventDisableTiming);
-  for (int k = 0; k < 2 && e == hipSuccess; ++k)
-    e = hipEventCreateWithFlags(&c->fork.ec_decoded[k], hipEventDisableTiming);
   for (int k = 0; k < 3 && e == hipSuccess; ++k) e = hipEventCreateWithFlags(&c->fork.ready[k], hipEventDisableTiming);
   for (int k = 0; k < 3 && e == hipSuccess; ++k) e = hipEventCreateWithFlags(&c->fork.row0[k], hipEventDisableTiming);
   if (e == hipSuccess) e = hipEventCreateWithFlags(&c->fork.front, hipEventDisableTiming);
   if (e == hipSuccess) e = hipEventCreateWithFlags(&c->fork.planned, hipEventDisableTiming);
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&c->fork.ed_tabs, hipEventDisableTiming);
-  for (int k = 0; k < 3 && e == hipSuccess; ++k) e = hipEventCreateWithFlags(&c->fork.chains[k], hipEventDisableTiming);
   if (e == hipSuccess) e = hipEventCreateWithFlags(&c->fork.ec_front_go, hipEventDisableTiming);
   for (int k = 0; k < 2 && e == hipSuccess; ++k)
     e = hipEventCreateWithFlags(&c->fork.ec_front_done[k], hipEventDisableTiming);
@@ -862,12 +803,11 @@ int cg_open(cg_ctx** out, const cg_config* cfg) {
   // dedicated queue): multiplexed onto the four default queues, the copy stream shared one with a
   // side stream, and the first chunk's bytes landed only after that stream's table builds (the
   // chunk's fronts started right after k_ed_keyprep_tab in every timeline; with
-  // GPU_MAX_HW_QUEUES=8 they started 3 ms earlier: profiles/r03/env_hwq). CG_COPY_QUEUE_SHARED=1:
-  // plain streams (A/B).
+  // GPU_MAX_HW_QUEUES=8 they started 3 ms earlier: profiles/r03/env_hwq). Plain streams only
+  // where the device does not report its CUs.
   {
     hipDeviceProp_t prop;
-    const bool own = !env_flag("CG_COPY_QUEUE_SHARED", false) && hipGetDeviceProperties(&prop, c->device) == hipSuccess &&
-                     prop.multiProcessorCount > 0;
+    const bool own = hipGetDeviceProperties(&prop, c->device) == hipSuccess && prop.multiProcessorCount > 0;
     std::vector<uint32_t> mask(own ? (prop.multiProcessorCount + 31) / 32 : 0, 0u);
     for (int cu = 0; own && cu < prop.multiProcessorCount; ++cu) mask[cu / 32] |= 1u << (cu % 32);
     for (hipStream_t* cs : {&c->copy, &c->copy2})
@@ -879,7 +819,6 @@ int cg_open(cg_ctx** out, const cg_config* cfg) {
   if (e == hipSuccess) e = hipEventCreateWithFlags(&c->done, hipEventDisableTiming);
   if (e == hipSuccess) e = hipEventCreateWithFlags(&c->bridge, hipEventDisableTiming);
   c->bridged = env_flag("CG_STREAM_BRIDGE", true);
-  for (int k = 0; k < 2 && e == hipSuccess; ++k) e = hipEventCreateWithFlags(&c->fs[k], hipEventDisableTiming);
   int var = 0;
   if (e == hipSuccess) e = acquire_tables(c->device, c->stream, tab_budget, &c->btab, &var);
   if (e == hipSuccess) {
@@ -931,9 +870,6 @@ void cg_close(cg_ctx* c) {
   if (c->fork.start) hipEventDestroy(c->fork.start);
   if (c->fork.front) hipEventDestroy(c->fork.front);
   if (c->fork.planned) hipEventDestroy(c->fork.planned);
-  if (c->fork.ed_tabs) hipEventDestroy(c->fork.ed_tabs);
-  for (int k = 0; k < 3; ++k)
-    if (c->fork.chains[k]) hipEventDestroy(c->fork.chains[k]);
   if (c->fork.ec_front_go) hipEventDestroy(c->fork.ec_front_go);
   for (int k = 0; k < 2; ++k)
     if (c->fork.ec_front_done[k]) hipEventDestroy(c->fork.ec_front_done[k]);
@@ -952,15 +888,11 @@ void cg_close(cg_ctx* c) {
     if (c->tev[k]) hipEventDestroy(c->tev[k]);
   if (c->done) hipEventDestroy(c->done);
   if (c->bridge) hipEventDestroy(c->bridge);
-  for (hipEvent_t ev : c->fs)
-    if (ev) hipEventDestroy(ev);
   for (auto* v : {&c->timer.recs, &c->timer.spare})
     for (auto& r : *v) {
       hipEventDestroy(r.a);
       hipEventDestroy(r.b);
     }
-  for (int k = 0; k < 2; ++k)
-    if (c->fork.ec_decoded[k]) hipEventDestroy(c->fork.ec_decoded[k]);
   if (c->stream) hipStreamDestroy(c->stream);
   delete c;
 }
@@ -1077,7 +1009,7 @@ int cg_prepare_keys_device(cg_ctx* c, const cg_key* d_keys, uint32_t n_keys, con
   Call call(c, Call::kDevice);
   HIP_TRY(call.open(hip_stream), "hipStreamWaitEvent");
   hipStream_t s = call.stream();
-  HIP_TRY(c->eng->launch_keyprep(d_keys, n_keys, d_arena, arena_len, c->keyprep.p, s, &c->fork, nullptr, 0, nullptr,
+  HIP_TRY(c->eng->launch_keyprep(d_keys, n_keys, d_arena, arena_len, c->keyprep.p, s, c->fork, nullptr, 0, nullptr,
                                  nullptr), "launch_keyprep");
   HIP_TRY(rsa_keyprep(c, d_keys, n_keys, d_arena, arena_len, s), "launch_rsa_keyprep");
   HIP_TRY(call.close(), "hipEventRecord");
@@ -1102,10 +1034,13 @@ int cg_verify_items_device(cg_ctx* c, const cg_key* d_keys, uint32_t n_keys, con
   HIP_TRY(call.open(hip_stream), "hipStreamWaitEvent");
   hipStream_t s = call.stream();
   const uint64_t per = chunk_of(c, n_items);
+  cg::ItemArgs a = {d_keys, n_keys, d_items, n_items, d_arena, arena_len, mode, d_status, c->keyprep.p, c->itemws.p,
+                    c->btab, nullptr, 0, nullptr};
   for (uint64_t f = 0; f < n_items; f += per) {
-    const uint64_t cnt = per < n_items - f ? per : n_items - f;
-    HIP_TRY(c->eng->launch_items(d_keys, n_keys, d_items + f, cnt, d_arena, arena_len, mode, d_status + f, c->keyprep.p,
-                                 c->itemws.p, c->btab, s, nullptr, 0, &c->fork, nullptr), "launch_items");
+    a.d_items = d_items + f;
+    a.n_items = per < n_items - f ? per : n_items - f;
+    a.d_status = d_status + f;
+    HIP_TRY(c->eng->launch_items(a, s, c->fork), "launch_items");
   }
   HIP_TRY(rsa_items(c, d_keys, n_keys, d_items, n_items, d_arena, arena_len, mode, d_status, s), "launch_rsa_items");
   HIP_TRY(call.close(), "hipEventRecord");
@@ -1863,16 +1798,6 @@ static hipError_t txsig_packed_device_ws(cg_ctx* c, uint32_t n_keys, uint64_t n_
   per = (per + 255) & ~(uint64_t)255;
   for (uint64_t f = 0; f < n_sigs; f += per) bounds.push_back(f);
   bounds.push_back(n_sigs);
-  // CG_DEV_FIRST_PCT=<p> (A/B): a two-chunk call's first chunk p% of the call instead of half; 50 / 60
-  // / 67% measured 391.2 / 392.1 / 392.3 M sigs/s over 3 rounds, within the noise (profiles/r06/firstpct)
-  static const uint64_t first_pct = [] {
-    const uint64_t x = env_u64("CG_DEV_FIRST_PCT", 0);
-    return x >= 10 && x <= 90 ? x : 0ull;
-  }();
-  if (first_pct && bounds.size() == 3) {
-    bounds[1] = std::min<uint64_t>(((n_sigs * first_pct / 100) + 255) & ~(uint64_t)255, n_sigs);
-    per = std::max(bounds[1], n_sigs - bounds[1]);
-  }
   hipError_t e = ensure_txsig_ws(c, n_sigs, n_tmpls, slot);
   if (e == hipSuccess) e = ensure_ws(c, n_keys, per, n_sigs);
   if (e == hipSuccess) e = c->sig12ws.ensure(cg::tx_sig12_scratch_bytes(n_sigs));

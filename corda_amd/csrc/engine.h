@@ -42,10 +42,12 @@ struct WidePool {
 // [2] Ed25519.
 // Key prep fork: side[0] / side[1] build the secp256r1 / secp256k1 keys (decode -> chain -> tab),
 // side[2] the Ed25519 keys; `start` orders them after the main stream's earlier work,
-// ec_decoded[c] / ready[c] are what the item kernels on the main stream wait for.
-// Item stages: the row-0 ladders (keys with few items, keyws.h) run on the side stream that
-// built their class's tables, after `front` (the hashes / ECDSA prep on the main stream), while
-// the main stream runs the full-table ladders; the main stream joins on row0[k]. A few row-0
+// ready[c] is what the ladders on the main stream wait for.
+// Item stages: each curve's ECDSA front runs on its side stream (after its decode there, between
+// ec_front_go and ec_front_done[c]) beside the challenge hashes on the main stream. The row-0
+// ladders (keys with few items, keyws.h) run on the side stream that built their class's tables,
+// after `front` (the hashes on the main stream), while the main stream runs the full-table
+// ladders; the Ed25519 finish follows on side[2]; the main stream joins on row0[k]. A few row-0
 // waves (long: 252 doublings) then overlap the full-table launch instead of trailing it.
 // Per-stage timing (cg_config.flags & CG_FLAG_STAGE_TIMING): a pair of events around each stage's
 // launches, recorded on the stream the stage runs on, so a stage's duration is measured where it
@@ -84,16 +86,15 @@ struct StageTimer {
 };
 #define CG_TIME(fork, stage, stream, launch)                                   \
   do {                                                                          \
-    const int _t = (fork) && (fork)->timer ? (fork)->timer->mark((stage), (stream)) : -1; \
+    const int _t = (fork).timer ? (fork).timer->mark((stage), (stream)) : -1;  \
     launch;                                                                     \
-    if (_t >= 0) (fork)->timer->done(_t, (stream));                            \
+    if (_t >= 0) (fork).timer->done(_t, (stream));                             \
   } while (0)
 
 // Key-table builds deferred by launch_keyprep until the first chunk's plan is sorted (the sort's
 // decoupled look-back stalls when the table builds hold the SIMDs), then enqueued by launch_items.
 struct PendingTabs {
   bool on = false;
-  bool ec_front_side = false;  // this call's ECDSA fronts run on the side streams (launch_items_front)
   const cg_key* keys = nullptr;
   uint32_t n_keys = 0;
   void* keyprep = nullptr;
@@ -107,11 +108,10 @@ struct PendingTabs {
 
 struct Fork {
   hipStream_t side[3];
-  hipEvent_t start, ec_decoded[2], ready[3], front, row0[3];
+  hipEvent_t start, ready[3], front, row0[3];
   StageTimer* timer;  // null unless the ctx was opened with CG_FLAG_STAGE_TIMING
-  hipEvent_t planned = nullptr, ed_tabs = nullptr;  // plan sorted (main); Ed25519 tables built (side[2])
-  hipEvent_t chains[3] = {nullptr, nullptr, nullptr};  // each family's row-base chains done (side[k])
-  // ECDSA fronts on side[k] (CG_EC_FRONT_SIDE): main's plan done / curve k's front done
+  hipEvent_t planned = nullptr;  // plan sorted (main): the deferred table builds fork from it
+  // ECDSA fronts on side[k]: main's plan done / curve k's front done
   hipEvent_t ec_front_go = nullptr, ec_front_done[2] = {nullptr, nullptr};
   mutable PendingTabs pending;
   hipEvent_t mark = nullptr;  // CG_HOST_TRACE: recorded on the main stream before a back's final joins
@@ -120,17 +120,26 @@ struct Fork {
   const std::function<hipError_t()>* mid_front = nullptr;
 };
 
-// Dynamic LDS reserved by each row-base chain workgroup (CG_CHAIN_SPREAD=1: more than half a CU's
-// 160 KB, so no two single-wave chain workgroups share a CU and their latency-bound walks never
-// split one SIMD's issue; 0 otherwise). A/B knob.
-inline uint32_t chain_spread_lds() {
-  static const uint32_t b = [] {
-    const char* v = getenv("CG_CHAIN_SPREAD");
-    return v && v[0] == '1' ? 82u * 1024u : 0u;
-  }();
-  return b;
-}
-
+// What the item stages of one chunk read and write: the call's key table, arena and workspaces, and
+// the chunk's items, status bytes and item workspace. Every field is required but d_msgs / msgs_len
+// (the engine's spliced-message workspace, read by items flagged CG_ITEM_MSG_WS (keyws.h); caller
+// items never carry that flag) and `wide` (null: no key of the call has wide tables).
+struct ItemArgs {
+  const cg_key* d_keys;
+  uint32_t n_keys;
+  const cg_item* d_items;
+  uint64_t n_items;
+  const uint8_t* d_arena;
+  uint64_t arena_len;
+  uint32_t mode;
+  uint8_t* d_status;
+  const void* d_keyprep;
+  void* d_item_ws;
+  const void* d_btab;
+  const uint8_t* d_msgs;
+  uint64_t msgs_len;
+  const WidePool* wide;
+};
 
 // Where the per-key use counts come from when there is no verify-item table yet: a cg_txsig table
 // in HBM (sampled on the device) or exact counts (n_keys u32 in HBM, made by the host).
@@ -162,24 +171,13 @@ struct EngineVariant {
   hipError_t (*init_btab)(void* d_btab, void* d_scratch, hipStream_t stream);
   size_t (*item_ws_bytes)(uint64_t n_items);
   hipError_t (*launch_keyprep)(const cg_key* d_keys, uint32_t n_keys, const uint8_t* d_arena, uint64_t arena_len,
-                               void* d_keyprep, hipStream_t stream, const Fork* fork, const cg_item* d_items,
+                               void* d_keyprep, hipStream_t stream, const Fork& fork, const cg_item* d_items,
                                uint64_t n_items, const WidePool* wide, const KeyUses* src);
-  hipError_t (*launch_key_tables)(const Fork* fork, hipStream_t stream);
-  hipError_t (*launch_items)(const cg_key* d_keys, uint32_t n_keys, const cg_item* d_items, uint64_t n_items,
-                             const uint8_t* d_arena, uint64_t arena_len, uint32_t mode, uint8_t* d_status,
-                             const void* d_keyprep, void* d_item_ws, const void* d_btab, hipStream_t stream,
-                             const uint8_t* d_msgs, uint64_t msgs_len, const Fork* fork, const WidePool* wide);
-  hipError_t (*launch_items_plan)(const cg_key* d_keys, uint32_t n_keys, const cg_item* d_items, uint64_t n_items,
-                                  uint8_t* d_status, const void* d_keyprep, void* d_item_ws, hipStream_t stream,
-                                  const Fork* fork, const WidePool* wide);
-  hipError_t (*launch_items_front)(const cg_key* d_keys, uint32_t n_keys, const cg_item* d_items, uint64_t n_items,
-                                   const uint8_t* d_arena, uint64_t arena_len, uint32_t mode, uint8_t* d_status,
-                                   const void* d_keyprep, void* d_item_ws, hipStream_t stream, const uint8_t* d_msgs,
-                                   uint64_t msgs_len, const Fork* fork, const WidePool* wide, bool planned);
-  hipError_t (*launch_items_back)(const cg_key* d_keys, uint32_t n_keys, const cg_item* d_items, uint64_t n_items,
-                                  const uint8_t* d_arena, uint64_t arena_len, uint8_t* d_status, const void* d_keyprep,
-                                  void* d_item_ws, const void* d_btab, hipStream_t stream, const Fork* fork,
-                                  const WidePool* wide);
+  hipError_t (*launch_key_tables)(const Fork& fork, hipStream_t stream);
+  hipError_t (*launch_items)(const ItemArgs& a, hipStream_t stream, const Fork& fork);
+  hipError_t (*launch_items_plan)(const ItemArgs& a, hipStream_t stream, const Fork& fork);
+  hipError_t (*launch_items_front)(const ItemArgs& a, hipStream_t stream, const Fork& fork, bool planned);
+  hipError_t (*launch_items_back)(const ItemArgs& a, hipStream_t stream, const Fork& fork);
 };
 
 }  // namespace cgt
@@ -188,10 +186,10 @@ namespace cg {
 
 using cgt::EngineVariant;
 using cgt::Fork;
+using cgt::ItemArgs;
 using cgt::PendingTabs;
 using cgt::StageTimer;
 using cgt::WidePool;
-using cgt::chain_spread_lds;
 
 // this build's entry points (verify.hip)
 const EngineVariant& variant();
@@ -212,13 +210,6 @@ WidePool make_wide_pool(void* base, uint32_t n_keys, uint64_t n_items, uint32_t 
 uint32_t wide_slots(uint32_t n_keys, uint64_t n_items, uint32_t max_slots);  // slots such a call may use
 size_t key_cache_bytes(uint32_t slots);  // the wide-table cache's bookkeeping for a pool of `slots` slots
 
-// Enqueue the whole verify pipeline for one batch on `stream`:
-//   key prep (one lane per key) -> per-scheme verify (one lane per item) -> status bytes.
-hipError_t launch_verify(const cg_key* d_keys, uint32_t n_keys, const cg_item* d_items, uint64_t n_items,
-                         const uint8_t* d_arena, uint64_t arena_len, uint32_t mode, uint8_t* d_status,
-                         void* d_keyprep, void* d_item_ws, const void* d_btab, hipStream_t stream,
-                         const uint8_t* d_msgs = nullptr, uint64_t msgs_len = 0, const Fork* fork = nullptr,
-                         const WidePool* wide = nullptr);
 // Constant base-point row table: size and one-time initialisation (per context).
 size_t btab_bytes();
 size_t btab_scratch_bytes();  // temporary scratch of init_btab (free once it has run)
@@ -229,19 +220,13 @@ using cgt::KeyUses;
 // With `d_items` (or `src`), each key's table is sized by the number of items that use it
 // (keyws.h); with neither (cg_prepare_keys_device), every key gets full tables.
 hipError_t launch_keyprep(const cg_key* d_keys, uint32_t n_keys, const uint8_t* d_arena, uint64_t arena_len,
-                          void* d_keyprep, hipStream_t stream, const Fork* fork = nullptr,
-                          const cg_item* d_items = nullptr, uint64_t n_items = 0, const WidePool* wide = nullptr,
-                          const KeyUses* src = nullptr);
+                          void* d_keyprep, hipStream_t stream, const Fork& fork, const cg_item* d_items,
+                          uint64_t n_items, const WidePool* wide, const KeyUses* src);
 // Start the table builds launch_keyprep deferred (no-op if already started): a host-buffer call
 // starts them before it blocks on the first chunk's arena copy, so they overlap that copy.
-hipError_t launch_key_tables(const Fork* fork, hipStream_t stream);
-// `d_msgs` (optional): the engine's spliced-message workspace, read by items flagged
-// CG_ITEM_MSG_WS (keyws.h); caller items never carry that flag.
-hipError_t launch_items(const cg_key* d_keys, uint32_t n_keys, const cg_item* d_items, uint64_t n_items,
-                        const uint8_t* d_arena, uint64_t arena_len, uint32_t mode, uint8_t* d_status,
-                        const void* d_keyprep, void* d_item_ws, const void* d_btab, hipStream_t stream,
-                        const uint8_t* d_msgs = nullptr, uint64_t msgs_len = 0, const Fork* fork = nullptr,
-                        const WidePool* wide = nullptr);
+hipError_t launch_key_tables(const Fork& fork, hipStream_t stream);
+// The item stages of one chunk: launch_items_front, then launch_items_back.
+hipError_t launch_items(const ItemArgs& a, hipStream_t stream, const Fork& fork);
 // launch_items in two halves: the front (status checks, plan sort, challenge hashes, ECDSA prep and
 // s^-1: needs only the decoded keys) and the back (ladders, finish: need the key tables). Between the
 // two a caller with a second item workspace may enqueue the next chunk's front, so the first chunk's
@@ -249,17 +234,9 @@ hipError_t launch_items(const cg_key* d_keys, uint32_t n_keys, const cg_item* d_
 // The front's plan sort can be enqueued on its own first (`planned` = true then skips it in the
 // front): onesweep's decoupled look-back stalls when the table builds hold the SIMDs, so a caller
 // with two chunks sorts both before the first front starts the table builds.
-hipError_t launch_items_plan(const cg_key* d_keys, uint32_t n_keys, const cg_item* d_items, uint64_t n_items,
-                             uint8_t* d_status, const void* d_keyprep, void* d_item_ws, hipStream_t stream,
-                             const Fork* fork, const WidePool* wide);
-hipError_t launch_items_front(const cg_key* d_keys, uint32_t n_keys, const cg_item* d_items, uint64_t n_items,
-                              const uint8_t* d_arena, uint64_t arena_len, uint32_t mode, uint8_t* d_status,
-                              const void* d_keyprep, void* d_item_ws, hipStream_t stream, const uint8_t* d_msgs,
-                              uint64_t msgs_len, const Fork* fork, const WidePool* wide, bool planned);
-hipError_t launch_items_back(const cg_key* d_keys, uint32_t n_keys, const cg_item* d_items, uint64_t n_items,
-                             const uint8_t* d_arena, uint64_t arena_len, uint8_t* d_status, const void* d_keyprep,
-                             void* d_item_ws, const void* d_btab, hipStream_t stream, const Fork* fork,
-                             const WidePool* wide);
+hipError_t launch_items_plan(const ItemArgs& a, hipStream_t stream, const Fork& fork);
+hipError_t launch_items_front(const ItemArgs& a, hipStream_t stream, const Fork& fork, bool planned);
+hipError_t launch_items_back(const ItemArgs& a, hipStream_t stream, const Fork& fork);
 
 // RSA_SHA256 (verify_rsa.hip; radix-independent, used only by contexts opened with CG_FLAG_RSA).
 // Key records for a key table (launch_rsa_keyprep fills them: accepted keys get their Montgomery

@@ -383,7 +383,7 @@ struct EdWideSlot {
   EdWideTab tab;
   ge_p3 bases[EdWideCfg::kRows];
   union {
-    fe zpre[EdWideCfg::kRows][EdWideCfg::kMult];                       // three-pass build
+    fe zpre[EdWideCfg::kRows][EdWideCfg::kMult];                       // sizes the slot (no kernel uses it)
     uint32_t park[EdWideCfg::kRows * EdWideCfg::kMult * ED_PARK_DWORDS];  // row-lane build
   };
 };
@@ -392,10 +392,12 @@ struct EcWideSlot {
   EcAff bases[EC_WIDE_DIGITS];  // 2^{8j} Q, affine (the row builds step by mixed additions)
   Jac jbases[EC_WIDE_DIGITS];   // the chain's Jacobian points
   union {
-    EcWideScratch s[EC_WIDE_ROWS];                                 // three-pass build, the chain
+    EcWideScratch s[EC_WIDE_ROWS];                                 // the chain's batch inversion (s[0])
     uint32_t park[EC_WIDE_ROWS * EC_WIDE_MULT * EC_PARK_DWORDS];   // row-lane build
   };
 };
+// the slot sizes lay out the wide pools and the cache's slot addresses (wide_pool_bytes, wide_pool)
+static_assert(sizeof(EdWideSlot) == 1184768 && sizeof(EcWideSlot) == 766080, "the wide pools' layout is fixed");
 // Slots for a call of n_items over n_keys: no more keys can reach KEY_WIDE_MIN_USES.
 // max_slots: the context's device-memory cap (cordagpu.cpp ensure_ws: ADVICE r3).
 static inline uint32_t wide_cap(uint32_t n_keys, uint64_t n_items, uint32_t max_slots = KEY_WIDE_MAX,
@@ -609,9 +611,9 @@ void ed_launch_finish(const cg_item* d_items, uint64_t n_items, const uint8_t* d
                       uint8_t* d_status, const ItemWs& iw, hipStream_t stream);
 hipError_t ec_upload_constants();
 hipError_t ec_init_const(void* d_btab, void* d_scratch, hipStream_t stream);
-// per curve: decode (records `decoded`: k_ec_prep needs the key status) -> chains; then the tables
+// per curve: decode (k_ec_prep, later on the same stream, needs the key status) -> chains; then the tables
 void ec_launch_keyprep_chains(int curve, const cg_key* d_keys, uint32_t n_keys, const uint8_t* d_arena,
-                              uint64_t arena_len, const KeyWs& w, hipStream_t stream, hipEvent_t decoded);
+                              uint64_t arena_len, const KeyWs& w, hipStream_t stream);
 void ec_launch_keyprep_tabs(int curve, const cg_key* d_keys, uint32_t n_keys, const KeyWs& w, hipStream_t stream,
                             bool full, bool wide);
 void ec_launch_front(int curve, const cg_item* d_items, uint64_t n_items, const uint8_t* d_arena,
@@ -621,8 +623,5 @@ void ec_launch_ladder(int curve, bool full, const cg_item* d_items, uint64_t n_i
                       const KeyWs& w, const ItemWs& iw, const void* d_btab, hipStream_t stream);
 void ec_launch_ladder_wide(int curve, const cg_item* d_items, uint64_t n_items, uint8_t* d_status, const KeyWs& w,
                            const ItemWs& iw, const void* d_btab, hipStream_t stream);
-// both curves' wide ladders in one launch (verify_ec.hip k_ec_ladder_wide2)
-void ec_launch_ladder_wide_merged(const cg_item* d_items, uint64_t n_items, uint8_t* d_status, const KeyWs& w,
-                                  const ItemWs& iw, const void* d_btab, hipStream_t stream);
 
 }  // namespace cg

@@ -334,59 +334,33 @@ hipError_t init_btab(void* d_btab, void* d_scratch, hipStream_t stream) {
 // The deferred table builds, forked from `stream` at this point: Ed25519 first (its ladder runs
 // first), the two curves after it (their ladders run after the Ed25519 ladder and finish); per
 // family the wide tables, then the full / row-0 ones.
-static hipError_t launch_pending_tabs(const Fork* fork, hipStream_t stream) {
-  PendingTabs& p = fork->pending;
+static hipError_t launch_pending_tabs(const Fork& fork, hipStream_t stream) {
+  PendingTabs& p = fork.pending;
   if (!p.on) return hipSuccess;
   p.on = false;
   const KeyWs w = key_ws(p.keyprep, p.n_keys, &p.wide);
-  hipError_t e = hipEventRecord(fork->planned, stream);
-  if (e == hipSuccess) e = hipStreamWaitEvent(fork->side[2], fork->planned, 0);
+  hipError_t e = hipEventRecord(fork.planned, stream);
   if (e != hipSuccess) return e;
-  // every family's row builds after ALL the row-base chains: a chain is one lane per key (a few
-  // dozen waves, latency-bound), and beside another family's row builds it ran 4x slower (r1: 5.6
-  // instead of 1.3 ms, then its rows after it: profiles/r03/env_copyq timeline). CG_CHAINS_FIRST=0:
-  // each family's builds right after its own chains (A/B). Round 4: with the chains' raised issue
-  // priority (keyws.h chain_prio) the builds no longer slow them, and each family's builds start
-  // as soon as its own chains end: CG_CHAINS_FIRST=1 restores the wait for all (3 x 3 runs each:
-  // chunk 0's front done 0.5-0.8 ms earlier, ~+2% whole-node, profiles/r04/phase1)
-  static const bool chains_first = [] {
-    const char* v = getenv("CG_CHAINS_FIRST");
-    return v && v[0] == '1';
-  }();
-  for (int k = 0; k < 3 && e == hipSuccess && chains_first; ++k)
-    for (int q = 0; q < 3 && e == hipSuccess; ++q)
-      if (q != k && fork->chains[q]) e = hipStreamWaitEvent(fork->side[k], fork->chains[q], 0);
-  if (e != hipSuccess) return e;
-  ed_launch_keyprep_tabs(p.keys, p.n_keys, w, fork->side[2], false, true);
-  e = hipEventRecord(fork->ed_tabs, fork->side[2]);
-  // then the full / row-0 tables (usually few keys: launched ahead of the wide builds, their
-  // near-empty grids queued behind the challenge hashes, which hold every SIMD, and stalled the
-  // wide builds behind them by ~1.8 ms per call: profiles/r02/sha_v2/timeline_step.txt)
-  if (p.need_full[2]) ed_launch_keyprep_tabs(p.keys, p.n_keys, w, fork->side[2], true, false);
-  if (e == hipSuccess) e = hipEventRecord(fork->ready[2], fork->side[2]);
-  // the curves' wide builds right after their own row-base chains, beside the Ed25519 builds, so
-  // that they are done before the first chunk's fronts (after the Ed25519 builds, they ran 5.8 ->
-  // 9.9 ms into the step and slowed the first chunk's challenge hashes 2.4x: profiles/r03/v8
-  // timeline); CG_TABS_CONCURRENT=0 (A/B): after the Ed25519 builds
-  static const bool concurrent = [] {
-    const char* v = getenv("CG_TABS_CONCURRENT");
-    return !(v && v[0] == '0');
-  }();
-  for (int k = 0; k < 2 && e == hipSuccess; ++k) {
-    e = hipStreamWaitEvent(fork->side[k], fork->planned, 0);
-    if (e == hipSuccess && !concurrent) e = hipStreamWaitEvent(fork->side[k], fork->ed_tabs, 0);
-    if (e != hipSuccess) break;
-    ec_launch_keyprep_tabs(k == 0 ? CG_CURVE_R1 : CG_CURVE_K1, p.keys, p.n_keys, w, fork->side[k], false, true);
-    if (p.need_full[k])
-      ec_launch_keyprep_tabs(k == 0 ? CG_CURVE_R1 : CG_CURVE_K1, p.keys, p.n_keys, w, fork->side[k], true, false);
-    e = hipEventRecord(fork->ready[k], fork->side[k]);
+  // Each family's builds follow its own row-base chains on its side stream and wait for no other
+  // family: the chains' raised issue priority (keyws.h chain_prio) keeps the builds from slowing
+  // them, and the curves' builds beside the Ed25519 ones are done before the first chunk's fronts.
+  // Per family the wide builds go first: the full / row-0 grids are near-empty and, launched ahead,
+  // queue behind the challenge hashes and stall the wide builds behind them.
+  for (int k : {2, 0, 1}) {
+    e = hipStreamWaitEvent(fork.side[k], fork.planned, 0);
+    if (e != hipSuccess) return e;
+    for (int full = 0; full < 2; ++full) {
+      if (full && !p.need_full[k]) continue;
+      if (k == 2) ed_launch_keyprep_tabs(p.keys, p.n_keys, w, fork.side[2], full, !full);
+      else ec_launch_keyprep_tabs(k == 0 ? CG_CURVE_R1 : CG_CURVE_K1, p.keys, p.n_keys, w, fork.side[k], full, !full);
+    }
+    e = hipEventRecord(fork.ready[k], fork.side[k]);
+    if (e != hipSuccess) return e;
   }
   return e;
 }
 
-hipError_t launch_key_tables(const Fork* fork, hipStream_t stream) {
-  return fork ? launch_pending_tabs(fork, stream) : hipSuccess;
-}
+hipError_t launch_key_tables(const Fork& fork, hipStream_t stream) { return launch_pending_tabs(fork, stream); }
 
 // k_key_classify's outcome from the host counts: does any key of family f (0 r1, 1 k1, 2 Ed25519)
 // end in row-0 or full-table mode? Mirrors the kernel (a counted key has u >= 1; wide when u >=
@@ -410,12 +384,11 @@ static void families_needing_full(const KeyUses& src, uint32_t n_keys, const Key
 }
 
 hipError_t launch_keyprep(const cg_key* d_keys, uint32_t n_keys, const uint8_t* d_arena, uint64_t arena_len,
-                          void* d_keyprep, hipStream_t stream, const Fork* fork, const cg_item* d_items,
+                          void* d_keyprep, hipStream_t stream, const Fork& fork, const cg_item* d_items,
                           uint64_t n_items, const WidePool* wide, const KeyUses* src) {
-  if (fork) {  // a call with no keys must not inherit the previous call's skip (k_mode_guard reads it)
-    fork->pending.skip_mask = 0;
-    for (int f = 0; f < 3; ++f) fork->pending.need_full[f] = true;
-  }
+  // a call with no keys must not inherit the previous call's skip (k_mode_guard reads it)
+  fork.pending.skip_mask = 0;
+  for (int f = 0; f < 3; ++f) fork.pending.need_full[f] = true;
   if (n_keys == 0) return hipSuccess;
   const bool counted = d_items || src;  // tables sized by the call's key uses
   if (!d_items && src) n_items = src->n;
@@ -436,34 +409,22 @@ hipError_t launch_keyprep(const cg_key* d_keys, uint32_t n_keys, const uint8_t* 
   else if (src && src->sigs12 && src->n)
     hipLaunchKernelGGL(k_key_uses_txsig<cg_txsig_packed>, dim3((unsigned)((src->n + 255) / 256)), dim3(256), 0,
                        stream, src->sigs12, src->n, n_keys, w.uses, w.seen);
-  static const bool serial = [] {  // CG_SERIAL_KEYPREP=1: key prep on the caller's stream (A/B runs)
-    const char* v = getenv("CG_SERIAL_KEYPREP");
-    return v && v[0] == '1';
-  }();
-  static const bool skip_full = [] {  // CG_SKIP_EMPTY_TABS=0: always launch the row-0 / full builds (A/B)
-    const char* v = getenv("CG_SKIP_EMPTY_TABS");
-    return !(v && v[0] == '0');
-  }();
   // every mode's builds and ladders unless this call's host counts prove a family has no row-0 /
   // quarter / full key; the classification checks that proof on the device (k_mode_guard)
   uint32_t skip_mask = 0;
-  if (fork) {
-    for (int f = 0; f < 3; ++f) fork->pending.need_full[f] = true;
-    if (skip_full && !serial && !d_items && src && src->counts && src->host_counts && src->host_keys)
-      families_needing_full(*src, n_keys, w, fork->pending.need_full);
-    // CG_TEST_SKIP_FAMILIES=<mask> (tests only): skip those families' row-0 / quarter / full work as
-    // if the host counts had proved it unneeded, so that the device check can be seen to catch it
-    static const uint32_t test_skip = [] {
-      const char* v = getenv("CG_TEST_SKIP_FAMILIES");
-      return v ? (uint32_t)strtoul(v, nullptr, 0) & 7u : 0u;
-    }();
-    for (int f = 0; f < 3; ++f) {
-      // serial key prep builds every table, so a test skip there would only mark good items NOT_RUN
-      if (!serial && ((test_skip >> f) & 1u)) fork->pending.need_full[f] = false;
-      if (!fork->pending.need_full[f]) skip_mask |= 1u << f;
-    }
-    fork->pending.skip_mask = skip_mask;
+  if (!d_items && src && src->counts && src->host_counts && src->host_keys)
+    families_needing_full(*src, n_keys, w, fork.pending.need_full);
+  // CG_TEST_SKIP_FAMILIES=<mask> (tests only): skip those families' row-0 / quarter / full work as
+  // if the host counts had proved it unneeded, so that the device check can be seen to catch it
+  static const uint32_t test_skip = [] {
+    const char* v = getenv("CG_TEST_SKIP_FAMILIES");
+    return v ? (uint32_t)strtoul(v, nullptr, 0) & 7u : 0u;
+  }();
+  for (int f = 0; f < 3; ++f) {
+    if ((test_skip >> f) & 1u) fork.pending.need_full[f] = false;
+    if (!fork.pending.need_full[f]) skip_mask |= 1u << f;
   }
+  fork.pending.skip_mask = skip_mask;
   // the wide-table cache (key_cache.h): its index before the classification probes it, the claim
   // pass after; all on this stream, ahead of the fork
   if (w.kc.on()) hipLaunchKernelGGL(k_kc_begin, dim3(2), dim3(KC_BLOCK), 0, stream, w.kc);
@@ -473,43 +434,21 @@ hipError_t launch_keyprep(const cg_key* d_keys, uint32_t n_keys, const uint8_t* 
   if (w.kc.on())
     hipLaunchKernelGGL(k_kc_claim, dim3(2), dim3(KC_BLOCK), 0, stream, d_keys, n_keys, d_arena, arena_len, w.wide_idx,
                        w.wide, w.wide_count, w.full, w.full_count, w.row0, skip_mask, w.kc);
-  if (!fork || serial) {
-    if (fork) {  // the item stages still wait for these events
-      fork->pending.on = false;
-    }
-    ed_launch_key_abyte(d_keys, n_keys, d_arena, arena_len, w, stream);
-    for (int curve : {CG_CURVE_R1, CG_CURVE_K1}) {
-      ec_launch_keyprep_chains(curve, d_keys, n_keys, d_arena, arena_len, w, stream, nullptr);
-      ec_launch_keyprep_tabs(curve, d_keys, n_keys, w, stream, true, true);
-    }
-    ed_launch_keyprep_chains(d_keys, n_keys, d_arena, arena_len, w, stream);
-    ed_launch_keyprep_tabs(d_keys, n_keys, w, stream, true, true);
-    if (fork) {
-      hipError_t e = hipSuccess;
-      for (int k = 0; k < 2 && e == hipSuccess; ++k) e = hipEventRecord(fork->ec_decoded[k], stream);
-      for (int k = 0; k < 3 && e == hipSuccess; ++k) e = hipEventRecord(fork->ready[k], stream);
-      if (e != hipSuccess) return e;
-    }
-    return hipGetLastError();
-  }
-  hipError_t e = hipEventRecord(fork->start, stream);
-  for (int k = 0; k < 3 && e == hipSuccess; ++k) e = hipStreamWaitEvent(fork->side[k], fork->start, 0);
+  hipError_t e = hipEventRecord(fork.start, stream);
+  for (int k = 0; k < 3 && e == hipSuccess; ++k) e = hipStreamWaitEvent(fork.side[k], fork.start, 0);
   if (e != hipSuccess) return e;
   // now: decodes and row-base chains (few waves, latency-bound)
-  ec_launch_keyprep_chains(CG_CURVE_R1, d_keys, n_keys, d_arena, arena_len, w, fork->side[0], fork->ec_decoded[0]);
-  ec_launch_keyprep_chains(CG_CURVE_K1, d_keys, n_keys, d_arena, arena_len, w, fork->side[1], fork->ec_decoded[1]);
-  ed_launch_keyprep_chains(d_keys, n_keys, d_arena, arena_len, w, fork->side[2]);
-  for (int k = 0; k < 3 && e == hipSuccess; ++k)
-    if (fork->chains[k]) e = hipEventRecord(fork->chains[k], fork->side[k]);
-  if (e != hipSuccess) return e;
+  ec_launch_keyprep_chains(CG_CURVE_R1, d_keys, n_keys, d_arena, arena_len, w, fork.side[0]);
+  ec_launch_keyprep_chains(CG_CURVE_K1, d_keys, n_keys, d_arena, arena_len, w, fork.side[1]);
+  ed_launch_keyprep_chains(d_keys, n_keys, d_arena, arena_len, w, fork.side[2]);
   // the tables (the wide ones hold every SIMD for milliseconds), wide first, then full / row 0:
   // after the first chunk's plan sort when items follow (its decoupled look-back stalls behind
   // them), else now
-  fork->pending.on = true;
-  fork->pending.keys = d_keys;
-  fork->pending.n_keys = n_keys;
-  fork->pending.keyprep = d_keyprep;
-  fork->pending.wide = counted && wide ? *wide : WidePool{};
+  fork.pending.on = true;
+  fork.pending.keys = d_keys;
+  fork.pending.n_keys = n_keys;
+  fork.pending.keyprep = d_keyprep;
+  fork.pending.wide = counted && wide ? *wide : WidePool{};
   if (!counted) e = launch_pending_tabs(fork, stream);
   if (e != hipSuccess) return e;
   // the only key work on the main stream: Abyte for k_ed_hash (no decode)
@@ -517,203 +456,114 @@ hipError_t launch_keyprep(const cg_key* d_keys, uint32_t n_keys, const uint8_t* 
   return hipGetLastError();
 }
 
-hipError_t launch_items_plan(const cg_key* d_keys, uint32_t n_keys, const cg_item* d_items, uint64_t n_items,
-                             uint8_t* d_status, const void* d_keyprep, void* d_item_ws, hipStream_t stream,
-                             const Fork* fork, const WidePool* wide) {
-  if (n_items == 0) return hipSuccess;
+hipError_t launch_items_plan(const ItemArgs& a, hipStream_t stream, const Fork& fork) {
+  if (a.n_items == 0) return hipSuccess;
   const uint32_t B = 256;
-  const uint64_t grid = (n_items + B - 1) / B;
-  const KeyWs w = key_ws((void*)d_keyprep, n_keys, wide);
-  const ItemWs iw = item_ws(d_item_ws, n_items);
-  hipLaunchKernelGGL(k_misc_status, dim3((unsigned)grid), dim3(B), 0, stream, d_items, n_items, d_keys, n_keys,
-                     d_status);
+  const uint64_t grid = (a.n_items + B - 1) / B;
+  const KeyWs w = key_ws((void*)a.d_keyprep, a.n_keys, a.wide);
+  const ItemWs iw = item_ws(a.d_item_ws, a.n_items);
+  hipLaunchKernelGGL(k_misc_status, dim3((unsigned)grid), dim3(B), 0, stream, a.d_items, a.n_items, a.d_keys,
+                     a.n_keys, a.d_status);
   // plan: items sorted by (scheme class, key) (plan_sort.hip)
   hipError_t e = hipSuccess;
-  CG_TIME(fork, CG_STAGE_PLAN, stream,
-          e = launch_plan(d_items, n_items, d_keys, n_keys, w, iw,
-                          stream));
+  CG_TIME(fork, CG_STAGE_PLAN, stream, e = launch_plan(a.d_items, a.n_items, a.d_keys, a.n_keys, w, iw, stream));
   return e;
 }
 
-hipError_t launch_items_front(const cg_key* d_keys, uint32_t n_keys, const cg_item* d_items, uint64_t n_items,
-                              const uint8_t* d_arena, uint64_t arena_len, uint32_t mode, uint8_t* d_status,
-                              const void* d_keyprep, void* d_item_ws, hipStream_t stream, const uint8_t* d_msgs,
-                              uint64_t msgs_len, const Fork* fork, const WidePool* wide, bool planned) {
-  if (n_items == 0) return hipSuccess;
-  const KeyWs w = key_ws((void*)d_keyprep, n_keys, wide);
-  const ItemWs iw = item_ws(d_item_ws, n_items);
+hipError_t launch_items_front(const ItemArgs& a, hipStream_t stream, const Fork& fork, bool planned) {
+  if (a.n_items == 0) return hipSuccess;
+  const KeyWs w = key_ws((void*)a.d_keyprep, a.n_keys, a.wide);
+  const ItemWs iw = item_ws(a.d_item_ws, a.n_items);
   hipError_t e = hipSuccess;
-  if (!planned)
-    e = launch_items_plan(d_keys, n_keys, d_items, n_items, d_status, d_keyprep, d_item_ws, stream, fork, wide);
-  if (e == hipSuccess && fork) e = launch_pending_tabs(fork, stream);  // the first front starts the table builds
-  if (e == hipSuccess && fork && fork->mid_front) e = (*fork->mid_front)();  // (the hook clears itself)
+  if (!planned) e = launch_items_plan(a, stream, fork);
+  if (e == hipSuccess) e = launch_pending_tabs(fork, stream);  // the first front starts the table builds
+  if (e == hipSuccess && fork.mid_front) e = (*fork.mid_front)();  // (the hook clears itself)
   if (e != hipSuccess) return e;
-  // fronts: Ed25519 challenges (need only Abyte), ECDSA prep + s^-1 per curve (need the decoded key).
-  // CG_EC_FRONT_SIDE: each curve's front on its side stream beside the challenge hashes (its
-  // s^-1 batches leave ~1 wave per SIMD: latency-bound alone), joined before that curve's ladders.
-  // The side stream waits for everything enqueued on `stream` so far: this chunk's plan, and the
-  // ladders of the chunk two back, which read the item workspace this front writes.
-  // Round 4 default (with CG_ED_FINISH_SIDE): 282 / 287 / 282 -> 299 / 298 / 302 M sigs/s over three
-  // interleaved runs (profiles/r04/side); =0 keeps them on `stream`.
-  static const bool ec_side = [] {
-    const char* v = getenv("CG_EC_FRONT_SIDE");
-    return !(v && v[0] == '0');
-  }();
-  if (fork && ec_side && fork->ec_front_go) {
-    e = hipEventRecord(fork->ec_front_go, stream);
-    for (int k = 0; k < 2 && e == hipSuccess; ++k) {
-      const int curve = k == 0 ? CG_CURVE_R1 : CG_CURVE_K1;
-      e = hipStreamWaitEvent(fork->side[k], fork->ec_front_go, 0);
-      if (e != hipSuccess) break;
-      CG_TIME(fork, k == 0 ? CG_STAGE_R1_FRONT : CG_STAGE_K1_FRONT, fork->side[k],
-              ec_launch_front(curve, d_items, n_items, d_arena, arena_len, mode, d_status, w, d_msgs, msgs_len, iw,
-                              fork->side[k]));
-      e = hipEventRecord(fork->ec_front_done[k], fork->side[k]);
-    }
-    if (e != hipSuccess) return e;
-    fork->pending.ec_front_side = true;
-    CG_TIME(fork, CG_STAGE_ED_HASH, stream,
-            ed_launch_front(d_items, n_items, d_arena, arena_len, mode, d_status, w, d_msgs, msgs_len, iw, stream));
-    return hipGetLastError();
-  }
-  if (fork) fork->pending.ec_front_side = false;
-  CG_TIME(fork, CG_STAGE_ED_HASH, stream,
-          ed_launch_front(d_items, n_items, d_arena, arena_len, mode, d_status, w, d_msgs, msgs_len, iw, stream));
-  if (fork) hipStreamWaitEvent(stream, fork->ec_decoded[0], 0);
-  CG_TIME(fork, CG_STAGE_R1_FRONT, stream,
-          ec_launch_front(CG_CURVE_R1, d_items, n_items, d_arena, arena_len, mode, d_status, w, d_msgs, msgs_len, iw,
-                          stream));
-  if (fork) hipStreamWaitEvent(stream, fork->ec_decoded[1], 0);
-  CG_TIME(fork, CG_STAGE_K1_FRONT, stream,
-          ec_launch_front(CG_CURVE_K1, d_items, n_items, d_arena, arena_len, mode, d_status, w, d_msgs, msgs_len, iw,
-                          stream));
-  return hipGetLastError();
-}
-
-hipError_t launch_items_back(const cg_key* d_keys, uint32_t n_keys, const cg_item* d_items, uint64_t n_items,
-                             const uint8_t* d_arena, uint64_t arena_len, uint8_t* d_status, const void* d_keyprep,
-                             void* d_item_ws, const void* d_btab, hipStream_t stream, const Fork* fork,
-                             const WidePool* wide) {
-  if (n_items == 0) return hipSuccess;
-  (void)d_keys;
-  const KeyWs w = key_ws((void*)d_keyprep, n_keys, wide);
-  const ItemWs iw = item_ws(d_item_ws, n_items);
-  hipError_t e = hipSuccess;
-  // row-0 ladders: on the side streams (after their tables) when forked, else first on `stream`.
-  // The full-table ladders stay on `stream`: on a side stream (round 3, for a handful of items per
-  // chunk) a persistent full-GPU grid there held every slot while the main stream's next fronts
-  // waited (Zipf keys: 125 -> 56 M sigs/s, profiles/r03/v12 vs v9); the stray full-table launch it
-  // was meant to hide is gone with the biased count estimate.
-  if (fork) {
-    e = hipEventRecord(fork->front, stream);
-    for (int k = 0; k < 3 && e == hipSuccess; ++k) e = hipStreamWaitEvent(fork->side[k], fork->front, 0);
-    if (e != hipSuccess) return e;
-  }
-  // (a family whose host counts prove it has no row-0 / quarter key launches none: launch_keyprep)
-  const bool* nf = fork ? fork->pending.need_full : nullptr;
-  if (!nf || nf[2])
-    CG_TIME(fork, CG_STAGE_ED_LADDER_ROW0, fork ? fork->side[2] : stream,
-            ed_launch_ladder(false, d_items, n_items, d_status, w, iw, d_btab, fork ? fork->side[2] : stream));
-  if (!nf || nf[0])
-    CG_TIME(fork, CG_STAGE_R1_LADDER_ROW0, fork ? fork->side[0] : stream,
-            ec_launch_ladder(CG_CURVE_R1, false, d_items, n_items, d_status, w, iw, d_btab, fork ? fork->side[0] : stream));
-  if (!nf || nf[1])
-    CG_TIME(fork, CG_STAGE_K1_LADDER_ROW0, fork ? fork->side[1] : stream,
-            ec_launch_ladder(CG_CURVE_K1, false, d_items, n_items, d_status, w, iw, d_btab, fork ? fork->side[1] : stream));
-  if (fork) {
-    for (int k = 0; k < 3 && e == hipSuccess; ++k) e = hipEventRecord(fork->row0[k], fork->side[k]);
-    if (e != hipSuccess) return e;
-  }
-  // full-table ladders on `stream`, each after its tables; Ed25519 finish after both ladders
-  // wide-table ladders right after their class's full-table one (same tables-ready event)
-  if (fork) hipStreamWaitEvent(stream, fork->ready[2], 0);
-  CG_TIME(fork, CG_STAGE_ED_LADDER, stream, ed_launch_ladder(true, d_items, n_items, d_status, w, iw, d_btab, stream));
-  if (w.cap_ed)
-    CG_TIME(fork, CG_STAGE_ED_LADDER_WIDE, stream, ed_launch_ladder_wide(d_items, n_items, d_status, w, iw, d_btab, stream));
-  // CG_ED_FINISH_SIDE: the finish (16 items per lane share an inversion: ~1.6 waves per SIMD,
-  // latency-bound) runs on side stream 2 after the row-0 ladders there, beside the ECDSA ladders on
-  // this stream; the stream joins on it at the end of the back
-  static const bool fin_side = [] {  // default on (CG_EC_FRONT_SIDE's note); =0: on `stream`
-    const char* v = getenv("CG_ED_FINISH_SIDE");
-    return !(v && v[0] == '0');
-  }();
-  if (fork && fin_side) {
-    e = hipEventRecord(fork->front, stream);  // the Ed25519 ladders on this stream are enqueued
-    if (e == hipSuccess) e = hipStreamWaitEvent(fork->side[2], fork->front, 0);
-    if (e != hipSuccess) return e;
-    CG_TIME(fork, CG_STAGE_ED_FINISH, fork->side[2],
-            ed_launch_finish(d_items, n_items, d_arena, arena_len, d_status, iw, fork->side[2]));
-    e = hipEventRecord(fork->row0[2], fork->side[2]);
-    if (e != hipSuccess) return e;
-  } else {
-    if (fork) hipStreamWaitEvent(stream, fork->row0[2], 0);
-    CG_TIME(fork, CG_STAGE_ED_FINISH, stream, ed_launch_finish(d_items, n_items, d_arena, arena_len, d_status, iw, stream));
-  }
-  // CG_EC_LADDER_SIDE (A/B, bit 0 secp256r1, bit 1 secp256k1): the curve's full-table and wide
-  // ladders on its side stream (after its front and its row-0 ladders there) instead of after the
-  // Ed25519 ladders on this stream, so the issue-bound ladders fill each other's tails
-  static const uint32_t ec_side = [] {
-    const char* v = getenv("CG_EC_LADDER_SIDE");
-    return v ? (uint32_t)strtoul(v, nullptr, 10) & 3u : 0u;
-  }();
-  // CG_EC_WIDE_MERGED=1 (A/B): the two curves' wide ladders as one launch after both full-table
-  // ladders (k_ec_ladder_wide2), timed as the r1 wide stage
-  static const bool ec_merged = [] {
-    const char* v = getenv("CG_EC_WIDE_MERGED");
-    return v && v[0] == '1';
-  }();
-  const bool merged = ec_merged && !ec_side && w.cap_ec;
-  for (int k = 0; k < 2; ++k) {
+  // Each curve's ECDSA front (prep + s^-1: needs the decoded key, which its side stream decoded) on
+  // its side stream beside the challenge hashes (need only Abyte) here: the s^-1 batches leave ~1
+  // wave per SIMD, latency-bound alone. The side stream waits for everything enqueued on `stream`
+  // so far: this chunk's plan, and the ladders of the chunk two back, which read the item workspace
+  // this front writes. The curve's ladders join on ec_front_done (launch_items_back).
+  e = hipEventRecord(fork.ec_front_go, stream);
+  for (int k = 0; k < 2 && e == hipSuccess; ++k) {
     const int curve = k == 0 ? CG_CURVE_R1 : CG_CURVE_K1;
-    const bool side = fork && (ec_side >> k & 1u);
-    const hipStream_t s = side ? fork->side[k] : stream;
-    if (fork) hipStreamWaitEvent(s, fork->ready[k], 0);
-    if (fork && fork->pending.ec_front_side) hipStreamWaitEvent(s, fork->ec_front_done[k], 0);
-    CG_TIME(fork, k == 0 ? CG_STAGE_R1_LADDER : CG_STAGE_K1_LADDER, s,
-            ec_launch_ladder(curve, true, d_items, n_items, d_status, w, iw, d_btab, s));
-    if (w.cap_ec && !merged)
-      CG_TIME(fork, k == 0 ? CG_STAGE_R1_LADDER_WIDE : CG_STAGE_K1_LADDER_WIDE, s,
-              ec_launch_ladder_wide(curve, d_items, n_items, d_status, w, iw, d_btab, s));
-    if (side) {  // the join below waits for this stream's last ladder
-      e = hipEventRecord(fork->row0[k], s);
-      if (e != hipSuccess) return e;
-    }
+    e = hipStreamWaitEvent(fork.side[k], fork.ec_front_go, 0);
+    if (e != hipSuccess) break;
+    CG_TIME(fork, k == 0 ? CG_STAGE_R1_FRONT : CG_STAGE_K1_FRONT, fork.side[k],
+            ec_launch_front(curve, a.d_items, a.n_items, a.d_arena, a.arena_len, a.mode, a.d_status, w, a.d_msgs,
+                            a.msgs_len, iw, fork.side[k]));
+    e = hipEventRecord(fork.ec_front_done[k], fork.side[k]);
   }
-  if (merged)
-    CG_TIME(fork, CG_STAGE_R1_LADDER_WIDE, stream,
-            ec_launch_ladder_wide_merged(d_items, n_items, d_status, w, iw, d_btab, stream));
-  if (fork) {
-    if (fork->mark) hipEventRecord(fork->mark, stream);
-    hipStreamWaitEvent(stream, fork->row0[0], 0);
-    hipStreamWaitEvent(stream, fork->row0[1], 0);
-    if (fin_side) hipStreamWaitEvent(stream, fork->row0[2], 0);
-    if (fork->pending.skip_mask)  // after every ladder and the finish of this chunk
-      hipLaunchKernelGGL(k_mode_guard, dim3(64), dim3(256), 0, stream, (const uint32_t*)iw.ranges,
-                         (const uint32_t*)iw.perm, (const uint32_t*)w.full_count, fork->pending.skip_mask, d_status);
-  }
+  if (e != hipSuccess) return e;
+  CG_TIME(fork, CG_STAGE_ED_HASH, stream,
+          ed_launch_front(a.d_items, a.n_items, a.d_arena, a.arena_len, a.mode, a.d_status, w, a.d_msgs, a.msgs_len,
+                          iw, stream));
   return hipGetLastError();
 }
 
-hipError_t launch_items(const cg_key* d_keys, uint32_t n_keys, const cg_item* d_items, uint64_t n_items,
-                        const uint8_t* d_arena, uint64_t arena_len, uint32_t mode, uint8_t* d_status,
-                        const void* d_keyprep, void* d_item_ws, const void* d_btab, hipStream_t stream,
-                        const uint8_t* d_msgs, uint64_t msgs_len, const Fork* fork, const WidePool* wide) {
-  hipError_t e = launch_items_front(d_keys, n_keys, d_items, n_items, d_arena, arena_len, mode, d_status, d_keyprep,
-                                    d_item_ws, stream, d_msgs, msgs_len, fork, wide, false);
+hipError_t launch_items_back(const ItemArgs& a, hipStream_t stream, const Fork& fork) {
+  if (a.n_items == 0) return hipSuccess;
+  const KeyWs w = key_ws((void*)a.d_keyprep, a.n_keys, a.wide);
+  const ItemWs iw = item_ws(a.d_item_ws, a.n_items);
+  // Row-0 ladders on the side streams, after their tables there and the hashes here. The full-table
+  // ladders stay on `stream`: a persistent full-GPU grid on a side stream holds every slot while
+  // this stream's next fronts wait.
+  hipError_t e = hipEventRecord(fork.front, stream);
+  for (int k = 0; k < 3 && e == hipSuccess; ++k) e = hipStreamWaitEvent(fork.side[k], fork.front, 0);
   if (e != hipSuccess) return e;
-  return launch_items_back(d_keys, n_keys, d_items, n_items, d_arena, arena_len, d_status, d_keyprep, d_item_ws,
-                           d_btab, stream, fork, wide);
+  // (a family whose host counts prove it has no row-0 / quarter key launches none: launch_keyprep)
+  const bool* nf = fork.pending.need_full;
+  if (nf[2])
+    CG_TIME(fork, CG_STAGE_ED_LADDER_ROW0, fork.side[2],
+            ed_launch_ladder(false, a.d_items, a.n_items, a.d_status, w, iw, a.d_btab, fork.side[2]));
+  if (nf[0])
+    CG_TIME(fork, CG_STAGE_R1_LADDER_ROW0, fork.side[0],
+            ec_launch_ladder(CG_CURVE_R1, false, a.d_items, a.n_items, a.d_status, w, iw, a.d_btab, fork.side[0]));
+  if (nf[1])
+    CG_TIME(fork, CG_STAGE_K1_LADDER_ROW0, fork.side[1],
+            ec_launch_ladder(CG_CURVE_K1, false, a.d_items, a.n_items, a.d_status, w, iw, a.d_btab, fork.side[1]));
+  for (int k = 0; k < 3 && e == hipSuccess; ++k) e = hipEventRecord(fork.row0[k], fork.side[k]);
+  if (e != hipSuccess) return e;
+  // full-table ladders on `stream`, each after its tables; the wide-table ladders right after
+  // their class's full-table one (same tables-ready event)
+  hipStreamWaitEvent(stream, fork.ready[2], 0);
+  CG_TIME(fork, CG_STAGE_ED_LADDER, stream,
+          ed_launch_ladder(true, a.d_items, a.n_items, a.d_status, w, iw, a.d_btab, stream));
+  if (w.cap_ed)
+    CG_TIME(fork, CG_STAGE_ED_LADDER_WIDE, stream,
+            ed_launch_ladder_wide(a.d_items, a.n_items, a.d_status, w, iw, a.d_btab, stream));
+  // The Ed25519 finish (16 items per lane share an inversion: ~1.6 waves per SIMD, latency-bound)
+  // on side stream 2, after the row-0 ladders there and the Ed25519 ladders enqueued here, beside
+  // the ECDSA ladders on this stream; row0[2] then marks its end.
+  e = hipEventRecord(fork.front, stream);
+  if (e == hipSuccess) e = hipStreamWaitEvent(fork.side[2], fork.front, 0);
+  if (e != hipSuccess) return e;
+  CG_TIME(fork, CG_STAGE_ED_FINISH, fork.side[2],
+          ed_launch_finish(a.d_items, a.n_items, a.d_arena, a.arena_len, a.d_status, iw, fork.side[2]));
+  e = hipEventRecord(fork.row0[2], fork.side[2]);
+  if (e != hipSuccess) return e;
+  for (int k = 0; k < 2; ++k) {  // each curve's ladders after its tables and its front
+    const int curve = k == 0 ? CG_CURVE_R1 : CG_CURVE_K1;
+    hipStreamWaitEvent(stream, fork.ready[k], 0);
+    hipStreamWaitEvent(stream, fork.ec_front_done[k], 0);
+    CG_TIME(fork, k == 0 ? CG_STAGE_R1_LADDER : CG_STAGE_K1_LADDER, stream,
+            ec_launch_ladder(curve, true, a.d_items, a.n_items, a.d_status, w, iw, a.d_btab, stream));
+    if (w.cap_ec)
+      CG_TIME(fork, k == 0 ? CG_STAGE_R1_LADDER_WIDE : CG_STAGE_K1_LADDER_WIDE, stream,
+              ec_launch_ladder_wide(curve, a.d_items, a.n_items, a.d_status, w, iw, a.d_btab, stream));
+  }
+  // join the side streams: the row-0 ladders and the finish
+  if (fork.mark) hipEventRecord(fork.mark, stream);
+  for (int k = 0; k < 3; ++k) hipStreamWaitEvent(stream, fork.row0[k], 0);
+  if (fork.pending.skip_mask)  // after every ladder and the finish of this chunk
+    hipLaunchKernelGGL(k_mode_guard, dim3(64), dim3(256), 0, stream, (const uint32_t*)iw.ranges,
+                       (const uint32_t*)iw.perm, (const uint32_t*)w.full_count, fork.pending.skip_mask, a.d_status);
+  return hipGetLastError();
 }
 
-hipError_t launch_verify(const cg_key* d_keys, uint32_t n_keys, const cg_item* d_items, uint64_t n_items,
-                         const uint8_t* d_arena, uint64_t arena_len, uint32_t mode, uint8_t* d_status,
-                         void* d_keyprep, void* d_item_ws, const void* d_btab, hipStream_t stream,
-                         const uint8_t* d_msgs, uint64_t msgs_len, const Fork* fork, const WidePool* wide) {
-  if (n_items == 0) return hipSuccess;
-  hipError_t e = launch_keyprep(d_keys, n_keys, d_arena, arena_len, d_keyprep, stream, fork, d_items, n_items, wide);
-  if (e != hipSuccess) return e;
-  return launch_items(d_keys, n_keys, d_items, n_items, d_arena, arena_len, mode, d_status, d_keyprep, d_item_ws,
-                      d_btab, stream, d_msgs, msgs_len, fork, wide);
+hipError_t launch_items(const ItemArgs& a, hipStream_t stream, const Fork& fork) {
+  const hipError_t e = launch_items_front(a, stream, fork, false);
+  return e != hipSuccess ? e : launch_items_back(a, stream, fork);
 }
 
 // This build's entry points for the C ABI layer (engine.h EngineVariant; one per fixed-base radix).

@@ -130,11 +130,7 @@ __global__ void __launch_bounds__(64) k_ec_wide_chain(uint32_t n_keys, const EdK
   jac_batch_to_affine<C>(ws.bases, ws.jbases, EC_WIDE_DIGITS, ws.s[0].pre, c_ec[C]);
 }
 
-// The row tables in three passes over (wide key, row, group of 32) lanes, as the Ed25519 build
-// (ecdsa_rows.h ec_wide_group_pass): chunk Z products, one inversion per row over its 64 chunk
-// products (in the row's scratch z[0..63], prefixes in pre[0..63]), then the entries.
-#define EC_WIDE_GROUP 32
-#define EC_WIDE_GROUPS (EC_WIDE_MULT / EC_WIDE_GROUP)
+// The lane of a launch with one lane per (wide key l, row j, part g of the row), and its key's slot.
 struct EcWideLane {
   uint32_t l, j, g;
 };
@@ -148,47 +144,12 @@ __device__ __forceinline__ EcWideLane ec_wide_lane(uint32_t rows, uint32_t group
   const uint32_t i = wide[(size_t)c * n_keys + (L).l];     \
   if (hdr[i].status != 0) return;                          \
   EcWideSlot& ws = wec[wide_idx[i]]
-static_assert(EC_WIDE_CHUNKS <= EC_WIDE_MULT, "chunk products fit a row's scratch");
-
-template <int C>
-__global__ void __launch_bounds__(64) k_ec_wide_fwd(uint32_t n_keys, const EdKeyHdr* __restrict__ hdr,
-                                                    const uint32_t* __restrict__ wide,
-                                                    const uint32_t* __restrict__ wide_count,
-                                                    const uint32_t* __restrict__ wide_idx, EcWideSlot* __restrict__ wec) {
-  const EcWideLane L = ec_wide_lane(EC_WIDE_ROWS, EC_WIDE_GROUPS);
-  EC_WIDE_KEY(C, L);
-  constexpr int CPG = EC_WIDE_GROUP / EC_WIDE_CHUNK;
-  ec_wide_group_pass<C, false>(nullptr, &ws.s[L.j].z[CPG * L.g],
-                               ws.bases[L.j < EC_WIDE_DIGITS ? L.j : EC_WIDE_DIGITS - 1], (int)L.j, (int)L.g, c_ec[C]);
-}
-
-template <int C>
-__global__ void __launch_bounds__(64) k_ec_wide_inv(uint32_t n_keys, const EdKeyHdr* __restrict__ hdr,
-                                                    const uint32_t* __restrict__ wide,
-                                                    const uint32_t* __restrict__ wide_count,
-                                                    const uint32_t* __restrict__ wide_idx, EcWideSlot* __restrict__ wec) {
-  const EcWideLane L = ec_wide_lane(EC_WIDE_ROWS, 1);
-  EC_WIDE_KEY(C, L);
-  m29_invert_run<C, EC_WIDE_CHUNKS>(ws.s[L.j].z, ws.s[L.j].pre, c_ec[C]);
-}
-
-template <int C>
-__global__ void __launch_bounds__(64) k_ec_wide_bwd(uint32_t n_keys, const EdKeyHdr* __restrict__ hdr,
-                                                    const uint32_t* __restrict__ wide,
-                                                    const uint32_t* __restrict__ wide_count,
-                                                    const uint32_t* __restrict__ wide_idx, EcWideSlot* __restrict__ wec) {
-  const EcWideLane L = ec_wide_lane(EC_WIDE_ROWS, EC_WIDE_GROUPS);
-  EC_WIDE_KEY(C, L);
-  constexpr int CPG = EC_WIDE_GROUP / EC_WIDE_CHUNK;
-  ec_wide_group_pass<C, true>(&ws.tab.t[L.j][EC_WIDE_GROUP * L.g], &ws.s[L.j].z[CPG * L.g],
-                              ws.bases[L.j < EC_WIDE_DIGITS ? L.j : EC_WIDE_DIGITS - 1], (int)L.j, (int)L.g, c_ec[C]);
-}
 
 #ifndef EC_WIDE_ROWS_PRIO_R1
 #define EC_WIDE_ROWS_PRIO_R1 0
 #endif
-// one lane per (wide key, row): the row's 128 affine multiples by co-Z additions, one launch
-// (ecdsa_rows.h ec_wide_row_build; replaces the three passes above unless CG_EC_WIDE_COZ=0)
+// EC_WIDE_ROW_LANES lanes per (wide key, row): the row's 128 affine multiples by co-Z additions,
+// one launch (ecdsa_rows.h ec_wide_row_build)
 template <int C>
 __global__ void __launch_bounds__(64) k_ec_wide_rows(uint32_t n_keys, const EdKeyHdr* __restrict__ hdr,
                                                      const uint32_t* __restrict__ wide,
@@ -204,9 +165,6 @@ __global__ void __launch_bounds__(64) k_ec_wide_rows(uint32_t n_keys, const EdKe
   ec_wide_row_build<C>(ws.tab.t[L.j], pk, ws.bases[L.j < EC_WIDE_DIGITS ? L.j : EC_WIDE_DIGITS - 1],
                        L.j == EC_WIDE_DIGITS, per * (int)L.g, per * (int)L.g + per, c_ec[C]);
 }
-#ifndef CG_EC_WIDE_COZ
-#define CG_EC_WIDE_COZ 1
-#endif
 
 // G wide rows: the row bases 2^{EC_WIDE_GW u} G first (one lane per row, into scratch slot 0),
 // then one lane per (row u, group g of 32 multiples) in batches over scratch slots 1..
@@ -496,30 +454,6 @@ k_ec_ladder_wide(const cg_item* __restrict__ items,
     ec_wide_item<C>(beg + wk.u, items, perm, wide_idx, wec, gw, status, ws, wave_lds, wl, lane);
 }
 
-// CG_EC_WIDE_MERGED (A/B): both curves' wide items in one launch, the secp256r1 range then the
-// secp256k1 range walked as one (a curve's launch alone leaves a partial last round of waves: the
-// k1 range is ~1.2 rounds of the resident lanes); a wave's items are of one curve except at the seam.
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(EC_LADDER_WIDE_WAVES)))
-k_ec_ladder_wide2(const cg_item* __restrict__ items, const uint32_t* __restrict__ perm,
-                  const uint32_t* __restrict__ ranges, const uint32_t* __restrict__ wide_idx,
-                  const EcWideSlot* __restrict__ wec, const EcGWideTab* __restrict__ gw_r1,
-                  const EcGWideTab* __restrict__ gw_k1, uint8_t* __restrict__ status,
-                  const EcItemWs* __restrict__ ws) {
-  __shared__ __attribute__((aligned(16))) uint8_t stage[4 * EC_WAVE_LDS];
-  const int c1 = plan_class_of_curve(CG_CURVE_R1), c0 = plan_class_of_curve(CG_CURVE_K1);
-  const uint32_t b1 = ranges[PLAN_WIDE + c1], n1 = ranges[c1 + 1] - b1;
-  const uint32_t b0 = ranges[PLAN_WIDE + c0], n0 = ranges[c0 + 1] - b0;
-  uint8_t* wave_lds = stage + (threadIdx.x >> 6) * EC_WAVE_LDS;
-  const uint32_t wl = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(ec_lds_ptr)wave_lds);
-  const uint32_t lane = __lane_id();
-  for (Walk wk = walk_units((uint64_t)n1 + n0); wk.u < wk.end; wk.u += wk.step) {
-    if (wk.u < n1)
-      ec_wide_item<CG_CURVE_R1>(b1 + wk.u, items, perm, wide_idx, wec, gw_r1, status, ws, wave_lds, wl, lane);
-    else
-      ec_wide_item<CG_CURVE_K1>(b0 + (wk.u - n1), items, perm, wide_idx, wec, gw_k1, status, ws, wave_lds, wl, lane);
-  }
-}
-
 hipError_t ec_upload_constants() {
   EcConsts k[2];
   ec_consts_init<CG_CURVE_K1>(k[CG_CURVE_K1]);
@@ -551,21 +485,17 @@ hipError_t ec_init_const(void* d_btab, void* d_scratch, hipStream_t stream) {
 
 template <int C>
 static void launch_keyprep_chains(const cg_key* d_keys, uint32_t n_keys, const uint8_t* d_arena, uint64_t arena_len,
-                                  const KeyWs& w, hipStream_t stream, hipEvent_t decoded) {
+                                  const KeyWs& w, hipStream_t stream) {
   const uint32_t B = 64;
   const dim3 g((n_keys + B - 1) / B);
   hipLaunchKernelGGL(k_ec_keyprep_decode<C>, g, dim3(B), 0, stream, d_keys, n_keys, d_arena, arena_len, w.hdr,
                      w.bases);
-  if (decoded) hipEventRecord(decoded, stream);
   hipLaunchKernelGGL(k_ec_keyprep_chain<C>, g, dim3(B), 0, stream, n_keys, w.hdr, (const uint32_t*)w.full,
                      (const uint32_t*)w.quart, (const uint32_t*)w.full_count, w.bases);
-  if (w.cap_ec) {
-    const uint32_t lds = chain_spread_lds();
-    if (lds) hipFuncSetAttribute((const void*)k_ec_wide_chain<C>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(k_ec_wide_chain<C>, dim3((w.cap_ec + B - 1) / B), dim3(B), lds, stream, n_keys, w.hdr,
+  if (w.cap_ec)
+    hipLaunchKernelGGL(k_ec_wide_chain<C>, dim3((w.cap_ec + B - 1) / B), dim3(B), 0, stream, n_keys, w.hdr,
                        (const uint32_t*)w.wide, (const uint32_t*)w.wide_count, (const uint32_t*)w.wide_idx,
                        (const BaseSlot*)w.bases, w.wec);
-  }
 }
 
 template <int C>
@@ -577,29 +507,18 @@ static void launch_keyprep_tabs(const cg_key* d_keys, uint32_t n_keys, const Key
                        (const uint32_t*)w.row0, (const uint32_t*)w.full, (const uint32_t*)w.quart,
                        (const uint32_t*)w.full_count, w.tab, w.park_ec[C], w.park_lanes_ec);
   if (wide && w.cap_ec) {
-    const uint64_t gl = (uint64_t)w.cap_ec * EC_WIDE_ROWS * EC_WIDE_GROUPS, rl = (uint64_t)w.cap_ec * EC_WIDE_ROWS;
-    const uint32_t* wl = (const uint32_t*)w.wide;
-    const uint32_t* wc = (const uint32_t*)w.wide_count;
-    const uint32_t* wi = (const uint32_t*)w.wide_idx;
-    if (CG_EC_WIDE_COZ) {
-      hipLaunchKernelGGL(k_ec_wide_rows<C>, dim3((unsigned)((rl * EC_WIDE_ROW_LANES + B - 1) / B)), dim3(B), 0, stream,
-                         n_keys, w.hdr, wl, wc, wi, w.wec);
-    } else {
-      hipLaunchKernelGGL(k_ec_wide_fwd<C>, dim3((unsigned)((gl + B - 1) / B)), dim3(B), 0, stream, n_keys, w.hdr,
-                         wl, wc, wi, w.wec);
-      hipLaunchKernelGGL(k_ec_wide_inv<C>, dim3((unsigned)((rl + B - 1) / B)), dim3(B), 0, stream, n_keys, w.hdr,
-                         wl, wc, wi, w.wec);
-      hipLaunchKernelGGL(k_ec_wide_bwd<C>, dim3((unsigned)((gl + B - 1) / B)), dim3(B), 0, stream, n_keys, w.hdr,
-                         wl, wc, wi, w.wec);
-    }
+    const uint64_t rl = (uint64_t)w.cap_ec * EC_WIDE_ROWS;
+    hipLaunchKernelGGL(k_ec_wide_rows<C>, dim3((unsigned)((rl * EC_WIDE_ROW_LANES + B - 1) / B)), dim3(B), 0, stream,
+                       n_keys, w.hdr, (const uint32_t*)w.wide, (const uint32_t*)w.wide_count,
+                       (const uint32_t*)w.wide_idx, w.wec);
     kc_launch_commit(C == CG_CURVE_R1 ? PLAN_R1 : PLAN_K1, n_keys, w, stream);
   }
 }
 
 void ec_launch_keyprep_chains(int curve, const cg_key* d_keys, uint32_t n_keys, const uint8_t* d_arena,
-                              uint64_t arena_len, const KeyWs& w, hipStream_t stream, hipEvent_t decoded) {
-  if (curve == CG_CURVE_R1) launch_keyprep_chains<CG_CURVE_R1>(d_keys, n_keys, d_arena, arena_len, w, stream, decoded);
-  else launch_keyprep_chains<CG_CURVE_K1>(d_keys, n_keys, d_arena, arena_len, w, stream, decoded);
+                              uint64_t arena_len, const KeyWs& w, hipStream_t stream) {
+  if (curve == CG_CURVE_R1) launch_keyprep_chains<CG_CURVE_R1>(d_keys, n_keys, d_arena, arena_len, w, stream);
+  else launch_keyprep_chains<CG_CURVE_K1>(d_keys, n_keys, d_arena, arena_len, w, stream);
 }
 
 void ec_launch_keyprep_tabs(int curve, const cg_key* d_keys, uint32_t n_keys, const KeyWs& w, hipStream_t stream,
@@ -623,12 +542,7 @@ static void launch_front(const cg_item* d_items, uint64_t n_items, const uint8_t
                          const ItemWs& iw, hipStream_t stream) {
   const uint32_t B = 256;  // a curve's range is at most n_items long
   EcItemWs* ws = (EcItemWs*)iw.slots;
-  static const uint32_t prep_waves = [] {  // CG_EC_PREP_WAVES (A/B): waves per SIMD of the prep grid
-    const char* v = getenv("CG_EC_PREP_WAVES");
-    const uint32_t x = v ? (uint32_t)strtoul(v, nullptr, 10) : 0u;
-    return x ? x : (uint32_t)EC_PREP_CAP_WAVES;
-  }();
-  const dim3 pgrid(walk_grid(n_items, B, WALK_CAP(prep_waves)));
+  const dim3 pgrid(walk_grid(n_items, B, WALK_CAP(EC_PREP_CAP_WAVES)));
   if (d_msgs)
     hipLaunchKernelGGL((k_ec_prep<C, true>), pgrid, dim3(B), 0, stream, d_items, iw.perm, iw.ranges, w.hdr, d_arena,
                        arena_len, d_msgs, msgs_len, mode, d_status, ws);
@@ -693,14 +607,6 @@ void ec_launch_ladder_wide(int curve, const cg_item* d_items, uint64_t n_items, 
                            const ItemWs& iw, const void* d_btab, hipStream_t stream) {
   if (curve == CG_CURVE_R1) launch_ladder_wide_t<CG_CURVE_R1>(d_items, n_items, d_status, w, iw, d_btab, stream);
   else launch_ladder_wide_t<CG_CURVE_K1>(d_items, n_items, d_status, w, iw, d_btab, stream);
-}
-
-void ec_launch_ladder_wide_merged(const cg_item* d_items, uint64_t n_items, uint8_t* d_status, const KeyWs& w,
-                                  const ItemWs& iw, const void* d_btab, hipStream_t stream) {
-  const uint32_t B = 256;
-  hipLaunchKernelGGL(k_ec_ladder_wide2, dim3(walk_grid(n_items, B, WALK_CAP(EC_LADDER_WIDE_WAVES))), dim3(B), 0, stream,
-                     d_items, iw.perm, iw.ranges, (const uint32_t*)w.wide_idx, (const EcWideSlot*)w.wec,
-                     gwide(d_btab, CG_CURVE_R1), gwide(d_btab, CG_CURVE_K1), d_status, (const EcItemWs*)iw.slots);
 }
 
 }  // namespace cg

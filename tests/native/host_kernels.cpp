@@ -617,7 +617,7 @@ static void tbw_touch(const uint32_t* es) {
 }
 
 // counts (optional): [0..1] ladder fe_mul / fe_sq per item, [2..3] table build per key (chain + rows)
-// k_ed_wide_rows (one lane per row) against the three-pass build (k_ed_wide_fwd / _inv / _bwd)
+// k_ed_wide_rows (one lane per row) against the three-pass lane functions (ed_wide_group_pass)
 // for the row base P = m B (m >= 1): the number of entries whose canonical encodings differ.
 extern "C" int t_ed_wide_row_cmp(uint32_t m) {
   init();
@@ -858,8 +858,8 @@ static int ecdsa_wide_verify(const uint8_t* arena, uint64_t lr, uint64_t key_off
   return (int)st;
 }
 
-// k_ec_wide_rows (co-Z, one lane per row) against the three-pass build (k_ec_wide_fwd / _inv /
-// _bwd) for row base m * G (m >= 1): every entry of rows 0, 1 and 32-style (top) equal after
+// k_ec_wide_rows (co-Z, one lane per row) against the three-pass lane functions
+// (ec_wide_group_pass) for row base m * G (m >= 1): every entry of rows 0, 1 and 32-style (top) equal after
 // canonicalisation. Returns the number of differing entries.
 template <int C>
 static int ec_wide_row_cmp(uint32_t m) {

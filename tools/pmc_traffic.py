@@ -28,8 +28,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KERNELS = ("k_ed_hash", "k_ed_hash<true>", "k_ed_hash<false>", "k_ec_prep<1, true>", "k_ec_prep<0, true>",
            "k_ec_prep<1, false>", "k_ec_prep<0, false>", "k_ed_ladder_pf", "k_ed_ladder_wide", "k_ed_finish", "k_ec_prep<1>", "k_ec_inv<1>",
            "k_ec_ladder<1, true>", "k_ec_ladder_wide<1>", "k_ec_prep<0>", "k_ec_inv<0>", "k_ec_ladder<0, true>",
-           "k_ec_ladder_wide<0>", "k_ed_wide_fwd", "k_ed_wide_inv", "k_ed_wide_bwd", "k_ec_wide_fwd<1>",
-           "k_ec_wide_bwd<1>", "k_ec_wide_fwd<0>", "k_ec_wide_bwd<0>", "k_ec_wide_inv<1>", "k_ec_wide_inv<0>",
+           "k_ec_ladder_wide<0>",
            # configs[3] transaction pipeline (tools/profile_tx.sh)
            "k_tx_map", "k_tx_leaf_count", "k_tx_leaf_scatter", "k_tx_leaves", "k_tx_roots", "k_txsig_items", "k_splice")
 
