@@ -348,17 +348,13 @@ hipError_t ensure_rsa(cg_ctx* c, uint32_t n_keys, uint64_t n_items) {
 // The RSA halves of a call, on the stream of its other launches: the key records before any item
 // stage, the item pass after the last chunk's back (the item table, the arena window, the tx items
 // and the message workspace are whole-call buffers, intact until the call ends).
-hipError_t rsa_keyprep(cg_ctx* c, const cg_key* d_keys, uint32_t n_keys, const uint8_t* d_arena, uint64_t arena_len,
-                       hipStream_t s) {
+hipError_t rsa_keyprep(cg_ctx* c, const cg::VerifyReq& r, hipStream_t s) {
   if (!c->rsa) return hipSuccess;
-  return cg::launch_rsa_keyprep(d_keys, n_keys, d_arena, arena_len, c->rsakeys.p, s);
+  return cg::launch_rsa_keyprep(r, c->rsakeys.p, s);
 }
-hipError_t rsa_items(cg_ctx* c, const cg_key* d_keys, uint32_t n_keys, const cg_item* d_items, uint64_t n_items,
-                     const uint8_t* d_arena, uint64_t arena_len, uint32_t mode, uint8_t* d_status, hipStream_t s,
-                     const uint8_t* d_msgs = nullptr, uint64_t msgs_len = 0) {
-  if (!c->rsa || n_items == 0) return hipSuccess;
-  return cg::launch_rsa_items(d_keys, n_keys, d_items, n_items, d_arena, arena_len, mode, d_status, c->rsakeys.p,
-                              c->rsalist.p, s, d_msgs, msgs_len);
+hipError_t rsa_items(cg_ctx* c, const cg::VerifyReq& r, hipStream_t s) {
+  if (!c->rsa || r.n_items == 0) return hipSuccess;
+  return cg::launch_rsa_items(r, c->rsakeys.p, c->rsalist.p, s);
 }
 
 hipError_t ensure_ws(cg_ctx* c, uint32_t n_keys, uint64_t ws_items, uint64_t call_items = 0) {
@@ -430,50 +426,42 @@ cg::WidePool wide_for(cg_ctx* c, uint32_t n_keys, uint64_t n_items) {
   return p;
 }
 
-// Key tables once for the whole call (sized by every item's key use), then the items in chunks.
-hipError_t launch_chunked(cg_ctx* c, const cg_key* d_keys, uint32_t n_keys, const cg_item* d_items, uint64_t n_items,
-                          const uint8_t* d_arena, uint64_t arena_len, uint32_t mode, uint8_t* d_status, hipStream_t s,
-                          const uint8_t* d_msgs = nullptr, uint64_t msgs_len = 0,
-                          const std::function<hipError_t(uint64_t, uint64_t, uint64_t)>* prepare = nullptr,
-                          const cg::KeyUses* uses = nullptr, const std::vector<uint64_t>* bounds = nullptr,
-                          bool prepare_blocks = false) {
-  // prepare (the tx-signature entry points): called with (k, first item, items) just before chunk
-  // k's front is enqueued; it makes chunk k's verify items (and, host form, its bytes) and orders
-  // `s` after them. The key tables are then sized from `uses` and start building at once, before
-  // any chunk is prepared (so they overlap the host copies).
-  if (n_items == 0) return hipSuccess;
-  const cg::WidePool wp = wide_for(c, n_keys, n_items);
-  hipError_t e = c->eng->launch_keyprep(d_keys, n_keys, d_arena, arena_len, c->keyprep.p, s, c->fork,
-                                    uses ? nullptr : d_items, n_items, &wp, uses);
-  if (e == hipSuccess) e = rsa_keyprep(c, d_keys, n_keys, d_arena, arena_len, s);
+// launch_chunked's options (the tx-signature entry points set them). prepare: called with (k, first
+// item, items) just before chunk k's front is enqueued; it makes chunk k's verify items (and, host
+// form, its bytes) and orders `s` after them. The key tables are then sized from `uses` and start
+// building at once, before any chunk is prepared (so they overlap the host copies).
+// prepare_blocks: the hook copies from host memory and blocks the enqueuing thread.
+struct ChunkOpts {
+  const std::function<hipError_t(uint64_t, uint64_t, uint64_t)>* prepare = nullptr;
+  const cg::KeyUses* uses = nullptr;
+  bool prepare_blocks = false;
+};
+
+// Key tables once for the whole call (sized by every item's key use), then the items in chunks:
+// chunk k = items [bounds[k], bounds[k + 1]) (bounds[0] = 0, the last one = r.n_items).
+hipError_t launch_chunked(cg_ctx* c, const cg::VerifyReq& r, const std::vector<uint64_t>& bounds, hipStream_t s,
+                          const ChunkOpts& o) {
+  if (r.n_items == 0) return hipSuccess;
+  const cg::WidePool wp = wide_for(c, r.n_keys, r.n_items);
+  hipError_t e = c->eng->launch_keyprep(r, c->keyprep.p, s, c->fork, &wp, o.uses);
+  if (e == hipSuccess) e = rsa_keyprep(c, r, s);
   // the RSA pass over the whole call, after the last chunk's back
-  auto rsa_pass = [&](hipError_t r) {
-    if (r == hipSuccess) c->kc_open = false;  // every kernel of the call is enqueued, the cache's commits among them
-    return r != hipSuccess ? r : rsa_items(c, d_keys, n_keys, d_items, n_items, d_arena, arena_len, mode, d_status, s,
-                                           d_msgs, msgs_len);
+  auto rsa_pass = [&](hipError_t x) {
+    if (x == hipSuccess) c->kc_open = false;  // every kernel of the call is enqueued, the cache's commits among them
+    return x != hipSuccess ? x : rsa_items(c, r, s);
   };
-  // chunk k = items [at(k), at(k) + cnt(k)): the caller's bounds (bounds[0] = 0, bounds[nch] = n),
-  // else equal chunks of chunk_of(c, n) items; `per` (the largest chunk) sizes the item workspaces
-  uint64_t per = chunk_of(c, n_items);
-  uint64_t nch = (n_items + per - 1) / per;
-  if (bounds) {
-    nch = bounds->size() - 1;
-    per = 0;
-    for (uint64_t k = 0; k < nch; ++k) per = std::max(per, (*bounds)[k + 1] - (*bounds)[k]);
-  }
-  auto at = [&](uint64_t k) { return bounds ? (*bounds)[k] : k * per; };
-  auto cnt = [&](uint64_t k) {
-    return bounds ? (*bounds)[k + 1] - (*bounds)[k] : (per < n_items - k * per ? per : n_items - k * per);
-  };
+  // `per` (the largest chunk) sizes the item workspaces
+  const uint64_t nch = bounds.size() - 1, per = cg::largest_chunk(bounds);
+  auto at = [&](uint64_t k) { return bounds[k]; };
+  auto cnt = [&](uint64_t k) { return bounds[k + 1] - bounds[k]; };
   // chunk k's item workspace: half k % 2 when the buffer holds two (ensure_ws), else the one
   const bool two = nch > 1 && c->itemws.cap >= 2 * item_half_bytes(c, per);
-  const cg::ItemArgs call = {d_keys, n_keys, d_items, n_items, d_arena, arena_len, mode, d_status, c->keyprep.p,
-                             c->itemws.p, c->btab, d_msgs, msgs_len, &wp};
+  const cg::ItemArgs call = {r, c->keyprep.p, c->itemws.p, c->btab, &wp};
   auto chunk = [&](uint64_t k) {
     cg::ItemArgs a = call;
-    a.d_items = d_items + at(k);
+    a.d_items = r.d_items + at(k);
     a.n_items = cnt(k);
-    a.d_status = d_status + at(k);
+    a.d_status = r.d_status + at(k);
     a.d_item_ws = (uint8_t*)c->itemws.p + (two ? (k & 1) * item_half_bytes(c, per) : 0);
     return a;
   };
@@ -482,12 +470,12 @@ hipError_t launch_chunked(cg_ctx* c, const cg_key* d_keys, uint32_t n_keys, cons
   // as pre_plan does for the batch forms, measured slower: 388.3 vs 392.1 M sigs/s over 3 pairs,
   // profiles/r06/preplan: chunk 0's Ed25519 ladder then starts earlier but shares the chip with chunk
   // 1's ECDSA fronts, 12.5 vs 11.9 ms of ladder per step; the chip is already full in phase 1)
-  const bool pre_plan = two && !prepare;
+  const bool pre_plan = two && !o.prepare;
   double prep_ms = 0;  // CG_HOST_TRACE: the host's time in chunk k's prepare hook
   auto front = [&](uint64_t k) {
-    if (prepare) {
+    if (o.prepare) {
       const auto p0 = std::chrono::steady_clock::now();
-      const hipError_t w = (*prepare)(k, at(k), cnt(k));
+      const hipError_t w = (*o.prepare)(k, at(k), cnt(k));
       prep_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - p0).count();
       if (w != hipSuccess) return w;
     }
@@ -502,7 +490,7 @@ hipError_t launch_chunked(cg_ctx* c, const cg_key* d_keys, uint32_t n_keys, cons
   // The host forms start the table builds now, so that they overlap the first chunk's copies. The
   // device forms have no copy to hide: their builds start after the first chunk's plan
   // (launch_items_front), whose onesweep look-back otherwise stalls behind the builds.
-  if (e == hipSuccess && prepare && prepare_blocks) e = c->eng->launch_key_tables(c->fork, s);
+  if (e == hipSuccess && o.prepare && o.prepare_blocks) e = c->eng->launch_key_tables(c->fork, s);
   auto back = [&](uint64_t k) {
     if (k == 0 && c->htrace && c->backt[0]) {  // chunk 0's front done; every table family built
       hipEventRecord(c->backt[0], s);
@@ -511,12 +499,12 @@ hipError_t launch_chunked(cg_ctx* c, const cg_key* d_keys, uint32_t n_keys, cons
       hipEventRecord(c->backt[1], t);
     }
     c->fork.mark = c->htrace && 3 * k + 2 < c->fbt.size() ? c->fbt[3 * k + 2] : nullptr;  // before the joins
-    const hipError_t r = c->eng->launch_items_back(chunk(k), s, c->fork);
+    const hipError_t x = c->eng->launch_items_back(chunk(k), s, c->fork);
     c->fork.mark = nullptr;
     if (c->htrace && 3 * k + 1 < c->fbt.size()) hipEventRecord(c->fbt[3 * k + 1], s);  // back k ends
-    return r;
+    return x;
   };
-  if (prepare_blocks) {
+  if (o.prepare_blocks) {
     // host copies in the prepare hook block the enqueuing thread: chunk k's back goes in before
     // chunk k + 1's copy, so the device runs chunk k's ladders during it (with chunk k + 1's front
     // first, chunk k's ladders waited for chunk k + 1's copy: profiles/r03/v5 timeline)
@@ -613,14 +601,16 @@ void fill_stats(cg_ctx* c, cg_stats* stats, uint64_t n_items, uint32_t n_keys, d
   stats->ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
 
-// cg_verify_batch with the ctx lock held. On failure the status bytes are CG_NOT_RUN.
-int verify_host_locked(cg_ctx* c, const cg_key* keys, uint32_t n_keys, const cg_item* items, uint64_t n_items,
-                       const uint8_t* arena, uint64_t arena_len, uint32_t mode, uint8_t* status_out, cg_stats* stats) {
+// cg_verify_batch with the ctx lock held; `h` holds the caller's host buffers. On failure the status
+// bytes are CG_NOT_RUN.
+int verify_host_locked(cg_ctx* c, const cg::VerifyReq& h, cg_stats* stats) {
   const auto t0 = std::chrono::steady_clock::now();
   if (const int rc = enter(c, "cg_verify_batch")) return rc;
+  const uint32_t n_keys = h.n_keys;
+  const uint64_t n_items = h.n_items;
   const uint64_t pipe = c->chunk < CG_PIPELINE_CHUNK_ITEMS ? c->chunk : CG_PIPELINE_CHUNK_ITEMS;
   HostPlan P;
-  plan_host(c, keys, n_keys, items, n_items, arena_len, pipe, P);
+  plan_host(c, h.d_keys, n_keys, h.d_items, n_items, h.arena_len, pipe, P);
   const uint64_t nch = P.ext.size();
   const uint64_t per_max = (n_items + nch - 1) / nch;
   HIP_TRY(c->keys.ensure(sizeof(cg_key) * (n_keys ? n_keys : 1)), "hipMalloc(keys)");
@@ -631,46 +621,57 @@ int verify_host_locked(cg_ctx* c, const cg_key* keys, uint32_t n_keys, const cg_
   HIP_TRY(ensure_events(c->seg, nch), "hipEventCreate");
   hipStream_t s = c->stream;
   uint8_t* dwin = (uint8_t*)c->arena.p;
-  // the kernels index the arena by absolute offsets: hand them the window's base shifted back
-  const uint8_t* dbase = dwin - P.win.lo;
   Call call(c, Call::kHost);
   HIP_TRY(call.open(), "hipStreamWaitEvent");
   HIP_TRY(hipEventRecord(c->tev[0], s), "hipEventRecord");
   HIP_TRY(hipStreamWaitEvent(c->copy, c->tev[0], 0), "hipStreamWaitEvent");
   cg::Resident have;
   if (n_keys)
-    HIP_TRY(hipMemcpyAsync(c->keys.p, keys, sizeof(cg_key) * n_keys, hipMemcpyHostToDevice, c->copy), "H2D keys");
-  HIP_TRY(copy_missing(have, P.keys, arena, dwin, P.win.lo, c->copy), "H2D key bytes");
-  HIP_TRY(hipMemcpyAsync(c->items.p, items, sizeof(cg_item) * n_items, hipMemcpyHostToDevice, c->copy), "H2D items");
+    HIP_TRY(hipMemcpyAsync(c->keys.p, h.d_keys, sizeof(cg_key) * n_keys, hipMemcpyHostToDevice, c->copy), "H2D keys");
+  HIP_TRY(copy_missing(have, P.keys, h.d_arena, dwin, P.win.lo, c->copy), "H2D key bytes");
+  HIP_TRY(hipMemcpyAsync(c->items.p, h.d_items, sizeof(cg_item) * n_items, hipMemcpyHostToDevice, c->copy), "H2D items");
   // key tables sized by every item's key, built while chunk 0's arena bytes copy
   HIP_TRY(hipEventRecord(c->seg[0], c->copy), "hipEventRecord");
   HIP_TRY(hipStreamWaitEvent(s, c->seg[0], 0), "hipStreamWaitEvent");
-  const cg_key* dk = (const cg_key*)c->keys.p;
-  const cg_item* di = (const cg_item*)c->items.p;
-  uint8_t* ds = (uint8_t*)c->status.p;
+  // the device's copy of the request; the kernels index the arena by absolute offsets: hand them the
+  // window's base shifted back
+  cg::VerifyReq d = h;
+  d.d_keys = (const cg_key*)c->keys.p;
+  d.d_items = (const cg_item*)c->items.p;
+  d.d_arena = dwin - P.win.lo;
+  d.d_status = (uint8_t*)c->status.p;
   const cg::WidePool wp = wide_for(c, n_keys, n_items);
-  HIP_TRY(c->eng->launch_keyprep(dk, n_keys, dbase, arena_len, c->keyprep.p, s, c->fork, di, n_items, &wp, nullptr),
-          "launch_keyprep");
-  cg::ItemArgs a = {dk, n_keys, di, n_items, dbase, arena_len, mode, ds, c->keyprep.p, c->itemws.p, c->btab, nullptr, 0, &wp};
-  HIP_TRY(rsa_keyprep(c, dk, n_keys, dbase, arena_len, s), "launch_rsa_keyprep");
+  HIP_TRY(c->eng->launch_keyprep(d, c->keyprep.p, s, c->fork, &wp, nullptr), "launch_keyprep");
+  cg::ItemArgs a = {d, c->keyprep.p, c->itemws.p, c->btab, &wp};
+  HIP_TRY(rsa_keyprep(c, d, s), "launch_rsa_keyprep");
   for (uint64_t k = 0; k < nch; ++k) {
-    HIP_TRY(copy_missing(have, P.ext[k], arena, dwin, P.win.lo, c->copy), "H2D arena");
+    HIP_TRY(copy_missing(have, P.ext[k], h.d_arena, dwin, P.win.lo, c->copy), "H2D arena");
     HIP_TRY(hipEventRecord(c->seg[k], c->copy), "hipEventRecord");
     HIP_TRY(hipStreamWaitEvent(s, c->seg[k], 0), "hipStreamWaitEvent");
     if (k == 0) HIP_TRY(hipEventRecord(c->tev[1], s), "hipEventRecord");
-    a.d_items = di + P.first[k];
+    a.d_items = d.d_items + P.first[k];
     a.n_items = P.first[k + 1] - P.first[k];
-    a.d_status = ds + P.first[k];
+    a.d_status = d.d_status + P.first[k];
     HIP_TRY(c->eng->launch_items(a, s, c->fork), "launch_items");
   }
   c->kc_open = false;  // every kernel of the call is enqueued, the wide-table cache's commits among them
-  HIP_TRY(rsa_items(c, dk, n_keys, di, n_items, dbase, arena_len, mode, ds, s), "launch_rsa_items");
+  HIP_TRY(rsa_items(c, d, s), "launch_rsa_items");
   HIP_TRY(hipEventRecord(c->tev[2], s), "hipEventRecord");
-  HIP_TRY(hipMemcpyAsync(status_out, ds, n_items, hipMemcpyDeviceToHost, s), "D2H status");
+  HIP_TRY(hipMemcpyAsync(h.d_status, d.d_status, n_items, hipMemcpyDeviceToHost, s), "D2H status");
   HIP_TRY(hipEventRecord(c->tev[3], s), "hipEventRecord");
   HIP_TRY(call.close(), "hipEventRecord");
   HIP_TRY(hipStreamSynchronize(s), "hipStreamSynchronize");
   fill_stats(c, stats, n_items, n_keys, 0, t0);
+  return CG_OK;
+}
+
+// The argument checks of the cg_verify_batch family, after the ctx / pool check (host: the forms over
+// host buffers, which the library itself reads)
+int batch_args(const char* fn, const cg::VerifyReq& r, bool host) {
+  if (r.n_items && (!r.d_items || !r.d_status)) return fail(CG_ERR_ARG, "%s: NULL buffer", fn);
+  if (host && r.n_keys && !r.d_keys) return fail(CG_ERR_ARG, "%s: keys is NULL", fn);
+  if (host && r.arena_len && !r.d_arena) return fail(CG_ERR_ARG, "%s: arena is NULL", fn);
+  if (r.mode > CG_MODE_ISVALID) return fail(CG_ERR_ARG, "%s: bad mode", fn);
   return CG_OK;
 }
 
@@ -985,14 +986,14 @@ int cg_verify_batch_device(cg_ctx* c, const cg_key* d_keys, uint32_t n_keys, con
                            uint64_t n_items, const uint8_t* d_arena, uint64_t arena_len, uint32_t mode,
                            uint8_t* d_status, void* hip_stream) {
   if (!c) return fail(CG_ERR_ARG, "cg_verify_batch_device: ctx is NULL");
-  if (n_items && (!d_items || !d_status)) return fail(CG_ERR_ARG, "cg_verify_batch_device: NULL buffer");
-  if (mode > CG_MODE_ISVALID) return fail(CG_ERR_ARG, "cg_verify_batch_device: bad mode");
+  const cg::VerifyReq r = {d_keys, n_keys, d_items, n_items, d_arena, arena_len, mode, d_status};
+  if (const int a = batch_args("cg_verify_batch_device", r, false)) return a;
   std::lock_guard<std::mutex> g(c->mu);
   if (const int rc = enter(c, "cg_verify_batch_device")) return rc;
   HIP_TRY(ensure_ws(c, n_keys, chunk_of(c, n_items), n_items), "hipMalloc(workspace)");
   Call call(c, Call::kDevice);
   HIP_TRY(call.open(hip_stream), "hipStreamWaitEvent");
-  HIP_TRY(launch_chunked(c, d_keys, n_keys, d_items, n_items, d_arena, arena_len, mode, d_status, call.stream()),
+  HIP_TRY(launch_chunked(c, r, cg::equal_bounds(n_items, chunk_of(c, n_items)), call.stream(), ChunkOpts{}),
           "launch_verify");
   HIP_TRY(call.close(), "hipEventRecord");
   return CG_OK;
@@ -1009,9 +1010,9 @@ int cg_prepare_keys_device(cg_ctx* c, const cg_key* d_keys, uint32_t n_keys, con
   Call call(c, Call::kDevice);
   HIP_TRY(call.open(hip_stream), "hipStreamWaitEvent");
   hipStream_t s = call.stream();
-  HIP_TRY(c->eng->launch_keyprep(d_keys, n_keys, d_arena, arena_len, c->keyprep.p, s, c->fork, nullptr, 0, nullptr,
-                                 nullptr), "launch_keyprep");
-  HIP_TRY(rsa_keyprep(c, d_keys, n_keys, d_arena, arena_len, s), "launch_rsa_keyprep");
+  const cg::VerifyReq r = {d_keys, n_keys, nullptr, 0, d_arena, arena_len, CG_MODE_DOVERIFY, nullptr};  // no items yet
+  HIP_TRY(c->eng->launch_keyprep(r, c->keyprep.p, s, c->fork, nullptr, nullptr), "launch_keyprep");
+  HIP_TRY(rsa_keyprep(c, r, s), "launch_rsa_keyprep");
   HIP_TRY(call.close(), "hipEventRecord");
   return CG_OK;
 }
@@ -1020,8 +1021,8 @@ int cg_verify_items_device(cg_ctx* c, const cg_key* d_keys, uint32_t n_keys, con
                            uint64_t n_items, const uint8_t* d_arena, uint64_t arena_len, uint32_t mode,
                            uint8_t* d_status, void* hip_stream) {
   if (!c) return fail(CG_ERR_ARG, "cg_verify_items_device: ctx is NULL");
-  if (n_items && (!d_items || !d_status)) return fail(CG_ERR_ARG, "cg_verify_items_device: NULL buffer");
-  if (mode > CG_MODE_ISVALID) return fail(CG_ERR_ARG, "cg_verify_items_device: bad mode");
+  const cg::VerifyReq r = {d_keys, n_keys, d_items, n_items, d_arena, arena_len, mode, d_status};
+  if (const int a = batch_args("cg_verify_items_device", r, false)) return a;
   std::lock_guard<std::mutex> g(c->mu);
   if (c->keyprep.cap < c->eng->keyprep_bytes(n_keys))
     return fail(CG_ERR_ARG, "cg_verify_items_device: keys were not prepared (call cg_prepare_keys_device)");
@@ -1034,15 +1035,14 @@ int cg_verify_items_device(cg_ctx* c, const cg_key* d_keys, uint32_t n_keys, con
   HIP_TRY(call.open(hip_stream), "hipStreamWaitEvent");
   hipStream_t s = call.stream();
   const uint64_t per = chunk_of(c, n_items);
-  cg::ItemArgs a = {d_keys, n_keys, d_items, n_items, d_arena, arena_len, mode, d_status, c->keyprep.p, c->itemws.p,
-                    c->btab, nullptr, 0, nullptr};
+  cg::ItemArgs a = {r, c->keyprep.p, c->itemws.p, c->btab, nullptr};
   for (uint64_t f = 0; f < n_items; f += per) {
     a.d_items = d_items + f;
     a.n_items = per < n_items - f ? per : n_items - f;
     a.d_status = d_status + f;
     HIP_TRY(c->eng->launch_items(a, s, c->fork), "launch_items");
   }
-  HIP_TRY(rsa_items(c, d_keys, n_keys, d_items, n_items, d_arena, arena_len, mode, d_status, s), "launch_rsa_items");
+  HIP_TRY(rsa_items(c, r, s), "launch_rsa_items");
   HIP_TRY(call.close(), "hipEventRecord");
   return CG_OK;
 }
@@ -1051,14 +1051,12 @@ int cg_verify_batch(cg_ctx* c, const cg_key* keys, uint32_t n_keys, const cg_ite
                     const uint8_t* arena, uint64_t arena_len, uint32_t mode, uint8_t* status_out,
                     cg_stats* stats) {
   if (!c) return fail(CG_ERR_ARG, "cg_verify_batch: ctx is NULL");
-  if (n_items && (!items || !status_out)) return fail(CG_ERR_ARG, "cg_verify_batch: NULL buffer");
-  if (n_keys && !keys) return fail(CG_ERR_ARG, "cg_verify_batch: keys is NULL");
-  if (arena_len && !arena) return fail(CG_ERR_ARG, "cg_verify_batch: arena is NULL");
-  if (mode > CG_MODE_ISVALID) return fail(CG_ERR_ARG, "cg_verify_batch: bad mode");
+  const cg::VerifyReq h = {keys, n_keys, items, n_items, arena, arena_len, mode, status_out};
+  if (const int a = batch_args("cg_verify_batch", h, true)) return a;
   if (n_items) memset(status_out, CG_NOT_RUN, n_items);
   if (n_items == 0) return CG_OK;
   std::lock_guard<std::mutex> g(c->mu);
-  const int rc = verify_host_locked(c, keys, n_keys, items, n_items, arena, arena_len, mode, status_out, stats);
+  const int rc = verify_host_locked(c, h, stats);
   if (rc != CG_OK) memset(status_out, CG_NOT_RUN, n_items);
   return rc;
 }
@@ -1193,32 +1191,60 @@ static uint64_t tmpl_slot(const cg_signable_tmpl* tmpls, uint32_t n_tmpls) {
   return slot ? slot : 16;
 }
 
-// The launches of cg_verify_transactions(_device) on `s`, inside the caller's open call (the ctx lock
-// held): grows the workspace (waiting for the device), then ids, verify items and the chunked verify.
-static int verify_transactions_locked(cg_ctx* c, const cg_tx* d_txs, uint64_t n_tx, const cg_component* d_comps,
-                                      uint64_t n_comps, const cg_key* d_keys, uint32_t n_keys, const cg_txsig* d_sigs,
-                                      uint64_t n_sigs, const cg_signable_tmpl* tmpls, uint32_t n_tmpls,
-                                      const uint8_t* d_arena, uint64_t arena_len, uint32_t mode, uint8_t* d_ids,
-                                      uint8_t* d_tx_status, uint8_t* d_sig_status, hipStream_t s) {
-  const uint64_t slot = tmpl_slot(tmpls, n_tmpls), msgs_len = cg::tx_msgs_head(n_tmpls, slot);
-  HIP_TRY(ensure_all({{&c->aux2, cg::tx_ws_bytes(n_comps)},
-                      {&c->txitems, sizeof(cg_item) * (n_sigs ? n_sigs : 1)},
+// One cg_verify_transactions call: the caller's tables (all in host memory, or all in HBM but the
+// templates) and the three result buffers.
+struct TxnReq {
+  const cg_tx* txs;
+  uint64_t n_tx;
+  const cg_component* comps;
+  uint64_t n_comps;
+  const cg_key* keys;
+  uint32_t n_keys;
+  const cg_txsig* sigs;
+  uint64_t n_sigs;
+  const cg_signable_tmpl* tmpls;  // host memory in every form
+  uint32_t n_tmpls;
+  const uint8_t* arena;
+  uint64_t arena_len;
+  uint32_t mode;
+  uint8_t *ids, *tx_status, *sig_status;
+};
+// The argument checks of the family, after the ctx / pool check (host: the forms over host buffers)
+static int txn_args(const char* fn, const TxnReq& q, bool host) {
+  if (q.n_tx && (!q.txs || !q.ids || !q.tx_status)) return fail(CG_ERR_ARG, "%s: NULL tx buffer", fn);
+  if (q.n_sigs && (!q.sigs || !q.sig_status)) return fail(CG_ERR_ARG, "%s: NULL sig buffer", fn);
+  if (host && q.n_comps && !q.comps) return fail(CG_ERR_ARG, "%s: comps is NULL", fn);
+  if (host && q.n_keys && !q.keys) return fail(CG_ERR_ARG, "%s: keys is NULL", fn);
+  if (q.n_tmpls && !q.tmpls) return fail(CG_ERR_ARG, "%s: templates is NULL", fn);
+  if (host && q.arena_len && !q.arena) return fail(CG_ERR_ARG, "%s: arena is NULL", fn);
+  if (q.mode > CG_MODE_ISVALID) return fail(CG_ERR_ARG, "%s: bad mode", fn);
+  return CG_OK;
+}
+
+// The launches of cg_verify_transactions(_device) on `s` over the device tables `d`, inside the
+// caller's open call (the ctx lock held): grows the workspace (waiting for the device), then ids, verify
+// items and the chunked verify.
+static int verify_transactions_locked(cg_ctx* c, const TxnReq& d, hipStream_t s) {
+  const uint64_t slot = tmpl_slot(d.tmpls, d.n_tmpls), msgs_len = cg::tx_msgs_head(d.n_tmpls, slot);
+  HIP_TRY(ensure_all({{&c->aux2, cg::tx_ws_bytes(d.n_comps)},
+                      {&c->txitems, sizeof(cg_item) * (d.n_sigs ? d.n_sigs : 1)},
                       {&c->msgs, msgs_len ? msgs_len : 16},
-                      {&c->tmpls, sizeof(cg_signable_tmpl) * (n_tmpls ? n_tmpls : 1)}}),
+                      {&c->tmpls, sizeof(cg_signable_tmpl) * (d.n_tmpls ? d.n_tmpls : 1)}}),
           "hipMalloc(transaction workspace)");
-  HIP_TRY(ensure_ws(c, n_keys, chunk_of(c, n_sigs), n_sigs), "hipMalloc(workspace)");
-  if (n_tmpls)
-    HIP_TRY(hipMemcpyAsync(c->tmpls.p, tmpls, sizeof(cg_signable_tmpl) * n_tmpls, hipMemcpyHostToDevice, s),
+  HIP_TRY(ensure_ws(c, d.n_keys, chunk_of(c, d.n_sigs), d.n_sigs), "hipMalloc(workspace)");
+  if (d.n_tmpls)
+    HIP_TRY(hipMemcpyAsync(c->tmpls.p, d.tmpls, sizeof(cg_signable_tmpl) * d.n_tmpls, hipMemcpyHostToDevice, s),
             "H2D templates");
-  HIP_TRY(cg::launch_tx_ids(d_txs, n_tx, d_comps, n_comps, d_arena, arena_len, d_ids, d_tx_status,
+  HIP_TRY(cg::launch_tx_ids(d.txs, d.n_tx, d.comps, d.n_comps, d.arena, d.arena_len, d.ids, d.tx_status,
                             (uint8_t*)c->aux2.p, s), "launch_tx_ids");
-  if (n_sigs) {
-    HIP_TRY(cg::launch_tx_sig_items(d_sigs, n_sigs, (const cg_signable_tmpl*)c->tmpls.p, n_tmpls, d_tx_status, n_tx,
-                                    d_ids, d_arena, arena_len, slot, (cg_item*)c->txitems.p, (uint8_t*)c->msgs.p, s),
+  if (d.n_sigs) {
+    HIP_TRY(cg::launch_tx_sig_items(d.sigs, d.n_sigs, (const cg_signable_tmpl*)c->tmpls.p, d.n_tmpls, d.tx_status,
+                                    d.n_tx, d.ids, d.arena, d.arena_len, slot, (cg_item*)c->txitems.p,
+                                    (uint8_t*)c->msgs.p, s),
             "launch_tx_sig_items");
-    HIP_TRY(launch_chunked(c, d_keys, n_keys, (const cg_item*)c->txitems.p, n_sigs, d_arena, arena_len, mode,
-                           d_sig_status, s, (const uint8_t*)c->msgs.p, msgs_len),
-            "launch_verify");
+    const cg::VerifyReq r = {d.keys, d.n_keys, (const cg_item*)c->txitems.p, d.n_sigs, d.arena, d.arena_len, d.mode,
+                             d.sig_status, (const uint8_t*)c->msgs.p, msgs_len};
+    HIP_TRY(launch_chunked(c, r, cg::equal_bounds(d.n_sigs, chunk_of(c, d.n_sigs)), s, ChunkOpts{}), "launch_verify");
   }
   return CG_OK;
 }
@@ -1229,50 +1255,47 @@ int cg_verify_transactions_device(cg_ctx* c, const cg_tx* d_txs, uint64_t n_tx, 
                                   const uint8_t* d_arena, uint64_t arena_len, uint32_t mode, uint8_t* d_ids,
                                   uint8_t* d_tx_status, uint8_t* d_sig_status, void* hip_stream) {
   if (!c) return fail(CG_ERR_ARG, "cg_verify_transactions_device: ctx is NULL");
-  if (n_tx && (!d_txs || !d_ids || !d_tx_status)) return fail(CG_ERR_ARG, "cg_verify_transactions_device: NULL tx buffer");
-  if (n_sigs && (!d_sigs || !d_sig_status)) return fail(CG_ERR_ARG, "cg_verify_transactions_device: NULL sig buffer");
-  if (n_tmpls && !tmpls) return fail(CG_ERR_ARG, "cg_verify_transactions_device: templates is NULL");
-  if (mode > CG_MODE_ISVALID) return fail(CG_ERR_ARG, "cg_verify_transactions_device: bad mode");
+  const TxnReq d = {d_txs, n_tx,  d_comps,   n_comps, d_keys, n_keys, d_sigs,      n_sigs,
+                    tmpls, n_tmpls, d_arena, arena_len, mode, d_ids,  d_tx_status, d_sig_status};
+  if (const int a = txn_args("cg_verify_transactions_device", d, false)) return a;
   std::lock_guard<std::mutex> g(c->mu);
   if (const int rc = enter(c, "cg_verify_transactions_device")) return rc;
   Call call(c, Call::kDevice);
   HIP_TRY(call.open(hip_stream), "hipStreamWaitEvent");
-  if (const int rc = verify_transactions_locked(c, d_txs, n_tx, d_comps, n_comps, d_keys, n_keys, d_sigs, n_sigs, tmpls,
-                                                n_tmpls, d_arena, arena_len, mode, d_ids, d_tx_status, d_sig_status,
-                                                call.stream()))
-    return rc;
+  if (const int rc = verify_transactions_locked(c, d, call.stream())) return rc;
   HIP_TRY(call.close(), "hipEventRecord");
   return CG_OK;
 }
 
 // cg_verify_transactions with the arguments checked and the ctx lock held (also a cg_pool slot's call)
-static int verify_transactions_host_locked(cg_ctx* c, const cg_tx* txs, uint64_t n_tx, const cg_component* comps,
-                                           uint64_t n_comps, const cg_key* keys, uint32_t n_keys, const cg_txsig* sigs,
-                                           uint64_t n_sigs, const cg_signable_tmpl* tmpls, uint32_t n_tmpls,
-                                           const uint8_t* arena, uint64_t arena_len, uint32_t mode, uint8_t* ids_out,
-                                           uint8_t* tx_status_out, uint8_t* sig_status_out) {
+static int verify_transactions_host_locked(cg_ctx* c, const TxnReq& h) {
   if (const int rc = enter(c, "cg_verify_transactions")) return rc;
   hipStream_t s = c->stream;
   Call call(c, Call::kHost);
   HIP_TRY(call.open(), "hipStreamWaitEvent");
-  HIP_TRY(stage(c->h_txs, txs, sizeof(cg_tx) * n_tx, s), "H2D txs");
-  HIP_TRY(stage(c->h_comps, comps, sizeof(cg_component) * n_comps, s), "H2D comps");
-  HIP_TRY(stage(c->keys, keys, sizeof(cg_key) * n_keys, s), "H2D keys");
-  HIP_TRY(stage(c->h_sigs, sigs, sizeof(cg_txsig) * n_sigs, s), "H2D sigs");
-  HIP_TRY(stage(c->arena, arena, arena_len, s, arena_room(arena_len)), "H2D arena");
-  HIP_TRY(c->h_ids.ensure(32 * (n_tx ? n_tx : 1)), "hipMalloc(ids)");
-  HIP_TRY(c->h_txst.ensure(n_tx ? n_tx : 1), "hipMalloc(tx status)");
-  HIP_TRY(c->status.ensure(n_sigs ? n_sigs : 1), "hipMalloc(sig status)");
-  if (const int rc = verify_transactions_locked(
-          c, (const cg_tx*)c->h_txs.p, n_tx, (const cg_component*)c->h_comps.p, n_comps, (const cg_key*)c->keys.p, n_keys,
-          (const cg_txsig*)c->h_sigs.p, n_sigs, tmpls, n_tmpls, (const uint8_t*)c->arena.p, arena_len, mode,
-          (uint8_t*)c->h_ids.p, (uint8_t*)c->h_txst.p, (uint8_t*)c->status.p, s))
-    return rc;
-  if (n_tx) {
-    HIP_TRY(hipMemcpyAsync(ids_out, c->h_ids.p, 32 * n_tx, hipMemcpyDeviceToHost, s), "D2H ids");
-    HIP_TRY(hipMemcpyAsync(tx_status_out, c->h_txst.p, n_tx, hipMemcpyDeviceToHost, s), "D2H tx status");
+  HIP_TRY(stage(c->h_txs, h.txs, sizeof(cg_tx) * h.n_tx, s), "H2D txs");
+  HIP_TRY(stage(c->h_comps, h.comps, sizeof(cg_component) * h.n_comps, s), "H2D comps");
+  HIP_TRY(stage(c->keys, h.keys, sizeof(cg_key) * h.n_keys, s), "H2D keys");
+  HIP_TRY(stage(c->h_sigs, h.sigs, sizeof(cg_txsig) * h.n_sigs, s), "H2D sigs");
+  HIP_TRY(stage(c->arena, h.arena, h.arena_len, s, arena_room(h.arena_len)), "H2D arena");
+  HIP_TRY(c->h_ids.ensure(32 * (h.n_tx ? h.n_tx : 1)), "hipMalloc(ids)");
+  HIP_TRY(c->h_txst.ensure(h.n_tx ? h.n_tx : 1), "hipMalloc(tx status)");
+  HIP_TRY(c->status.ensure(h.n_sigs ? h.n_sigs : 1), "hipMalloc(sig status)");
+  TxnReq d = h;  // the staged copies
+  d.txs = (const cg_tx*)c->h_txs.p;
+  d.comps = (const cg_component*)c->h_comps.p;
+  d.keys = (const cg_key*)c->keys.p;
+  d.sigs = (const cg_txsig*)c->h_sigs.p;
+  d.arena = (const uint8_t*)c->arena.p;
+  d.ids = (uint8_t*)c->h_ids.p;
+  d.tx_status = (uint8_t*)c->h_txst.p;
+  d.sig_status = (uint8_t*)c->status.p;
+  if (const int rc = verify_transactions_locked(c, d, s)) return rc;
+  if (h.n_tx) {
+    HIP_TRY(hipMemcpyAsync(h.ids, d.ids, 32 * h.n_tx, hipMemcpyDeviceToHost, s), "D2H ids");
+    HIP_TRY(hipMemcpyAsync(h.tx_status, d.tx_status, h.n_tx, hipMemcpyDeviceToHost, s), "D2H tx status");
   }
-  if (n_sigs) HIP_TRY(hipMemcpyAsync(sig_status_out, c->status.p, n_sigs, hipMemcpyDeviceToHost, s), "D2H sig status");
+  if (h.n_sigs) HIP_TRY(hipMemcpyAsync(h.sig_status, d.sig_status, h.n_sigs, hipMemcpyDeviceToHost, s), "D2H sig status");
   HIP_TRY(call.close(), "hipEventRecord");
   HIP_TRY(hipStreamSynchronize(s), "hipStreamSynchronize");
   return CG_OK;
@@ -1284,18 +1307,13 @@ int cg_verify_transactions(cg_ctx* c, const cg_tx* txs, uint64_t n_tx, const cg_
                            uint64_t arena_len, uint32_t mode, uint8_t* ids_out, uint8_t* tx_status_out,
                            uint8_t* sig_status_out) {
   if (!c) return fail(CG_ERR_ARG, "cg_verify_transactions: ctx is NULL");
-  if (n_tx && (!txs || !ids_out || !tx_status_out)) return fail(CG_ERR_ARG, "cg_verify_transactions: NULL tx buffer");
-  if (n_sigs && (!sigs || !sig_status_out)) return fail(CG_ERR_ARG, "cg_verify_transactions: NULL sig buffer");
-  if (n_comps && !comps) return fail(CG_ERR_ARG, "cg_verify_transactions: comps is NULL");
-  if (n_keys && !keys) return fail(CG_ERR_ARG, "cg_verify_transactions: keys is NULL");
-  if (n_tmpls && !tmpls) return fail(CG_ERR_ARG, "cg_verify_transactions: templates is NULL");
-  if (arena_len && !arena) return fail(CG_ERR_ARG, "cg_verify_transactions: arena is NULL");
-  if (mode > CG_MODE_ISVALID) return fail(CG_ERR_ARG, "cg_verify_transactions: bad mode");
+  const TxnReq h = {txs,   n_tx,    comps, n_comps,   keys, n_keys,  sigs,          n_sigs,
+                    tmpls, n_tmpls, arena, arena_len, mode, ids_out, tx_status_out, sig_status_out};
+  if (const int a = txn_args("cg_verify_transactions", h, true)) return a;
   for (uint64_t i = 0; i < n_sigs; ++i) sig_status_out[i] = CG_NOT_RUN;
   if (n_tx == 0 && n_sigs == 0) return CG_OK;
   std::lock_guard<std::mutex> g(c->mu);
-  return verify_transactions_host_locked(c, txs, n_tx, comps, n_comps, keys, n_keys, sigs, n_sigs, tmpls, n_tmpls,
-                                         arena, arena_len, mode, ids_out, tx_status_out, sig_status_out);
+  return verify_transactions_host_locked(c, h);
 }
 
 // ---------------------------------------------------------------- signatures over known tx ids
@@ -1307,48 +1325,65 @@ static hipError_t ensure_txsig_ws(cg_ctx* c, uint64_t n_sigs, uint32_t n_tmpls, 
                      {&c->tmpls, sizeof(cg_signable_tmpl) * (n_tmpls ? n_tmpls : 1)}});
 }
 
-// Templates to the device (midstates + images), then the chunked verify: key tables sized from
-// `uses` (sampled from the signature table on the device, or the host's exact counts), each chunk's
-// verify items and spliced SignableData made just before its front (after `ready`, which the host
-// form uses to land the chunk's signature table slice and bytes).
-// The 12-byte table (cg_txsig_packed): d_sigs is null and `p12` says where the signatures sit: the
-// stream at arena offset sig_region, chunk k's first signature at stream offset (*chunk_base)[k] (host
-// form: the host sums the lengths as it scans each chunk) or every block's offset precomputed in
-// d_bases (device form).
-struct Packed12 {
-  const cg_txsig_packed* d_sigs = nullptr;
-  uint64_t sig_region = 0, sig_bytes_len = 0;
+// One tx-signature call (cg_verify_tx_signatures and its packed, device, pool and required-signatures
+// forms): the caller's tables, all in host memory or all in HBM but the templates (host memory in every
+// form). The 12-byte table's signatures are a dense stream of sig_bytes_len bytes: a buffer of its own
+// in the host forms (sig_bytes), a stretch of the arena in the device forms (sig_bytes_off). A pool
+// shard is a copy with the table, the status bytes and the stream narrowed.
+struct TxsigReq {
+  const cg_key* keys;
+  uint32_t n_keys;
+  const uint8_t* ids;
+  uint64_t n_ids;
+  cg::SigTable sigs;
+  uint64_t n_sigs;
+  const cg_signable_tmpl* tmpls;
+  uint32_t n_tmpls;
+  const uint8_t* arena;
+  uint64_t arena_len;
+  uint32_t mode;
+  uint8_t* status;
+  const uint8_t* sig_bytes = nullptr;
+  uint64_t sig_bytes_off = 0, sig_bytes_len = 0;
+};
+
+// How launch_txsig schedules a call: the chunk bounds, where the key-use counts come from (sampled
+// from the signature table on the device, or the host's exact counts), `ready` (the host form: run
+// before chunk k's items are made, it lands the chunk's signature-table slice and bytes), and for the
+// 12-byte table where the signatures start in the stream: chunk k's first one at (*chunk_base)[k] (host
+// form: the host sums the lengths as it scans each chunk) or every 256-record block's offset
+// precomputed in d_bases (device form).
+struct TxsigSched {
+  const std::vector<uint64_t>& bounds;
+  cg::KeyUses uses;
+  const std::function<hipError_t(uint64_t, uint64_t, uint64_t)>* ready = nullptr;
   const std::vector<uint64_t>* chunk_base = nullptr;
   const uint64_t* d_bases = nullptr;
 };
-static hipError_t launch_txsig(cg_ctx* c, const cg_key* d_keys, uint32_t n_keys, const uint8_t* d_ids, uint64_t n_ids,
-                               const cg_txsig* d_sigs, uint64_t n_sigs, const cg_signable_tmpl* tmpls,
-                               uint32_t n_tmpls, const uint8_t* d_arena, uint64_t arena_len, uint32_t mode,
-                               uint8_t* d_status, hipStream_t s, uint64_t slot, const cg::KeyUses& uses,
-                               const std::function<hipError_t(uint64_t, uint64_t, uint64_t)>* ready,
-                               const std::vector<uint64_t>* bounds = nullptr, const Packed12* p12 = nullptr) {
-  if (n_sigs == 0) return hipSuccess;
+// Templates to the device (midstates + images), then the chunked verify over the device tables `d`:
+// each chunk's verify items and spliced SignableData made just before its front.
+static hipError_t launch_txsig(cg_ctx* c, const TxsigReq& d, uint64_t slot, const TxsigSched& p, hipStream_t s) {
+  if (d.n_sigs == 0) return hipSuccess;
   hipError_t e = hipSuccess;
   const cg_signable_tmpl* dt = (const cg_signable_tmpl*)c->tmpls.p;
-  if (n_tmpls) e = hipMemcpyAsync(c->tmpls.p, tmpls, sizeof(cg_signable_tmpl) * n_tmpls, hipMemcpyHostToDevice, s);
+  if (d.n_tmpls) e = hipMemcpyAsync(c->tmpls.p, d.tmpls, sizeof(cg_signable_tmpl) * d.n_tmpls, hipMemcpyHostToDevice, s);
   if (e == hipSuccess)
-    e = cg::launch_tx_sig_templates(dt, n_tmpls, d_arena, arena_len, slot, d_ids, n_ids, (uint8_t*)c->msgs.p, s);
+    e = cg::launch_tx_sig_templates(dt, d.n_tmpls, d.arena, d.arena_len, slot, d.ids, d.n_ids, (uint8_t*)c->msgs.p, s);
   const std::function<hipError_t(uint64_t, uint64_t, uint64_t)> prepare = [&](uint64_t k, uint64_t first,
                                                                                uint64_t cnt) {
-    hipError_t r = ready ? (*ready)(k, first, cnt) : hipSuccess;
-    if (r == hipSuccess && p12)
-      r = cg::launch_tx_sig12_range(p12->d_sigs, first, cnt, p12->sig_region, p12->sig_bytes_len,
-                                    p12->chunk_base ? (*p12->chunk_base)[k] : 0, p12->d_bases, dt, n_tmpls, n_ids,
-                                    arena_len, (cg_item*)c->txitems.p, c->sig12ws.p, s);
+    hipError_t r = p.ready ? (*p.ready)(k, first, cnt) : hipSuccess;
+    if (r == hipSuccess && d.sigs.packed())
+      r = cg::launch_tx_sig12_range((const cg_txsig_packed*)d.sigs.p, first, cnt, d.sig_bytes_off, d.sig_bytes_len,
+                                    p.chunk_base ? (*p.chunk_base)[k] : 0, p.d_bases, dt, d.n_tmpls, d.n_ids,
+                                    d.arena_len, (cg_item*)c->txitems.p, c->sig12ws.p, s);
     else if (r == hipSuccess)
-      r = cg::launch_tx_sig_range(d_sigs, first, cnt, dt, n_tmpls, nullptr, n_ids, d_ids, arena_len, slot,
-                                  (cg_item*)c->txitems.p, (uint8_t*)c->msgs.p, s);
+      r = cg::launch_tx_sig_range((const cg_txsig*)d.sigs.p, first, cnt, dt, d.n_tmpls, nullptr, d.n_ids, d.ids,
+                                  d.arena_len, slot, (cg_item*)c->txitems.p, (uint8_t*)c->msgs.p, s);
     return r;
   };
-  if (e == hipSuccess)
-    e = launch_chunked(c, d_keys, n_keys, (const cg_item*)c->txitems.p, n_sigs, d_arena, arena_len, mode, d_status, s,
-                       (const uint8_t*)c->msgs.p, cg::tx_msgs_head(n_tmpls, slot), &prepare, &uses,
-                       bounds, ready != nullptr);
+  const cg::VerifyReq r = {d.keys, d.n_keys, (const cg_item*)c->txitems.p, d.n_sigs, d.arena, d.arena_len, d.mode,
+                           d.status, (const uint8_t*)c->msgs.p, cg::tx_msgs_head(d.n_tmpls, slot)};
+  if (e == hipSuccess) e = launch_chunked(c, r, p.bounds, s, ChunkOpts{&prepare, &p.uses, p.ready != nullptr});
   return e;
 }
 
@@ -1455,13 +1490,10 @@ struct TxsigFeed {
   cg_ctx* c;
   HostTrace& tr;
   const std::vector<uint64_t>& bounds;
-  // the caller's buffers: one of the two tables, the ids, the arena, the 12-byte form's stream
-  const cg_txsig* sigs = nullptr;
-  const cg_txsig_packed* sigs12 = nullptr;
-  const uint8_t *ids = nullptr, *arena = nullptr, *sig_bytes = nullptr;
-  uint64_t n_ids = 0, arena_len = 0, sig_region = 0, sig_bytes_len = 0;  // arena_len: what the kernels see
-  uint64_t nt = 1;  // host threads of the extent scans, run through `par`
-  cg::ParFor par;
+  const TxsigReq& h;  // the caller's buffers
+  const TxsigReq& d;  // what the kernels see: the arena's length, where the 12-byte form's stream follows it
+  const uint64_t nt;  // host threads of the extent scans, run through `par`
+  const cg::ParFor& par;
   std::vector<Extent> ext_e, ext_i;  // chunk k's signature bytes / id bytes
   // the 12-byte table: chunk k's first signature at stream offset cbase[k] (cbase[k + 1] is set when
   // chunk k's table slice is staged)
@@ -1474,9 +1506,10 @@ struct TxsigFeed {
     return before(k);
   };
 
-  bool packed() const { return sigs12 != nullptr; }
-  TxsigFeed(cg_ctx* ctx, HostTrace& trace, const std::vector<uint64_t>& b)
-      : c(ctx), tr(trace), bounds(b), ext_e(b.size() - 1), ext_i(b.size() - 1), cbase(b.size(), 0) {}
+  TxsigFeed(cg_ctx* ctx, HostTrace& trace, const std::vector<uint64_t>& b, const TxsigReq& host, const TxsigReq& dev,
+            uint64_t threads, const cg::ParFor& pf)
+      : c(ctx), tr(trace), bounds(b), h(host), d(dev), nt(threads), par(pf), ext_e(b.size() - 1),
+        ext_i(b.size() - 1), cbase(b.size(), 0) {}
   TxsigFeed(const TxsigFeed&) = delete;
   ~TxsigFeed() { c->fork.mid_front = nullptr; }  // no hook outlives the call, whatever the exit path
 
@@ -1484,21 +1517,19 @@ struct TxsigFeed {
   hipError_t copy_table(uint64_t k) {
     const uint64_t first = bounds[k], cnt = bounds[k + 1] - bounds[k];
     const double h0 = tr.ms();
-    const cg::ChunkScan x = packed() ? cg::scan_chunk(sigs12, first, first + cnt, n_ids, arena_len, nt, par)
-                                     : cg::scan_chunk(sigs, first, first + cnt, n_ids, arena_len, nt, par);
+    const cg::ChunkScan x = cg::with_records(h.sigs, [&](auto* recs) {
+      return cg::scan_chunk(recs, first, first + cnt, h.n_ids, d.arena_len, nt, par);
+    });
     ext_e[k] = x.sig;
     ext_i[k] = x.ids;
-    if (packed()) {  // the chunk's stream bytes, clipped to the caller's buffer (past it: CG_NOT_RUN)
+    if (h.sigs.packed()) {  // the chunk's stream bytes, clipped to the caller's buffer (past it: CG_NOT_RUN)
       cbase[k + 1] = cbase[k] + x.span;
       ext_e[k] = Extent();
-      ext_e[k].add(cbase[k], x.span, sig_bytes_len);
+      ext_e[k].add(cbase[k], x.span, h.sig_bytes_len);
     }
     const double h1 = tr.ms();
-    const hipError_t e =
-        packed() ? hipMemcpyAsync((cg_txsig_packed*)c->h_sigs.p + first, sigs12 + first, sizeof(cg_txsig_packed) * cnt,
-                                  hipMemcpyHostToDevice, c->copy)
-                 : hipMemcpyAsync((cg_txsig*)c->h_sigs.p + first, sigs + first, sizeof(cg_txsig) * cnt,
-                                  hipMemcpyHostToDevice, c->copy);
+    const hipError_t e = hipMemcpyAsync((uint8_t*)c->h_sigs.p + (size_t)h.sigs.stride * first, h.sigs.from(first).p,
+                                        (size_t)h.sigs.stride * cnt, hipMemcpyHostToDevice, c->copy);
     tr.table_staged(k, h0, h1);
     return e;
   }
@@ -1507,14 +1538,12 @@ struct TxsigFeed {
     const Extent& ek = ext_e[k];
     uint8_t* dwin = (uint8_t*)c->arena.p;  // the device arena mirrors [0, arena_len)
     const double h2 = tr.ms();
-    hipError_t e = copy_missing(have_ids, ext_i[k], ids, (uint8_t*)c->h_ids.p, 0, c->copy);
+    hipError_t e = copy_missing(have_ids, ext_i[k], h.ids, (uint8_t*)c->h_ids.p, 0, c->copy);
     const double h3 = tr.ms();
-    if (e == hipSuccess && packed()) e = copy_missing(have_sig, ek, sig_bytes, dwin + sig_region, 0, c->copy);
-    else if (e == hipSuccess) e = copy_missing(have, ek, arena, dwin, 0, c->copy);
+    if (e == hipSuccess && h.sigs.packed()) e = copy_missing(have_sig, ek, h.sig_bytes, dwin + d.sig_bytes_off, 0, c->copy);
+    else if (e == hipSuccess) e = copy_missing(have, ek, h.arena, dwin, 0, c->copy);
     if (e == hipSuccess) e = hipEventRecord(c->seg[k], c->copy);
-    if (e == hipSuccess)
-      e = tr.bytes_staged(k, c->copy, h2, h3,
-                          (packed() ? sizeof(cg_txsig_packed) : sizeof(cg_txsig)) * (bounds[k + 1] - bounds[k]) / 1e6, ek);
+    if (e == hipSuccess) e = tr.bytes_staged(k, c->copy, h2, h3, h.sigs.stride * (bounds[k + 1] - bounds[k]) / 1e6, ek);
     return e;
   }
   // the second half of chunk mid_k's staging: bytes copied, the front's stream ordered after them
@@ -1545,28 +1574,10 @@ struct TxsigFeed {
   }
 };
 
-// ---- per-transaction verdicts (txverdict.hip): the host forms' tables, staged in one buffer
-struct TxvHost {
-  const uint32_t* key_class = nullptr;
-  const cg_tx_check* checks = nullptr;
-  uint64_t n_tx = 0;
-  const uint32_t* reqs = nullptr;
-  uint32_t n_reqs = 0;
-  const cg_req_node* nodes = nullptr;
-  uint32_t n_nodes = 0;
-  cg_tx_verdict* verdicts_out = nullptr;
-  uint8_t* req_status_out = nullptr;
-};
-struct TxvDev {
-  uint32_t* key_class = nullptr;
-  cg_tx_check* checks = nullptr;
-  uint32_t* reqs = nullptr;
-  cg_req_node* nodes = nullptr;
-  cg_tx_verdict* verdicts = nullptr;
-  uint8_t* req_status = nullptr;
-};
+// ---- per-transaction verdicts (txverdict.hip): the host forms' tables (cg::TxvSet `h`), staged in one
+// buffer (`d`)
 // Carves c->txvio for the tables of `h` (waits for the device when it grows), and the list workspace.
-static hipError_t txv_stage(cg_ctx* c, const TxvHost& h, uint32_t n_keys, TxvDev* d) {
+static hipError_t txv_stage(cg_ctx* c, const cg::TxvSet& h, uint32_t n_keys, cg::TxvSet* d) {
   auto up = [](size_t x) { return (x + 15) & ~(size_t)15; };
   const size_t o_checks = 0, o_nodes = o_checks + up(sizeof(cg_tx_check) * h.n_tx),
                o_verd = o_nodes + up(sizeof(cg_req_node) * h.n_nodes),
@@ -1576,6 +1587,7 @@ static hipError_t txv_stage(cg_ctx* c, const TxvHost& h, uint32_t n_keys, TxvDev
   const hipError_t e = ensure_all({{&c->txvws, cg::tx_verdicts_ws_bytes(h.n_tx)}, {&c->txvio, need}});
   if (e != hipSuccess) return e;
   uint8_t* b = (uint8_t*)c->txvio.p;
+  *d = h;  // the counts
   d->checks = (cg_tx_check*)(b + o_checks);
   d->nodes = (cg_req_node*)(b + o_nodes);
   d->verdicts = (cg_tx_verdict*)(b + o_verd);
@@ -1584,58 +1596,58 @@ static hipError_t txv_stage(cg_ctx* c, const TxvHost& h, uint32_t n_keys, TxvDev
   d->req_status = b + o_rst;
   return hipSuccess;
 }
-static hipError_t txv_upload(const TxvHost& h, uint32_t n_keys, const TxvDev& d, hipStream_t s) {
+// (d's tables are the context's own buffer, carved by txv_stage: writable)
+static hipError_t txv_upload(const cg::TxvSet& h, uint32_t n_keys, const cg::TxvSet& d, hipStream_t s) {
   hipError_t e = hipSuccess;
-  if (h.n_tx) e = hipMemcpyAsync(d.checks, h.checks, sizeof(cg_tx_check) * h.n_tx, hipMemcpyHostToDevice, s);
+  if (h.n_tx) e = hipMemcpyAsync((void*)d.checks, h.checks, sizeof(cg_tx_check) * h.n_tx, hipMemcpyHostToDevice, s);
   if (e == hipSuccess && h.n_nodes)
-    e = hipMemcpyAsync(d.nodes, h.nodes, sizeof(cg_req_node) * h.n_nodes, hipMemcpyHostToDevice, s);
+    e = hipMemcpyAsync((void*)d.nodes, h.nodes, sizeof(cg_req_node) * h.n_nodes, hipMemcpyHostToDevice, s);
   if (e == hipSuccess && h.n_reqs)
-    e = hipMemcpyAsync(d.reqs, h.reqs, sizeof(uint32_t) * h.n_reqs, hipMemcpyHostToDevice, s);
+    e = hipMemcpyAsync((void*)d.reqs, h.reqs, sizeof(uint32_t) * h.n_reqs, hipMemcpyHostToDevice, s);
   if (e == hipSuccess && h.key_class && n_keys)
-    e = hipMemcpyAsync(d.key_class, h.key_class, sizeof(uint32_t) * n_keys, hipMemcpyHostToDevice, s);
+    e = hipMemcpyAsync((void*)d.key_class, h.key_class, sizeof(uint32_t) * n_keys, hipMemcpyHostToDevice, s);
   return e;
 }
-static hipError_t txv_download(const TxvHost& h, const TxvDev& d, hipStream_t s) {
+static hipError_t txv_download(const cg::TxvSet& h, const cg::TxvSet& d, hipStream_t s) {
   hipError_t e = hipSuccess;
-  if (h.n_tx) e = hipMemcpyAsync(h.verdicts_out, d.verdicts, sizeof(cg_tx_verdict) * h.n_tx, hipMemcpyDeviceToHost, s);
-  if (e == hipSuccess && h.n_reqs) e = hipMemcpyAsync(h.req_status_out, d.req_status, h.n_reqs, hipMemcpyDeviceToHost, s);
+  if (h.n_tx) e = hipMemcpyAsync(h.verdicts, d.verdicts, sizeof(cg_tx_verdict) * h.n_tx, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess && h.n_reqs) e = hipMemcpyAsync(h.req_status, d.req_status, h.n_reqs, hipMemcpyDeviceToHost, s);
   return e;
 }
 // what a call that failed leaves in the caller's result buffers: nothing ran
-static void txv_fill_not_run(const TxvHost& h) {
-  for (uint64_t t = 0; t < h.n_tx; ++t) h.verdicts_out[t] = cg_tx_verdict{0xFFFFFFFFu, CG_NOT_RUN, CG_TXV_SPAN_BAD, 0};
-  if (h.n_reqs) memset(h.req_status_out, CG_REQ_HOST, h.n_reqs);
+static void txv_fill_not_run(const cg::TxvSet& h) {
+  for (uint64_t t = 0; t < h.n_tx; ++t) h.verdicts[t] = cg_tx_verdict{0xFFFFFFFFu, CG_NOT_RUN, CG_TXV_SPAN_BAD, 0};
+  if (h.n_reqs) memset(h.req_status, CG_REQ_HOST, h.n_reqs);
 }
 
-// cg_verify_tx_signatures with the ctx lock held. Host side, in order: the key table and key bytes,
-// the template bytes, the ids and the signature table (everything the key tables and the plans
-// need), then the signature bytes chunk by chunk, each copy issued just before its chunk's front
-// so that the key-table builds and the previous chunk's kernels run during it.
-// The 12-byte form (cg_verify_tx_signatures_packed): sigs is null, sigs12 the table, the signatures
-// dense in sig_bytes. On the device they follow the caller's arena at sig_region (16-aligned), so the
-// kernels address every byte by an absolute arena offset as in the 24-byte form; a key or template
-// that lies outside [0, arena_len) is moved out of the extended arena too (never reads a signature).
-// txv (cg_verify_required_signatures_packed): the per-transaction verdict kernels follow the last chunk
-// on the same stream; their tables go up on the copy stream behind the last chunk's bytes. status_out
-// may then be null (the statuses stay on the device).
-static int verify_txsig_host_locked(cg_ctx* c, const cg_key* keys, uint32_t n_keys, const uint8_t* ids,
-                                    uint64_t n_ids, const cg_txsig* sigs, uint64_t n_sigs,
-                                    const cg_signable_tmpl* tmpls, uint32_t n_tmpls, const uint8_t* arena,
-                                    uint64_t arena_len, uint32_t mode, uint8_t* status_out, cg_stats* stats,
-                                    const cg_txsig_packed* sigs12 = nullptr, const uint8_t* sig_bytes = nullptr,
-                                    uint64_t sig_bytes_len = 0, const TxvHost* txv = nullptr) {
+// cg_verify_tx_signatures with the ctx lock held, over the caller's host buffers `q`. Host side, in
+// order: the key table and key bytes, the template bytes, the ids and the signature table (everything
+// the key tables and the plans need), then the signature bytes chunk by chunk, each copy issued just
+// before its chunk's front so that the key-table builds and the previous chunk's kernels run during it.
+// The 12-byte form (cg_verify_tx_signatures_packed): the signatures dense in q.sig_bytes. On the
+// device they follow the caller's arena at sig_region (16-aligned), so the kernels address every byte
+// by an absolute arena offset as in the 24-byte form; a key or template that lies outside [0,
+// arena_len) is moved out of the extended arena too (never reads a signature).
+// txv (cg_verify_required_signatures_packed; else null): the per-transaction verdict kernels follow the
+// last chunk on the same stream; their tables go up on the copy stream behind the last chunk's bytes.
+// q.status may then be null (the statuses stay on the device).
+static int verify_txsig_host_locked(cg_ctx* c, const TxsigReq& q, cg_stats* stats, const cg::TxvSet* txv) {
   const auto t0 = std::chrono::steady_clock::now();
-  const bool packed = sigs12 != nullptr;
-  const uint64_t caller_len = arena_len;
-  const uint64_t sig_region = packed ? ((arena_len + 15) & ~(uint64_t)15) : 0;
-  if (packed) arena_len = sig_region + sig_bytes_len;  // what the kernels see
+  const bool packed = q.sigs.packed();
+  const uint32_t n_keys = q.n_keys, n_tmpls = q.n_tmpls;
+  const uint64_t n_sigs = q.n_sigs, n_ids = q.n_ids;
+  TxsigReq h = q;  // the caller's buffers, its keys and templates fixed up
+  TxsigReq d = q;  // what the kernels see
+  d.sig_bytes_off = packed ? ((q.arena_len + 15) & ~(uint64_t)15) : 0;
+  if (packed) d.arena_len = d.sig_bytes_off + q.sig_bytes_len;
   std::vector<cg_key> keys_fix;
   std::vector<cg_signable_tmpl> tmpls_fix;
   if (packed) {  // out-of-arena keys / templates stay out of range in the extended arena
-    cg::txsig_packed_fixup(keys, n_keys, tmpls, n_tmpls, caller_len, keys_fix, tmpls_fix);
-    if (!keys_fix.empty()) keys = keys_fix.data();
-    if (!tmpls_fix.empty()) tmpls = tmpls_fix.data();
+    cg::txsig_packed_fixup(q.keys, n_keys, q.tmpls, n_tmpls, q.arena_len, keys_fix, tmpls_fix);
+    if (!keys_fix.empty()) h.keys = keys_fix.data();
+    if (!tmpls_fix.empty()) h.tmpls = tmpls_fix.data();
   }
+  d.tmpls = h.tmpls;
   if (const int rc = enter(c, "cg_verify_tx_signatures")) return rc;
   // chunk bounds (txsig_plan.h); `per`, the largest chunk, sizes the item workspaces
   static const uint64_t first_div = env_u64("CG_TXSIG_FIRST_DIV", cg::kTxsigFirstDiv);
@@ -1643,23 +1655,23 @@ static int verify_txsig_host_locked(cg_ctx* c, const cg_key* keys, uint32_t n_ke
   const uint64_t nch = bounds.size() - 1, per = cg::largest_chunk(bounds);
   // arena extents: key bytes + template bytes (the header), then each chunk's signature bytes, scanned
   // just before its copy, while the device works on the chunks before it
-  const Extent head = cg::txsig_head_extent(keys, n_keys, tmpls, n_tmpls, caller_len);
+  const Extent head = cg::txsig_head_extent(h.keys, n_keys, h.tmpls, n_tmpls, q.arena_len);
   // the budget's host threads (host_budget.h), on the context's pool (spawning 16 threads per scan
   // cost 0.35-0.5 ms a round)
   const uint64_t nt = host_threads_of(c, n_sigs);
   const cg::ParFor par = [c](uint64_t m, const std::function<void(uint64_t)>& fn) { host_par(c, m, fn); };
   std::vector<uint32_t> counts(n_keys ? n_keys : 1, 0u);
-  const uint64_t slot = tmpl_slot(tmpls, n_tmpls);
+  const uint64_t slot = tmpl_slot(h.tmpls, n_tmpls);
   HIP_TRY(c->keys.ensure(sizeof(cg_key) * (n_keys ? n_keys : 1)), "hipMalloc(keys)");
-  HIP_TRY(c->h_sigs.ensure((packed ? sizeof(cg_txsig_packed) : sizeof(cg_txsig)) * n_sigs), "hipMalloc(sigs)");
+  HIP_TRY(c->h_sigs.ensure(q.sigs.stride * n_sigs), "hipMalloc(sigs)");
   if (packed) HIP_TRY(c->sig12ws.ensure(cg::tx_sig12_scratch_bytes(per)), "hipMalloc(signature offsets)");
   HIP_TRY(c->aux1.ensure(sizeof(uint32_t) * counts.size()), "hipMalloc(key use counts)");
   HIP_TRY(c->h_ids.ensure(32 * (n_ids ? n_ids : 1)), "hipMalloc(ids)");
-  HIP_TRY(c->arena.ensure(arena_len + 16), "hipMalloc(arena window)");  // mirrors [0, arena_len): only referenced bytes are copied
+  HIP_TRY(c->arena.ensure(d.arena_len + 16), "hipMalloc(arena window)");  // mirrors [0, arena_len): only referenced bytes are copied
   HIP_TRY(c->status.ensure(n_sigs), "hipMalloc(status)");
   HIP_TRY(ensure_txsig_ws(c, n_sigs, n_tmpls, slot), "hipMalloc(tx signature workspace)");
   HIP_TRY(ensure_ws(c, n_keys, per, n_sigs), "hipMalloc(workspace)");
-  TxvDev txd;
+  cg::TxvSet txd;
   if (txv) HIP_TRY(txv_stage(c, *txv, n_keys, &txd), "hipMalloc(verdict tables)");
   HIP_TRY(ensure_events(c->seg, nch + 1), "hipEventCreate");
   HIP_TRY(ensure_events(c->segtab, nch), "hipEventCreate");
@@ -1667,26 +1679,19 @@ static int verify_txsig_host_locked(cg_ctx* c, const cg_key* keys, uint32_t n_ke
   HostTrace tr{c, t0, htrace, {}};
   HIP_TRY(tr.begin(nch), "hipEventCreate");
   hipStream_t s = c->stream;
-  const uint8_t* dbase = (const uint8_t*)c->arena.p;  // kernels index the arena by absolute offsets
+  d.keys = (const cg_key*)c->keys.p;
+  d.ids = (const uint8_t*)c->h_ids.p;
+  d.sigs.p = c->h_sigs.p;
+  d.arena = (const uint8_t*)c->arena.p;  // kernels index the arena by absolute offsets
+  d.status = (uint8_t*)c->status.p;
   Call call(c, Call::kHost);
   HIP_TRY(call.open(), "hipStreamWaitEvent");
   HIP_TRY(hipEventRecord(c->tev[0], s), "hipEventRecord");
   HIP_TRY(hipStreamWaitEvent(c->copy, c->tev[0], 0), "hipStreamWaitEvent");
-  TxsigFeed feed(c, tr, bounds);
-  feed.sigs = sigs;
-  feed.sigs12 = sigs12;
-  feed.ids = ids;
-  feed.arena = arena;
-  feed.sig_bytes = sig_bytes;
-  feed.n_ids = n_ids;
-  feed.arena_len = arena_len;
-  feed.sig_region = sig_region;
-  feed.sig_bytes_len = sig_bytes_len;
-  feed.nt = nt;
-  feed.par = par;
+  TxsigFeed feed(c, tr, bounds, h, d, nt, par);
   if (n_keys)
-    HIP_TRY(hipMemcpyAsync(c->keys.p, keys, sizeof(cg_key) * n_keys, hipMemcpyHostToDevice, c->copy), "H2D keys");
-  HIP_TRY(copy_missing(feed.have, head, arena, (uint8_t*)c->arena.p, 0, c->copy), "H2D key / template bytes");
+    HIP_TRY(hipMemcpyAsync(c->keys.p, h.keys, sizeof(cg_key) * n_keys, hipMemcpyHostToDevice, c->copy), "H2D keys");
+  HIP_TRY(copy_missing(feed.have, head, h.arena, (uint8_t*)c->arena.p, 0, c->copy), "H2D key / template bytes");
   // The key-use counts (txsig_plan.h) gate only the key tables; chunk 0's bytes gate everything else.
   // (Sampling the counts while chunk 0 copies, on a second copy stream with a pinned counts buffer,
   // measured slower on the configs[4] shard: 197 / 205 vs 213 / 220 M sigs/s, profiles/r03/ab_sc: the
@@ -1696,35 +1701,22 @@ static int verify_txsig_host_locked(cg_ctx* c, const cg_key* keys, uint32_t n_ke
     static const uint32_t B = cg::sample_block((uint32_t)env_u64("CG_TXSIG_SAMPLE_BLOCK", cg::kTxsigSampleBlock));
     const uint32_t S = cg::sample_rate(S_env, n_sigs, n_keys);
     const cg::WidePool thr = c->eng->make_wide_pool(nullptr, n_keys, n_sigs, cg::kKeyWideMax, 0);  // the wide thresholds
-    if (packed)
-      cg::key_use_counts(sigs12, n_sigs, keys, n_keys, nt, par, S, B, thr.min_ed, thr.min_ec, c->count_scratch,
+    cg::with_records(h.sigs, [&](auto* recs) {
+      cg::key_use_counts(recs, n_sigs, h.keys, n_keys, nt, par, S, B, thr.min_ed, thr.min_ec, c->count_scratch,
                          counts.data());
-    else
-      cg::key_use_counts(sigs, n_sigs, keys, n_keys, nt, par, S, B, thr.min_ed, thr.min_ec, c->count_scratch,
-                         counts.data());
+    });
   }
   const double ms_plan = ms_since(t0);  // host-side planning: the key-use sample pass
   HIP_TRY(hipMemcpyAsync(c->aux1.p, counts.data(), sizeof(uint32_t) * counts.size(), hipMemcpyHostToDevice, c->copy),
           "H2D key use counts");
   HIP_TRY(hipEventRecord(c->seg[nch], c->copy), "hipEventRecord");
   HIP_TRY(hipStreamWaitEvent(s, c->seg[nch], 0), "hipStreamWaitEvent");
-  uint8_t* ds = (uint8_t*)c->status.p;
-  cg::KeyUses uses;
-  uses.counts = (const uint32_t*)c->aux1.p;
-  uses.n = n_sigs;
-  uses.host_keys = keys;
-  uses.host_counts = counts.data();
-  Packed12 p12;
-  if (packed) {
-    p12.d_sigs = (const cg_txsig_packed*)c->h_sigs.p;
-    p12.sig_region = sig_region;
-    p12.sig_bytes_len = sig_bytes_len;
-    p12.chunk_base = &feed.cbase;
-  }
-  const hipError_t le = launch_txsig(c, (const cg_key*)c->keys.p, n_keys, (const uint8_t*)c->h_ids.p, n_ids,
-                                     packed ? nullptr : (const cg_txsig*)c->h_sigs.p, n_sigs, tmpls, n_tmpls, dbase,
-                                     arena_len, mode, ds, s, slot, uses, &feed.before_hook, &bounds,
-                                     packed ? &p12 : nullptr);
+  TxsigSched sched{bounds, {}, &feed.before_hook, packed ? &feed.cbase : nullptr, nullptr};
+  sched.uses.counts = (const uint32_t*)c->aux1.p;
+  sched.uses.n = n_sigs;
+  sched.uses.host_keys = h.keys;
+  sched.uses.host_counts = counts.data();
+  const hipError_t le = launch_txsig(c, d, slot, sched, s);
   if (le == hipSuccess && c->fork.mid_front) feed.mid();  // the last front did not consume its hook
   if (feed.copy_err != hipSuccess) return hip_fail(feed.copy_err, "H2D signature bytes");
   HIP_TRY(le, "launch_txsig");
@@ -1732,13 +1724,10 @@ static int verify_txsig_host_locked(cg_ctx* c, const cg_key* keys, uint32_t n_ke
     HIP_TRY(txv_upload(*txv, n_keys, txd, c->copy), "H2D verdict tables");
     HIP_TRY(hipEventRecord(c->seg[nch], c->copy), "hipEventRecord");
     HIP_TRY(hipStreamWaitEvent(s, c->seg[nch], 0), "hipStreamWaitEvent");
-    HIP_TRY(cg::launch_tx_verdicts(c->h_sigs.p, (uint32_t)sizeof(cg_txsig_packed), n_sigs, ds, (const cg_key*)c->keys.p,
-                                   n_keys, txd.key_class, txd.checks, (uint32_t)txv->n_tx, txd.reqs, txv->n_reqs,
-                                   txd.nodes, txv->n_nodes, txd.verdicts, txd.req_status, c->txvws.p, s),
-            "launch_tx_verdicts");
+    HIP_TRY(cg::launch_tx_verdicts(d.sigs, n_sigs, d.status, d.keys, n_keys, txd, c->txvws.p, s), "launch_tx_verdicts");
   }
   HIP_TRY(hipEventRecord(c->tev[2], s), "hipEventRecord");
-  if (status_out) HIP_TRY(hipMemcpyAsync(status_out, ds, n_sigs, hipMemcpyDeviceToHost, s), "D2H status");
+  if (q.status) HIP_TRY(hipMemcpyAsync(q.status, d.status, n_sigs, hipMemcpyDeviceToHost, s), "D2H status");
   if (txv) HIP_TRY(txv_download(*txv, txd, s), "D2H verdicts");
   HIP_TRY(hipEventRecord(c->tev[3], s), "hipEventRecord");
   HIP_TRY(call.close(), "hipEventRecord");
@@ -1749,17 +1738,25 @@ static int verify_txsig_host_locked(cg_ctx* c, const cg_key* keys, uint32_t n_ke
   return CG_OK;
 }
 
-
-static int txsig_args(const char* fn, cg_ctx* c, uint32_t n_keys, const void* keys, uint64_t n_ids, const void* ids,
-                      uint64_t n_sigs, const void* sigs, const void* status, uint32_t n_tmpls, const void* tmpls,
-                      uint32_t mode) {
+// The argument checks of the tx-signature family: what every form checks (need_status: the status
+// buffer must be there when there are signatures), then what only the forms over host buffers (which
+// the library reads itself) or only the device forms (the 12-byte table's stream) check.
+static int txsig_args(const char* fn, cg_ctx* c, const TxsigReq& q, bool need_status = true) {
   if (!c) return fail(CG_ERR_ARG, "%s: ctx is NULL", fn);
-  if (n_sigs && (!sigs || !status)) return fail(CG_ERR_ARG, "%s: NULL signature / status buffer", fn);
-  if (n_keys && !keys) return fail(CG_ERR_ARG, "%s: keys is NULL", fn);
-  if (n_ids && !ids) return fail(CG_ERR_ARG, "%s: ids is NULL", fn);
-  if (n_tmpls && !tmpls) return fail(CG_ERR_ARG, "%s: templates is NULL", fn);
-  if (n_tmpls > 0x10000u) return fail(CG_ERR_ARG, "%s: more than 65536 templates (cg_txsig.tmpl is 16-bit)", fn);
-  if (mode > CG_MODE_ISVALID) return fail(CG_ERR_ARG, "%s: bad mode", fn);
+  if (q.n_sigs && (!q.sigs.p || (need_status && !q.status)))
+    return fail(CG_ERR_ARG, "%s: NULL signature / status buffer", fn);
+  if (q.n_keys && !q.keys) return fail(CG_ERR_ARG, "%s: keys is NULL", fn);
+  if (q.n_ids && !q.ids) return fail(CG_ERR_ARG, "%s: ids is NULL", fn);
+  if (q.n_tmpls && !q.tmpls) return fail(CG_ERR_ARG, "%s: templates is NULL", fn);
+  if (q.n_tmpls > 0x10000u) return fail(CG_ERR_ARG, "%s: more than 65536 templates (cg_txsig.tmpl is 16-bit)", fn);
+  if (q.mode > CG_MODE_ISVALID) return fail(CG_ERR_ARG, "%s: bad mode", fn);
+  return CG_OK;
+}
+static int txsig_buffer_args(const char* fn, const TxsigReq& q, bool host) {
+  if (host && q.arena_len && !q.arena) return fail(CG_ERR_ARG, "%s: arena is NULL", fn);
+  if (host && q.sig_bytes_len && !q.sig_bytes) return fail(CG_ERR_ARG, "%s: sig_bytes is NULL", fn);
+  if (!host && (q.sig_bytes_off > q.arena_len || q.sig_bytes_len > q.arena_len - q.sig_bytes_off))
+    return fail(CG_ERR_ARG, "%s: the signature stream lies outside the arena", fn);
   return CG_OK;
 }
 
@@ -1767,61 +1764,49 @@ int cg_verify_tx_signatures_device(cg_ctx* c, const cg_key* d_keys, uint32_t n_k
                                    uint64_t n_ids, const cg_txsig* d_sigs, uint64_t n_sigs,
                                    const cg_signable_tmpl* tmpls, uint32_t n_tmpls, const uint8_t* d_arena,
                                    uint64_t arena_len, uint32_t mode, uint8_t* d_status, void* hip_stream) {
-  const int a = txsig_args("cg_verify_tx_signatures_device", c, n_keys, d_keys, n_ids, d_ids, n_sigs, d_sigs, d_status,
-                           n_tmpls, tmpls, mode);
-  if (a != CG_OK) return a;
+  const TxsigReq d = {d_keys, n_keys,  d_ids,   n_ids,     {d_sigs, (uint32_t)sizeof(cg_txsig)}, n_sigs,
+                      tmpls,  n_tmpls, d_arena, arena_len, mode,                                 d_status};
+  if (const int a = txsig_args("cg_verify_tx_signatures_device", c, d)) return a;
   if (n_sigs == 0) return CG_OK;
   std::lock_guard<std::mutex> g(c->mu);
   if (const int rc = enter(c, "cg_verify_tx_signatures_device")) return rc;
   const uint64_t slot = tmpl_slot(tmpls, n_tmpls);
+  const std::vector<uint64_t> bounds = cg::equal_bounds(n_sigs, chunk_of(c, n_sigs));
   HIP_TRY(ensure_txsig_ws(c, n_sigs, n_tmpls, slot), "hipMalloc(tx signature workspace)");
   HIP_TRY(ensure_ws(c, n_keys, chunk_of(c, n_sigs), n_sigs), "hipMalloc(workspace)");
   Call call(c, Call::kDevice);
   HIP_TRY(call.open(hip_stream), "hipStreamWaitEvent");
-  cg::KeyUses uses;
-  uses.sigs = d_sigs;
-  uses.n = n_sigs;
-  HIP_TRY(launch_txsig(c, d_keys, n_keys, d_ids, n_ids, d_sigs, n_sigs, tmpls, n_tmpls, d_arena, arena_len, mode,
-                       d_status, call.stream(), slot, uses, nullptr),
-          "launch_txsig");
+  TxsigSched sched{bounds, {}};
+  sched.uses.sigs = d.sigs;
+  sched.uses.n = n_sigs;
+  HIP_TRY(launch_txsig(c, d, slot, sched, call.stream()), "launch_txsig");
   HIP_TRY(call.close(), "hipEventRecord");
   return CG_OK;
 }
 
-// The two halves of a packed device call, with the ctx lock held and the device set: the chunk bounds
-// and the workspace before the call opens, then every launch up to the last chunk's back on `s`.
-static hipError_t txsig_packed_device_ws(cg_ctx* c, uint32_t n_keys, uint64_t n_sigs, uint32_t n_tmpls, uint64_t slot,
-                                         std::vector<uint64_t>& bounds) {
-  if (n_sigs == 0) return hipSuccess;
+// The two halves of a packed device call over the device tables `d`, with the ctx lock held and the
+// device set: the chunk bounds and the workspace before the call opens, then every launch up to the
+// last chunk's back on `s`.
+static hipError_t txsig_packed_device_ws(cg_ctx* c, const TxsigReq& d, uint64_t slot, std::vector<uint64_t>& bounds) {
+  if (d.n_sigs == 0) return hipSuccess;
   // equal chunks rounded to the 256-record blocks whose stream offsets are computed once for the table
-  uint64_t per = chunk_of(c, n_sigs);
-  per = (per + 255) & ~(uint64_t)255;
-  for (uint64_t f = 0; f < n_sigs; f += per) bounds.push_back(f);
-  bounds.push_back(n_sigs);
-  hipError_t e = ensure_txsig_ws(c, n_sigs, n_tmpls, slot);
-  if (e == hipSuccess) e = ensure_ws(c, n_keys, per, n_sigs);
-  if (e == hipSuccess) e = c->sig12ws.ensure(cg::tx_sig12_scratch_bytes(n_sigs));
+  const uint64_t per = (chunk_of(c, d.n_sigs) + 255) & ~(uint64_t)255;
+  bounds = cg::equal_bounds(d.n_sigs, per);
+  hipError_t e = ensure_txsig_ws(c, d.n_sigs, d.n_tmpls, slot);
+  if (e == hipSuccess) e = ensure_ws(c, d.n_keys, per, d.n_sigs);
+  if (e == hipSuccess) e = c->sig12ws.ensure(cg::tx_sig12_scratch_bytes(d.n_sigs));
   return e;
 }
-static hipError_t launch_txsig_packed_device(cg_ctx* c, const cg_key* d_keys, uint32_t n_keys, const uint8_t* d_ids,
-                                             uint64_t n_ids, const cg_txsig_packed* d_sigs, uint64_t n_sigs,
-                                             uint64_t sig_bytes_off, uint64_t sig_bytes_len,
-                                             const cg_signable_tmpl* tmpls, uint32_t n_tmpls, const uint8_t* d_arena,
-                                             uint64_t arena_len, uint32_t mode, uint8_t* d_status, uint64_t slot,
+static hipError_t launch_txsig_packed_device(cg_ctx* c, const TxsigReq& d, uint64_t slot,
                                              const std::vector<uint64_t>& bounds, hipStream_t s) {
-  if (n_sigs == 0) return hipSuccess;
-  const hipError_t e = cg::launch_tx_sig12_bases(d_sigs, 0, n_sigs, 0, (uint64_t*)c->sig12ws.p, s);
+  if (d.n_sigs == 0) return hipSuccess;
+  const hipError_t e =
+      cg::launch_tx_sig12_bases((const cg_txsig_packed*)d.sigs.p, 0, d.n_sigs, 0, (uint64_t*)c->sig12ws.p, s);
   if (e != hipSuccess) return e;
-  cg::KeyUses uses;
-  uses.sigs12 = d_sigs;
-  uses.n = n_sigs;
-  Packed12 p12;
-  p12.d_sigs = d_sigs;
-  p12.sig_region = sig_bytes_off;
-  p12.sig_bytes_len = sig_bytes_len;
-  p12.d_bases = (const uint64_t*)c->sig12ws.p;
-  return launch_txsig(c, d_keys, n_keys, d_ids, n_ids, nullptr, n_sigs, tmpls, n_tmpls, d_arena, arena_len, mode,
-                      d_status, s, slot, uses, nullptr, &bounds, &p12);
+  TxsigSched sched{bounds, {}, nullptr, nullptr, (const uint64_t*)c->sig12ws.p};
+  sched.uses.sigs = d.sigs;
+  sched.uses.n = d.n_sigs;
+  return launch_txsig(c, d, slot, sched, s);
 }
 
 int cg_verify_tx_signatures_packed_device(cg_ctx* c, const cg_key* d_keys, uint32_t n_keys, const uint8_t* d_ids,
@@ -1829,24 +1814,33 @@ int cg_verify_tx_signatures_packed_device(cg_ctx* c, const cg_key* d_keys, uint3
                                           uint64_t sig_bytes_off, uint64_t sig_bytes_len,
                                           const cg_signable_tmpl* tmpls, uint32_t n_tmpls, const uint8_t* d_arena,
                                           uint64_t arena_len, uint32_t mode, uint8_t* d_status, void* hip_stream) {
-  const int a = txsig_args("cg_verify_tx_signatures_packed_device", c, n_keys, d_keys, n_ids, d_ids, n_sigs, d_sigs,
-                           d_status, n_tmpls, tmpls, mode);
+  const char* fn = "cg_verify_tx_signatures_packed_device";
+  const TxsigReq d = {d_keys,  n_keys,  d_ids,     n_ids, {d_sigs, (uint32_t)sizeof(cg_txsig_packed)}, n_sigs,  tmpls,
+                      n_tmpls, d_arena, arena_len, mode,  d_status, nullptr, sig_bytes_off, sig_bytes_len};
+  int a = txsig_args(fn, c, d);
+  if (a == CG_OK) a = txsig_buffer_args(fn, d, false);
   if (a != CG_OK) return a;
-  if (sig_bytes_off > arena_len || sig_bytes_len > arena_len - sig_bytes_off)
-    return fail(CG_ERR_ARG, "cg_verify_tx_signatures_packed_device: the signature stream lies outside the arena");
   if (n_sigs == 0) return CG_OK;
   std::lock_guard<std::mutex> g(c->mu);
-  if (const int rc = enter(c, "cg_verify_tx_signatures_packed_device")) return rc;
+  if (const int rc = enter(c, fn)) return rc;
   const uint64_t slot = tmpl_slot(tmpls, n_tmpls);
   std::vector<uint64_t> bounds;
-  HIP_TRY(txsig_packed_device_ws(c, n_keys, n_sigs, n_tmpls, slot, bounds), "hipMalloc(tx signature workspace)");
+  HIP_TRY(txsig_packed_device_ws(c, d, slot, bounds), "hipMalloc(tx signature workspace)");
   Call call(c, Call::kDevice);
   HIP_TRY(call.open(hip_stream), "hipStreamWaitEvent");
-  HIP_TRY(launch_txsig_packed_device(c, d_keys, n_keys, d_ids, n_ids, d_sigs, n_sigs, sig_bytes_off, sig_bytes_len, tmpls,
-                                     n_tmpls, d_arena, arena_len, mode, d_status, slot, bounds, call.stream()),
-          "launch_txsig");
+  HIP_TRY(launch_txsig_packed_device(c, d, slot, bounds, call.stream()), "launch_txsig");
   HIP_TRY(call.close(), "hipEventRecord");
   return CG_OK;
+}
+
+// cg_verify_tx_signatures and its packed form over the caller's host buffers `h`, arguments checked
+static int verify_txsig_host(cg_ctx* c, const TxsigReq& h, cg_stats* stats) {
+  if (h.n_sigs) memset(h.status, CG_NOT_RUN, h.n_sigs);
+  if (h.n_sigs == 0) return CG_OK;
+  std::lock_guard<std::mutex> g(c->mu);
+  const int rc = verify_txsig_host_locked(c, h, stats, nullptr);
+  if (rc != CG_OK) memset(h.status, CG_NOT_RUN, h.n_sigs);
+  return rc;
 }
 
 int cg_verify_tx_signatures_packed(cg_ctx* c, const cg_key* keys, uint32_t n_keys, const uint8_t* ids, uint64_t n_ids,
@@ -1854,55 +1848,42 @@ int cg_verify_tx_signatures_packed(cg_ctx* c, const cg_key* keys, uint32_t n_key
                                    uint64_t sig_bytes_len, const cg_signable_tmpl* tmpls, uint32_t n_tmpls,
                                    const uint8_t* arena, uint64_t arena_len, uint32_t mode, uint8_t* status_out,
                                    cg_stats* stats) {
-  const int a = txsig_args("cg_verify_tx_signatures_packed", c, n_keys, keys, n_ids, ids, n_sigs, sigs, status_out,
-                           n_tmpls, tmpls, mode);
-  if (a != CG_OK) return a;
-  if (arena_len && !arena) return fail(CG_ERR_ARG, "cg_verify_tx_signatures_packed: arena is NULL");
-  if (sig_bytes_len && !sig_bytes) return fail(CG_ERR_ARG, "cg_verify_tx_signatures_packed: sig_bytes is NULL");
-  if (n_sigs) memset(status_out, CG_NOT_RUN, n_sigs);
-  if (n_sigs == 0) return CG_OK;
-  std::lock_guard<std::mutex> g(c->mu);
-  const int rc = verify_txsig_host_locked(c, keys, n_keys, ids, n_ids, nullptr, n_sigs, tmpls, n_tmpls, arena,
-                                          arena_len, mode, status_out, stats, sigs, sig_bytes, sig_bytes_len);
-  if (rc != CG_OK) memset(status_out, CG_NOT_RUN, n_sigs);
-  return rc;
+  const char* fn = "cg_verify_tx_signatures_packed";
+  const TxsigReq h = {keys,    n_keys, ids,       n_ids, {sigs, (uint32_t)sizeof(cg_txsig_packed)}, n_sigs,    tmpls,
+                      n_tmpls, arena,  arena_len, mode,  status_out, sig_bytes, 0, sig_bytes_len};
+  int a = txsig_args(fn, c, h);
+  if (a == CG_OK) a = txsig_buffer_args(fn, h, true);
+  return a != CG_OK ? a : verify_txsig_host(c, h, stats);
 }
 
 int cg_verify_tx_signatures(cg_ctx* c, const cg_key* keys, uint32_t n_keys, const uint8_t* ids, uint64_t n_ids,
                             const cg_txsig* sigs, uint64_t n_sigs, const cg_signable_tmpl* tmpls, uint32_t n_tmpls,
                             const uint8_t* arena, uint64_t arena_len, uint32_t mode, uint8_t* status_out,
                             cg_stats* stats) {
-  const int a = txsig_args("cg_verify_tx_signatures", c, n_keys, keys, n_ids, ids, n_sigs, sigs, status_out, n_tmpls,
-                           tmpls, mode);
-  if (a != CG_OK) return a;
-  if (arena_len && !arena) return fail(CG_ERR_ARG, "cg_verify_tx_signatures: arena is NULL");
-  if (n_sigs) memset(status_out, CG_NOT_RUN, n_sigs);
-  if (n_sigs == 0) return CG_OK;
-  std::lock_guard<std::mutex> g(c->mu);
-  const int rc = verify_txsig_host_locked(c, keys, n_keys, ids, n_ids, sigs, n_sigs, tmpls, n_tmpls, arena, arena_len,
-                                          mode, status_out, stats);
-  if (rc != CG_OK) memset(status_out, CG_NOT_RUN, n_sigs);
-  return rc;
+  const char* fn = "cg_verify_tx_signatures";
+  const TxsigReq h = {keys,  n_keys,  ids,   n_ids,     {sigs, (uint32_t)sizeof(cg_txsig)}, n_sigs,
+                      tmpls, n_tmpls, arena, arena_len, mode,                               status_out};
+  int a = txsig_args(fn, c, h);
+  if (a == CG_OK) a = txsig_buffer_args(fn, h, true);
+  return a != CG_OK ? a : verify_txsig_host(c, h, stats);
 }
 
 // ---------------------------------------------------------------- per-transaction verdicts
-static int txv_args(const char* fn, uint32_t sig_stride, uint64_t n_sigs, const void* sig_table, const void* status,
-                    uint32_t n_keys, const void* keys, uint64_t n_tx, const void* checks, uint32_t n_reqs,
-                    const void* reqs, uint32_t n_nodes, const void* nodes, const void* verdicts,
-                    const void* req_status) {
-  if (sig_stride != sizeof(cg_txsig_packed) && sig_stride != sizeof(cg_txsig))
+static int txv_args(const char* fn, const cg::SigTable& sigs, uint64_t n_sigs, const void* status, uint32_t n_keys,
+                    const void* keys, const cg::TxvSet& t) {
+  if (sigs.stride != sizeof(cg_txsig_packed) && sigs.stride != sizeof(cg_txsig))
     return fail(CG_ERR_ARG, "%s: sig_stride is neither 12 (cg_txsig_packed) nor 24 (cg_txsig)", fn);
-  if (n_sigs && (!sig_table || !status)) return fail(CG_ERR_ARG, "%s: NULL signature table / status", fn);
+  if (n_sigs && (!sigs.p || !status)) return fail(CG_ERR_ARG, "%s: NULL signature table / status", fn);
   if (n_keys && !keys) return fail(CG_ERR_ARG, "%s: keys is NULL", fn);
-  if (n_tx && (!checks || !verdicts)) return fail(CG_ERR_ARG, "%s: NULL checks / verdicts", fn);
-  if (n_tx > 0xFFFFFFFFull) return fail(CG_ERR_ARG, "%s: more than 2^32 - 1 transactions", fn);
-  if (n_reqs && (!reqs || !req_status)) return fail(CG_ERR_ARG, "%s: NULL reqs / req_status", fn);
-  if (n_nodes && !nodes) return fail(CG_ERR_ARG, "%s: nodes is NULL", fn);
+  if (t.n_tx && (!t.checks || !t.verdicts)) return fail(CG_ERR_ARG, "%s: NULL checks / verdicts", fn);
+  if (t.n_tx > 0xFFFFFFFFull) return fail(CG_ERR_ARG, "%s: more than 2^32 - 1 transactions", fn);
+  if (t.n_reqs && (!t.reqs || !t.req_status)) return fail(CG_ERR_ARG, "%s: NULL reqs / req_status", fn);
+  if (t.n_nodes && !t.nodes) return fail(CG_ERR_ARG, "%s: nodes is NULL", fn);
   return CG_OK;
 }
-static int txv_reserved(const char* fn, const cg_tx_check* checks, uint64_t n_tx) {
-  for (uint64_t t = 0; t < n_tx; ++t)
-    if (checks[t].reserved != 0) return fail(CG_ERR_ARG, "%s: cg_tx_check.reserved must be 0", fn);
+static int txv_reserved(const char* fn, const cg::TxvSet& t) {
+  for (uint64_t k = 0; k < t.n_tx; ++k)
+    if (t.checks[k].reserved != 0) return fail(CG_ERR_ARG, "%s: cg_tx_check.reserved must be 0", fn);
   return CG_OK;
 }
 
@@ -1912,38 +1893,35 @@ int cg_tx_verdicts_device(cg_ctx* c, const void* d_sig_table, uint32_t sig_strid
                           const cg_req_node* d_nodes, uint32_t n_nodes, cg_tx_verdict* d_verdicts,
                           uint8_t* d_req_status, void* hip_stream) {
   if (!c) return fail(CG_ERR_ARG, "cg_tx_verdicts_device: ctx is NULL");
-  const int a = txv_args("cg_tx_verdicts_device", sig_stride, n_sigs, d_sig_table, d_status, n_keys, d_keys, n_tx,
-                         d_checks, n_reqs, d_reqs, n_nodes, d_nodes, d_verdicts, d_req_status);
-  if (a != CG_OK) return a;
+  const cg::SigTable sigs = {d_sig_table, sig_stride};
+  const cg::TxvSet d = {d_key_class, d_checks, n_tx, d_reqs, n_reqs, d_nodes, n_nodes, d_verdicts, d_req_status};
+  if (const int a = txv_args("cg_tx_verdicts_device", sigs, n_sigs, d_status, n_keys, d_keys, d)) return a;
   if (n_tx == 0 && n_reqs == 0) return CG_OK;
   std::lock_guard<std::mutex> g(c->mu);
   if (const int rc = enter(c, "cg_tx_verdicts_device")) return rc;
   HIP_TRY(ensure_all({{&c->txvws, cg::tx_verdicts_ws_bytes(n_tx)}}), "hipMalloc(verdict workspace)");
   Call call(c, Call::kDevice);
   HIP_TRY(call.open(hip_stream), "hipStreamWaitEvent");
-  HIP_TRY(cg::launch_tx_verdicts(d_sig_table, sig_stride, n_sigs, d_status, d_keys, n_keys, d_key_class, d_checks,
-                                 (uint32_t)n_tx, d_reqs, n_reqs, d_nodes, n_nodes, d_verdicts, d_req_status,
-                                 c->txvws.p, call.stream()),
+  HIP_TRY(cg::launch_tx_verdicts(sigs, n_sigs, d_status, d_keys, n_keys, d, c->txvws.p, call.stream()),
           "launch_tx_verdicts");
   HIP_TRY(call.close(), "hipEventRecord");
   return CG_OK;
 }
 
-static int tx_verdicts_host_locked(cg_ctx* c, const void* sig_table, uint32_t sig_stride, uint64_t n_sigs,
-                                   const uint8_t* status, const cg_key* keys, uint32_t n_keys, const TxvHost& h) {
+static int tx_verdicts_host_locked(cg_ctx* c, const cg::SigTable& sigs, uint64_t n_sigs, const uint8_t* status,
+                                   const cg_key* keys, uint32_t n_keys, const cg::TxvSet& h) {
   if (const int rc = enter(c, "cg_tx_verdicts")) return rc;
-  TxvDev d;
+  cg::TxvSet d;
   HIP_TRY(txv_stage(c, h, n_keys, &d), "hipMalloc(verdict tables)");
   hipStream_t s = c->stream;
   Call call(c, Call::kHost);
   HIP_TRY(call.open(), "hipStreamWaitEvent");
-  HIP_TRY(stage(c->h_sigs, sig_table, (size_t)sig_stride * n_sigs, s), "H2D sigs");
+  HIP_TRY(stage(c->h_sigs, sigs.p, (size_t)sigs.stride * n_sigs, s), "H2D sigs");
   HIP_TRY(stage(c->status, status, n_sigs, s), "H2D status");
   HIP_TRY(stage(c->keys, keys, sizeof(cg_key) * n_keys, s), "H2D keys");
   HIP_TRY(txv_upload(h, n_keys, d, s), "H2D verdict tables");
-  HIP_TRY(cg::launch_tx_verdicts(c->h_sigs.p, sig_stride, n_sigs, (const uint8_t*)c->status.p, (const cg_key*)c->keys.p,
-                                 n_keys, d.key_class, d.checks, (uint32_t)h.n_tx, d.reqs, h.n_reqs, d.nodes, h.n_nodes,
-                                 d.verdicts, d.req_status, c->txvws.p, s),
+  HIP_TRY(cg::launch_tx_verdicts({c->h_sigs.p, sigs.stride}, n_sigs, (const uint8_t*)c->status.p,
+                                 (const cg_key*)c->keys.p, n_keys, d, c->txvws.p, s),
           "launch_tx_verdicts");
   HIP_TRY(txv_download(h, d, s), "D2H verdicts");
   HIP_TRY(call.close(), "hipEventRecord");
@@ -1956,14 +1934,14 @@ int cg_tx_verdicts(cg_ctx* c, const void* sig_table, uint32_t sig_stride, uint64
                    uint64_t n_tx, const uint32_t* reqs, uint32_t n_reqs, const cg_req_node* nodes, uint32_t n_nodes,
                    cg_tx_verdict* verdicts_out, uint8_t* req_status_out) {
   if (!c) return fail(CG_ERR_ARG, "cg_tx_verdicts: ctx is NULL");
-  int a = txv_args("cg_tx_verdicts", sig_stride, n_sigs, sig_table, status, n_keys, keys, n_tx, checks, n_reqs, reqs,
-                   n_nodes, nodes, verdicts_out, req_status_out);
-  if (a == CG_OK) a = txv_reserved("cg_tx_verdicts", checks, n_tx);
+  const cg::SigTable sigs = {sig_table, sig_stride};
+  const cg::TxvSet h = {key_class, checks, n_tx, reqs, n_reqs, nodes, n_nodes, verdicts_out, req_status_out};
+  int a = txv_args("cg_tx_verdicts", sigs, n_sigs, status, n_keys, keys, h);
+  if (a == CG_OK) a = txv_reserved("cg_tx_verdicts", h);
   if (a != CG_OK) return a;
   if (n_tx == 0 && n_reqs == 0) return CG_OK;
-  const TxvHost h{key_class, checks, n_tx, reqs, n_reqs, nodes, n_nodes, verdicts_out, req_status_out};
   std::lock_guard<std::mutex> g(c->mu);
-  const int rc = tx_verdicts_host_locked(c, sig_table, sig_stride, n_sigs, status, keys, n_keys, h);
+  const int rc = tx_verdicts_host_locked(c, sigs, n_sigs, status, keys, n_keys, h);
   if (rc != CG_OK) txv_fill_not_run(h);
   return rc;
 }
@@ -1978,31 +1956,26 @@ int cg_verify_required_signatures_packed_device(cg_ctx* c, const cg_key* d_keys,
                                                 const cg_req_node* d_nodes, uint32_t n_nodes, uint8_t* d_status,
                                                 cg_tx_verdict* d_verdicts, uint8_t* d_req_status, void* hip_stream) {
   const char* fn = "cg_verify_required_signatures_packed_device";
-  int a = txsig_args(fn, c, n_keys, d_keys, n_ids, d_ids, n_sigs, d_sigs, d_status, n_tmpls, tmpls, mode);
-  if (a == CG_OK)
-    a = txv_args(fn, (uint32_t)sizeof(cg_txsig_packed), n_sigs, d_sigs, d_status, n_keys, d_keys, n_tx, d_checks,
-                 n_reqs, d_reqs, n_nodes, d_nodes, d_verdicts, d_req_status);
+  const TxsigReq d = {d_keys,  n_keys,  d_ids,     n_ids, {d_sigs, (uint32_t)sizeof(cg_txsig_packed)}, n_sigs,  tmpls,
+                      n_tmpls, d_arena, arena_len, mode,  d_status, nullptr, sig_bytes_off, sig_bytes_len};
+  const cg::TxvSet t = {d_key_class, d_checks, n_tx, d_reqs, n_reqs, d_nodes, n_nodes, d_verdicts, d_req_status};
+  int a = txsig_args(fn, c, d);
+  if (a == CG_OK) a = txv_args(fn, d.sigs, n_sigs, d_status, n_keys, d_keys, t);
+  if (a == CG_OK) a = txsig_buffer_args(fn, d, false);
   if (a != CG_OK) return a;
-  if (sig_bytes_off > arena_len || sig_bytes_len > arena_len - sig_bytes_off)
-    return fail(CG_ERR_ARG, "%s: the signature stream lies outside the arena", fn);
   if (n_sigs == 0 && n_tx == 0 && n_reqs == 0) return CG_OK;
   std::lock_guard<std::mutex> g(c->mu);
   if (const int rc = enter(c, fn)) return rc;
   HIP_TRY(ensure_all({{&c->txvws, cg::tx_verdicts_ws_bytes(n_tx)}}), "hipMalloc(verdict workspace)");
   const uint64_t slot = tmpl_slot(tmpls, n_tmpls);
   std::vector<uint64_t> bounds;
-  HIP_TRY(txsig_packed_device_ws(c, n_keys, n_sigs, n_tmpls, slot, bounds), "hipMalloc(tx signature workspace)");
+  HIP_TRY(txsig_packed_device_ws(c, d, slot, bounds), "hipMalloc(tx signature workspace)");
   Call call(c, Call::kDevice);
   HIP_TRY(call.open(hip_stream), "hipStreamWaitEvent");
   hipStream_t s = call.stream();
-  HIP_TRY(launch_txsig_packed_device(c, d_keys, n_keys, d_ids, n_ids, d_sigs, n_sigs, sig_bytes_off, sig_bytes_len, tmpls,
-                                     n_tmpls, d_arena, arena_len, mode, d_status, slot, bounds, s),
-          "launch_txsig");
+  HIP_TRY(launch_txsig_packed_device(c, d, slot, bounds, s), "launch_txsig");
   // launch_txsig has joined the side streams and run the mode guard on s: the statuses are final there
-  HIP_TRY(cg::launch_tx_verdicts(d_sigs, (uint32_t)sizeof(cg_txsig_packed), n_sigs, d_status, d_keys, n_keys,
-                                 d_key_class, d_checks, (uint32_t)n_tx, d_reqs, n_reqs, d_nodes, n_nodes, d_verdicts,
-                                 d_req_status, c->txvws.p, s),
-          "launch_tx_verdicts");
+  HIP_TRY(cg::launch_tx_verdicts(d.sigs, n_sigs, d_status, d_keys, n_keys, t, c->txvws.p, s), "launch_tx_verdicts");
   HIP_TRY(call.close(), "hipEventRecord");
   return CG_OK;
 }
@@ -2017,25 +1990,21 @@ int cg_verify_required_signatures_packed(cg_ctx* c, const cg_key* keys, uint32_t
                                          uint8_t* status_out, cg_tx_verdict* verdicts_out, uint8_t* req_status_out,
                                          cg_stats* stats) {
   const char* fn = "cg_verify_required_signatures_packed";
-  // status_out may be NULL: txsig_args only needs it to be there when there are signatures
-  int a = txsig_args(fn, c, n_keys, keys, n_ids, ids, n_sigs, sigs, status_out ? (const void*)status_out : (const void*)sigs,
-                     n_tmpls, tmpls, mode);
-  if (a == CG_OK)
-    a = txv_args(fn, (uint32_t)sizeof(cg_txsig_packed), n_sigs, sigs, sigs, n_keys, keys, n_tx, checks, n_reqs, reqs,
-                 n_nodes, nodes, verdicts_out, req_status_out);
-  if (a == CG_OK) a = txv_reserved(fn, checks, n_tx);
+  const TxsigReq q = {keys,    n_keys, ids,       n_ids, {sigs, (uint32_t)sizeof(cg_txsig_packed)}, n_sigs,    tmpls,
+                      n_tmpls, arena,  arena_len, mode,  status_out, sig_bytes, 0, sig_bytes_len};
+  const cg::TxvSet h = {key_class, checks, n_tx, reqs, n_reqs, nodes, n_nodes, verdicts_out, req_status_out};
+  // status_out may be NULL (the verdict checks then take the table for it)
+  int a = txsig_args(fn, c, q, false);
+  if (a == CG_OK) a = txv_args(fn, q.sigs, n_sigs, sigs, n_keys, keys, h);
+  if (a == CG_OK) a = txv_reserved(fn, h);
+  if (a == CG_OK) a = txsig_buffer_args(fn, q, true);
   if (a != CG_OK) return a;
-  if (arena_len && !arena) return fail(CG_ERR_ARG, "%s: arena is NULL", fn);
-  if (sig_bytes_len && !sig_bytes) return fail(CG_ERR_ARG, "%s: sig_bytes is NULL", fn);
   if (n_sigs && status_out) memset(status_out, CG_NOT_RUN, n_sigs);
   if (n_sigs == 0 && n_tx == 0 && n_reqs == 0) return CG_OK;
-  const TxvHost h{key_class, checks, n_tx, reqs, n_reqs, nodes, n_nodes, verdicts_out, req_status_out};
   std::lock_guard<std::mutex> g(c->mu);
   // without signatures the verify path has nothing to enqueue: the reduction alone
-  const int rc = n_sigs ? verify_txsig_host_locked(c, keys, n_keys, ids, n_ids, nullptr, n_sigs, tmpls, n_tmpls, arena,
-                                                   arena_len, mode, status_out, stats, sigs, sig_bytes, sig_bytes_len,
-                                                   &h)
-                        : tx_verdicts_host_locked(c, sigs, (uint32_t)sizeof(cg_txsig_packed), 0, nullptr, keys, n_keys, h);
+  const int rc = n_sigs ? verify_txsig_host_locked(c, q, stats, &h)
+                        : tx_verdicts_host_locked(c, q.sigs, 0, nullptr, keys, n_keys, h);
   if (rc != CG_OK) {
     if (n_sigs && status_out) memset(status_out, CG_NOT_RUN, n_sigs);
     txv_fill_not_run(h);
@@ -2187,17 +2156,21 @@ int cg_pool_verify_tx_signatures(cg_pool* p, const cg_key* keys, uint32_t n_keys
                                  const cg_txsig* sigs, uint64_t n_sigs, const cg_signable_tmpl* tmpls,
                                  uint32_t n_tmpls, const uint8_t* arena, uint64_t arena_len, uint32_t mode,
                                  uint8_t* status_out, cg_pool_stats* stats) {
-  if (!p) return fail(CG_ERR_ARG, "cg_pool_verify_tx_signatures: pool is NULL");
-  if (p->ctx.empty()) return fail(CG_ERR_ARG, "cg_pool_verify_tx_signatures: empty pool");
-  const int a = txsig_args("cg_pool_verify_tx_signatures", p->ctx[0], n_keys, keys, n_ids, ids, n_sigs, sigs,
-                           status_out, n_tmpls, tmpls, mode);
+  const char* fn = "cg_pool_verify_tx_signatures";
+  if (!p) return fail(CG_ERR_ARG, "%s: pool is NULL", fn);
+  if (p->ctx.empty()) return fail(CG_ERR_ARG, "%s: empty pool", fn);
+  const TxsigReq h = {keys,  n_keys,  ids,   n_ids,     {sigs, (uint32_t)sizeof(cg_txsig)}, n_sigs,
+                      tmpls, n_tmpls, arena, arena_len, mode,                               status_out};
+  int a = txsig_args(fn, p->ctx[0], h);
+  if (a == CG_OK) a = txsig_buffer_args(fn, h, true);
   if (a != CG_OK) return a;
-  if (arena_len && !arena) return fail(CG_ERR_ARG, "cg_pool_verify_tx_signatures: arena is NULL");
-  return pool_call(p, n_sigs, status_out, stats, "cg_pool_verify_tx_signatures",
-                   [&](cg_ctx* c, uint64_t first, uint64_t count) {
-                     return verify_txsig_host_locked(c, keys, n_keys, ids, n_ids, sigs + first, count, tmpls, n_tmpls,
-                                                     arena, arena_len, mode, status_out + first, nullptr);
-                   });
+  return pool_call(p, n_sigs, status_out, stats, fn, [&](cg_ctx* c, uint64_t first, uint64_t count) {
+    TxsigReq shard = h;
+    shard.sigs = h.sigs.from(first);
+    shard.n_sigs = count;
+    shard.status = status_out + first;
+    return verify_txsig_host_locked(c, shard, nullptr, nullptr);
+  });
 }
 
 // The whole call on one live slot (a signature may reference any transaction's id, so the call is not
@@ -2209,20 +2182,14 @@ int cg_pool_verify_transactions(cg_pool* p, const cg_tx* txs, uint64_t n_tx, con
                                 uint8_t* sig_status_out, cg_pool_stats* stats) {
   if (!p) return fail(CG_ERR_ARG, "cg_pool_verify_transactions: pool is NULL");
   if (p->ctx.empty()) return fail(CG_ERR_ARG, "cg_pool_verify_transactions: empty pool");
-  if (n_tx && (!txs || !ids_out || !tx_status_out)) return fail(CG_ERR_ARG, "cg_pool_verify_transactions: NULL tx buffer");
-  if (n_sigs && (!sigs || !sig_status_out)) return fail(CG_ERR_ARG, "cg_pool_verify_transactions: NULL sig buffer");
-  if (n_comps && !comps) return fail(CG_ERR_ARG, "cg_pool_verify_transactions: comps is NULL");
-  if (n_keys && !keys) return fail(CG_ERR_ARG, "cg_pool_verify_transactions: keys is NULL");
-  if (n_tmpls && !tmpls) return fail(CG_ERR_ARG, "cg_pool_verify_transactions: templates is NULL");
-  if (arena_len && !arena) return fail(CG_ERR_ARG, "cg_pool_verify_transactions: arena is NULL");
-  if (mode > CG_MODE_ISVALID) return fail(CG_ERR_ARG, "cg_pool_verify_transactions: bad mode");
+  const TxnReq h = {txs,   n_tx,    comps, n_comps,   keys, n_keys,  sigs,          n_sigs,
+                    tmpls, n_tmpls, arena, arena_len, mode, ids_out, tx_status_out, sig_status_out};
+  if (const int a = txn_args("cg_pool_verify_transactions", h, true)) return a;
   for (uint64_t i = 0; i < n_sigs; ++i) sig_status_out[i] = CG_NOT_RUN;
   if (n_tx == 0 && n_sigs == 0) return CG_OK;
   uint8_t unit = CG_NOT_RUN;
   const int rc = pool_call(p, 1, &unit, stats, "cg_pool_verify_transactions", [&](cg_ctx* c, uint64_t, uint64_t) {
-    const int r = verify_transactions_host_locked(c, txs, n_tx, comps, n_comps, keys, n_keys, sigs, n_sigs, tmpls,
-                                                  n_tmpls, arena, arena_len, mode, ids_out, tx_status_out,
-                                                  sig_status_out);
+    const int r = verify_transactions_host_locked(c, h);
     if (r != CG_OK)
       for (uint64_t i = 0; i < n_sigs; ++i) sig_status_out[i] = CG_NOT_RUN;
     return r;
@@ -2237,13 +2204,14 @@ int cg_pool_verify_tx_signatures_packed(cg_pool* p, const cg_key* keys, uint32_t
                                         const cg_signable_tmpl* tmpls, uint32_t n_tmpls, const uint8_t* arena,
                                         uint64_t arena_len, uint32_t mode, uint8_t* status_out,
                                         cg_pool_stats* stats) {
-  if (!p) return fail(CG_ERR_ARG, "cg_pool_verify_tx_signatures_packed: pool is NULL");
-  if (p->ctx.empty()) return fail(CG_ERR_ARG, "cg_pool_verify_tx_signatures_packed: empty pool");
-  const int a = txsig_args("cg_pool_verify_tx_signatures_packed", p->ctx[0], n_keys, keys, n_ids, ids, n_sigs, sigs,
-                           status_out, n_tmpls, tmpls, mode);
+  const char* fn = "cg_pool_verify_tx_signatures_packed";
+  if (!p) return fail(CG_ERR_ARG, "%s: pool is NULL", fn);
+  if (p->ctx.empty()) return fail(CG_ERR_ARG, "%s: empty pool", fn);
+  const TxsigReq h = {keys,    n_keys, ids,       n_ids, {sigs, (uint32_t)sizeof(cg_txsig_packed)}, n_sigs,    tmpls,
+                      n_tmpls, arena,  arena_len, mode,  status_out, sig_bytes, 0, sig_bytes_len};
+  int a = txsig_args(fn, p->ctx[0], h);
+  if (a == CG_OK) a = txsig_buffer_args(fn, h, true);
   if (a != CG_OK) return a;
-  if (arena_len && !arena) return fail(CG_ERR_ARG, "cg_pool_verify_tx_signatures_packed: arena is NULL");
-  if (sig_bytes_len && !sig_bytes) return fail(CG_ERR_ARG, "cg_pool_verify_tx_signatures_packed: sig_bytes is NULL");
   // a shard [first, first + count) starts at the stream offset of record `first`: the sum of the spans
   // before it, in one threaded pass over the table (a prefix per 2^16-record block), looked up per shard
   const uint64_t B = 1u << 16, nb = (n_sigs + B - 1) / B;
@@ -2267,13 +2235,16 @@ int cg_pool_verify_tx_signatures_packed(cg_pool* p, const cg_key* keys, uint32_t
     for (uint64_t j = (i / B) * B; j < i; ++j) o += ((uint64_t)sigs[j].sig_len + 3u) & ~(uint64_t)3;
     return o;
   };
-  return pool_call(p, n_sigs, status_out, stats, "cg_pool_verify_tx_signatures_packed",
-                   [&](cg_ctx* c, uint64_t first, uint64_t count) {
-                     const uint64_t o = std::min(stream_at(first), sig_bytes_len);
-                     return verify_txsig_host_locked(c, keys, n_keys, ids, n_ids, nullptr, count, tmpls, n_tmpls,
-                                                     arena, arena_len, mode, status_out + first, nullptr, sigs + first,
-                                                     sig_bytes + o, sig_bytes_len - o);
-                   });
+  return pool_call(p, n_sigs, status_out, stats, fn, [&](cg_ctx* c, uint64_t first, uint64_t count) {
+    const uint64_t o = std::min(stream_at(first), sig_bytes_len);
+    TxsigReq shard = h;
+    shard.sigs = h.sigs.from(first);
+    shard.n_sigs = count;
+    shard.status = status_out + first;
+    shard.sig_bytes = sig_bytes + o;
+    shard.sig_bytes_len = sig_bytes_len - o;
+    return verify_txsig_host_locked(c, shard, nullptr, nullptr);
+  });
 }
 
 int cg_pool_verify_required_signatures_packed(cg_pool* p, const cg_key* keys, uint32_t n_keys, const uint8_t* ids,
@@ -2288,16 +2259,16 @@ int cg_pool_verify_required_signatures_packed(cg_pool* p, const cg_key* keys, ui
   const char* fn = "cg_pool_verify_required_signatures_packed";
   if (!p) return fail(CG_ERR_ARG, "%s: pool is NULL", fn);
   if (p->ctx.empty()) return fail(CG_ERR_ARG, "%s: empty pool", fn);
-  int a = txv_args(fn, (uint32_t)sizeof(cg_txsig_packed), n_sigs, sigs, sigs, n_keys, keys, n_tx, checks, n_reqs, reqs,
-                   n_nodes, nodes, verdicts_out, req_status_out);
-  if (a == CG_OK) a = txv_reserved(fn, checks, n_tx);
+  const cg::SigTable table = {sigs, (uint32_t)sizeof(cg_txsig_packed)};
+  const cg::TxvSet h = {key_class, checks, n_tx, reqs, n_reqs, nodes, n_nodes, verdicts_out, req_status_out};
+  int a = txv_args(fn, table, n_sigs, sigs, n_keys, keys, h);
+  if (a == CG_OK) a = txv_reserved(fn, h);
   if (a != CG_OK) return a;
   std::vector<uint8_t> own;
   if (!status_out && n_sigs) {
     own.assign(n_sigs, CG_NOT_RUN);
     status_out = own.data();
   }
-  const TxvHost h{key_class, checks, n_tx, reqs, n_reqs, nodes, n_nodes, verdicts_out, req_status_out};
   // the existing pool call: shards, re-run on a fault; what no slot ran stays CG_NOT_RUN
   const int rc = cg_pool_verify_tx_signatures_packed(p, keys, n_keys, ids, n_ids, sigs, n_sigs, sig_bytes, sig_bytes_len,
                                                      tmpls, n_tmpls, arena, arena_len, mode, status_out, stats);
@@ -2315,7 +2286,7 @@ int cg_pool_verify_required_signatures_packed(cg_pool* p, const cg_key* keys, ui
       if (!p->healthy[k]) continue;
       cg_ctx* c = p->ctx[k];
       std::lock_guard<std::mutex> gc(c->mu);
-      vr = tx_verdicts_host_locked(c, sigs, (uint32_t)sizeof(cg_txsig_packed), n_sigs, status_out, keys, n_keys, h);
+      vr = tx_verdicts_host_locked(c, table, n_sigs, status_out, keys, n_keys, h);
       if (vr == CG_ERR_DEVICE) p->healthy[k] = 0;
       else if (vr != CG_OK) break;
     }
@@ -2333,13 +2304,14 @@ int cg_pool_verify_batch(cg_pool* p, const cg_key* keys, uint32_t n_keys, const 
                          const uint8_t* arena, uint64_t arena_len, uint32_t mode, uint8_t* status_out,
                          cg_pool_stats* stats) {
   if (!p) return fail(CG_ERR_ARG, "cg_pool_verify_batch: pool is NULL");
-  if (n_items && (!items || !status_out)) return fail(CG_ERR_ARG, "cg_pool_verify_batch: NULL buffer");
-  if (n_keys && !keys) return fail(CG_ERR_ARG, "cg_pool_verify_batch: keys is NULL");
-  if (arena_len && !arena) return fail(CG_ERR_ARG, "cg_pool_verify_batch: arena is NULL");
-  if (mode > CG_MODE_ISVALID) return fail(CG_ERR_ARG, "cg_pool_verify_batch: bad mode");
+  const cg::VerifyReq h = {keys, n_keys, items, n_items, arena, arena_len, mode, status_out};
+  if (const int a = batch_args("cg_pool_verify_batch", h, true)) return a;
   return pool_call(p, n_items, status_out, stats, "cg_pool_verify_batch", [&](cg_ctx* c, uint64_t first, uint64_t count) {
-    return verify_host_locked(c, keys, n_keys, items + first, count, arena, arena_len, mode, status_out + first,
-                              nullptr);
+    cg::VerifyReq shard = h;  // the items and the status bytes narrowed
+    shard.d_items = items + first;
+    shard.n_items = count;
+    shard.d_status = status_out + first;
+    return verify_host_locked(c, shard, nullptr);
   });
 }
 

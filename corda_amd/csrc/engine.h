@@ -120,11 +120,23 @@ struct Fork {
   const std::function<hipError_t()>* mid_front = nullptr;
 };
 
-// What the item stages of one chunk read and write: the call's key table, arena and workspaces, and
-// the chunk's items, status bytes and item workspace. Every field is required but d_msgs / msgs_len
-// (the engine's spliced-message workspace, read by items flagged CG_ITEM_MSG_WS (keyws.h); caller
-// items never carry that flag) and `wide` (null: no key of the call has wide tables).
-struct ItemArgs {
+// A signature table in either record form: `stride` is sizeof(cg_txsig) or sizeof(cg_txsig_packed).
+struct SigTable {
+  const void* p = nullptr;
+  uint32_t stride = sizeof(cg_txsig);
+  bool packed() const { return stride == sizeof(cg_txsig_packed); }
+  SigTable from(uint64_t first) const { return {(const uint8_t*)p + first * stride, stride}; }  // records first, first + 1, ...
+};
+// f(the table's records, typed by its stride)
+template <class F>
+auto with_records(const SigTable& t, F&& f) {
+  return !t.packed() ? f((const cg_txsig*)t.p) : f((const cg_txsig_packed*)t.p);
+}
+
+// One verify call as its caller states it: the key table, the items, the arena, the mode and the
+// status bytes, plus the engine's spliced-message workspace (d_msgs / msgs_len: read by items flagged
+// CG_ITEM_MSG_WS (keyws.h); caller items never carry that flag). Every other field is required.
+struct VerifyReq {
   const cg_key* d_keys;
   uint32_t n_keys;
   const cg_item* d_items;
@@ -133,19 +145,24 @@ struct ItemArgs {
   uint64_t arena_len;
   uint32_t mode;
   uint8_t* d_status;
+  const uint8_t* d_msgs = nullptr;
+  uint64_t msgs_len = 0;
+};
+
+// What the item stages of one chunk read and write: the request narrowed to the chunk's items and
+// status bytes, the call's workspaces and the chunk's item workspace. Every field is required but
+// `wide` (null: no key of the call has wide tables).
+struct ItemArgs : VerifyReq {
   const void* d_keyprep;
   void* d_item_ws;
   const void* d_btab;
-  const uint8_t* d_msgs;
-  uint64_t msgs_len;
   const WidePool* wide;
 };
 
-// Where the per-key use counts come from when there is no verify-item table yet: a cg_txsig table
+// Where the per-key use counts come from when there is no verify-item table yet: a signature table
 // in HBM (sampled on the device) or exact counts (n_keys u32 in HBM, made by the host).
 struct KeyUses {
-  const cg_txsig* sigs = nullptr;
-  const cg_txsig_packed* sigs12 = nullptr;  // or the 12-byte table (cg_verify_tx_signatures_packed_device)
+  SigTable sigs;
   const uint32_t* counts = nullptr;
   uint64_t n = 0;  // signatures the counts cover (sizes the wide pools)
   // optional host copies of the key table and of `counts` (the host-buffer tx-signature path): the
@@ -170,9 +187,8 @@ struct EngineVariant {
   size_t (*btab_scratch_bytes)();
   hipError_t (*init_btab)(void* d_btab, void* d_scratch, hipStream_t stream);
   size_t (*item_ws_bytes)(uint64_t n_items);
-  hipError_t (*launch_keyprep)(const cg_key* d_keys, uint32_t n_keys, const uint8_t* d_arena, uint64_t arena_len,
-                               void* d_keyprep, hipStream_t stream, const Fork& fork, const cg_item* d_items,
-                               uint64_t n_items, const WidePool* wide, const KeyUses* src);
+  hipError_t (*launch_keyprep)(const VerifyReq& r, void* d_keyprep, hipStream_t stream, const Fork& fork,
+                               const WidePool* wide, const KeyUses* src);
   hipError_t (*launch_key_tables)(const Fork& fork, hipStream_t stream);
   hipError_t (*launch_items)(const ItemArgs& a, hipStream_t stream, const Fork& fork);
   hipError_t (*launch_items_plan)(const ItemArgs& a, hipStream_t stream, const Fork& fork);
@@ -188,8 +204,11 @@ using cgt::EngineVariant;
 using cgt::Fork;
 using cgt::ItemArgs;
 using cgt::PendingTabs;
+using cgt::SigTable;
 using cgt::StageTimer;
+using cgt::VerifyReq;
 using cgt::WidePool;
+using cgt::with_records;
 
 // this build's entry points (verify.hip)
 const EngineVariant& variant();
@@ -217,11 +236,11 @@ hipError_t init_btab(void* d_btab, void* d_scratch, hipStream_t stream);
 // Bytes of per-item workspace (projective Ed25519 results awaiting the batched inversion).
 size_t item_ws_bytes(uint64_t n_items);
 using cgt::KeyUses;
-// With `d_items` (or `src`), each key's table is sized by the number of items that use it
-// (keyws.h); with neither (cg_prepare_keys_device), every key gets full tables.
-hipError_t launch_keyprep(const cg_key* d_keys, uint32_t n_keys, const uint8_t* d_arena, uint64_t arena_len,
-                          void* d_keyprep, hipStream_t stream, const Fork& fork, const cg_item* d_items,
-                          uint64_t n_items, const WidePool* wide, const KeyUses* src);
+// The key tables of r's keys. With `src`, or else with r.d_items, each key's table is sized by the
+// number of items that use it (keyws.h; `src` when the items are not made yet: r.d_items is then not
+// read); with neither (cg_prepare_keys_device), every key gets full tables.
+hipError_t launch_keyprep(const VerifyReq& r, void* d_keyprep, hipStream_t stream, const Fork& fork,
+                          const WidePool* wide, const KeyUses* src);
 // Start the table builds launch_keyprep deferred (no-op if already started): a host-buffer call
 // starts them before it blocks on the first chunk's arena copy, so they overlap that copy.
 hipError_t launch_key_tables(const Fork& fork, hipStream_t stream);
@@ -247,12 +266,8 @@ hipError_t launch_items_back(const ItemArgs& a, hipStream_t stream, const Fork& 
 constexpr uint64_t kRsaSegment = 1ull << 30;
 size_t rsa_keys_bytes(uint32_t n_keys);
 size_t rsa_list_bytes(uint64_t n_items);
-hipError_t launch_rsa_keyprep(const cg_key* d_keys, uint32_t n_keys, const uint8_t* d_arena, uint64_t arena_len,
-                              void* d_rsakeys, hipStream_t stream);
-hipError_t launch_rsa_items(const cg_key* d_keys, uint32_t n_keys, const cg_item* d_items, uint64_t n_items,
-                            const uint8_t* d_arena, uint64_t arena_len, uint32_t mode, uint8_t* d_status,
-                            const void* d_rsakeys, void* d_rsalist, hipStream_t stream, const uint8_t* d_msgs = nullptr,
-                            uint64_t msgs_len = 0);
+hipError_t launch_rsa_keyprep(const VerifyReq& r, void* d_rsakeys, hipStream_t stream);
+hipError_t launch_rsa_items(const VerifyReq& r, const void* d_rsakeys, void* d_rsalist, hipStream_t stream);
 
 // Hashing kernels
 hipError_t launch_sha256(const cg_span* d_spans, uint64_t n, const uint8_t* d_arena, uint64_t arena_len,
@@ -316,14 +331,23 @@ hipError_t launch_filtered(const cg_filtered_tx* d_ftxs, uint64_t n_ftx, const c
                            uint64_t arena_len, uint8_t* d_status, uint8_t* d_ws, hipStream_t stream);
 
 
-// Per-transaction verdicts (txverdict.hip): req_status preset to CG_REQ_HOST, then the lane-per-transaction
-// kernel and the wave-per-transaction kernel over the list it leaves in d_ws (tx_verdicts_ws_bytes(n_tx)
-// bytes). sig_stride: sizeof(cg_txsig_packed) or sizeof(cg_txsig).
+// Per-transaction verdicts (txverdict.hip). One call's tables and results, all on one side of the bus:
+// the caller's (host or device) or the context's staged copies.
+struct TxvSet {
+  const uint32_t* key_class = nullptr;
+  const cg_tx_check* checks = nullptr;
+  uint64_t n_tx = 0;  // below 2^32 (the entry points check)
+  const uint32_t* reqs = nullptr;
+  uint32_t n_reqs = 0;
+  const cg_req_node* nodes = nullptr;
+  uint32_t n_nodes = 0;
+  cg_tx_verdict* verdicts = nullptr;
+  uint8_t* req_status = nullptr;
+};
+// req_status preset to CG_REQ_HOST, then the lane-per-transaction kernel and the wave-per-transaction
+// kernel over the list it leaves in d_ws (tx_verdicts_ws_bytes(n_tx) bytes).
 size_t tx_verdicts_ws_bytes(uint64_t n_tx);
-hipError_t launch_tx_verdicts(const void* d_sig_table, uint32_t sig_stride, uint64_t n_sigs, const uint8_t* d_status,
-                              const cg_key* d_keys, uint32_t n_keys, const uint32_t* d_key_class,
-                              const cg_tx_check* d_checks, uint32_t n_tx, const uint32_t* d_reqs, uint32_t n_reqs,
-                              const cg_req_node* d_nodes, uint32_t n_nodes, cg_tx_verdict* d_verdicts,
-                              uint8_t* d_req_status, void* d_ws, hipStream_t stream);
+hipError_t launch_tx_verdicts(const SigTable& d_sigs, uint64_t n_sigs, const uint8_t* d_status, const cg_key* d_keys,
+                              uint32_t n_keys, const TxvSet& d, void* d_ws, hipStream_t stream);
 
 }  // namespace cg

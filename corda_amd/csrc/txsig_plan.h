@@ -38,6 +38,14 @@ inline uint64_t equal_chunk(uint64_t chunk, uint64_t n) {
   return (n + k - 1) / k;
 }
 
+// Chunks of `per` items, the last one shorter: {0, per, 2 per, ..., n} (n = 0: no chunk).
+inline std::vector<uint64_t> equal_bounds(uint64_t n, uint64_t per) {
+  std::vector<uint64_t> bounds;
+  for (uint64_t f = 0; f < n; f += per) bounds.push_back(f);
+  bounds.push_back(n);
+  return bounds;
+}
+
 // Chunk k of a host tx-signature call = signatures [bounds[k], bounds[k + 1]).
 // chunks: the device chunk, but at least kTxsigMinChunks of them for a large call unless the
 // caller set cg_config.chunk_items (the first chunk's copy is the part nothing overlaps; measured on
@@ -55,16 +63,11 @@ inline std::vector<uint64_t> txsig_bounds(uint64_t n_sigs, uint64_t chunk, bool 
     const uint64_t alt = (n_sigs + kTxsigMinChunks - 1) / kTxsigMinChunks;
     if (alt < per) per = alt;
   }
-  std::vector<uint64_t> bounds;
   const uint64_t k0 = (n_sigs + per - 1) / per;
-  if (first_div > 1 && k0 > 1) {
-    const uint64_t f0 = n_sigs / first_div, rest = n_sigs - f0, kr = k0;
-    bounds.push_back(0);
-    bounds.push_back(f0);
-    for (uint64_t k = 1; k <= kr; ++k) bounds.push_back(f0 + rest * k / kr);
-  } else {
-    for (uint64_t k = 0; k <= k0; ++k) bounds.push_back(k == k0 ? n_sigs : k * per);
-  }
+  if (first_div <= 1 || k0 <= 1) return equal_bounds(n_sigs, per);
+  const uint64_t f0 = n_sigs / first_div, rest = n_sigs - f0;
+  std::vector<uint64_t> bounds = {0, f0};
+  for (uint64_t k = 1; k <= k0; ++k) bounds.push_back(f0 + rest * k / k0);
   return bounds;
 }
 

@@ -115,13 +115,11 @@ hipError_t launch_with(Acc acc, const TxvTables& tb, const cg_tx_check* d_checks
 
 size_t tx_verdicts_ws_bytes(uint64_t n_tx) { return sizeof(uint32_t) * (4 + (size_t)n_tx); }
 
-hipError_t launch_tx_verdicts(const void* d_sig_table, uint32_t sig_stride, uint64_t n_sigs, const uint8_t* d_status,
-                              const cg_key* d_keys, uint32_t n_keys, const uint32_t* d_key_class,
-                              const cg_tx_check* d_checks, uint32_t n_tx, const uint32_t* d_reqs, uint32_t n_reqs,
-                              const cg_req_node* d_nodes, uint32_t n_nodes, cg_tx_verdict* d_verdicts,
-                              uint8_t* d_req_status, void* d_ws, hipStream_t stream) {
+hipError_t launch_tx_verdicts(const SigTable& d_sigs, uint64_t n_sigs, const uint8_t* d_status, const cg_key* d_keys,
+                              uint32_t n_keys, const TxvSet& d, void* d_ws, hipStream_t stream) {
+  const uint32_t n_tx = (uint32_t)d.n_tx;
   hipError_t e = hipSuccess;
-  if (n_reqs) e = hipMemsetAsync(d_req_status, CG_REQ_HOST, n_reqs, stream);
+  if (d.n_reqs) e = hipMemsetAsync(d.req_status, CG_REQ_HOST, d.n_reqs, stream);
   if (e != hipSuccess || n_tx == 0) return e;
   e = hipMemsetAsync(d_ws, 0, 4 * sizeof(uint32_t), stream);
   if (e != hipSuccess) return e;
@@ -130,16 +128,16 @@ hipError_t launch_tx_verdicts(const void* d_sig_table, uint32_t sig_stride, uint
   tb.status = d_status;
   tb.keys = d_keys;
   tb.n_keys = n_keys;
-  tb.key_class = d_key_class;
-  tb.reqs = d_reqs;
-  tb.n_reqs = n_reqs;
-  tb.nodes = d_nodes;
-  tb.n_nodes = n_nodes;
-  if (sig_stride == sizeof(cg_txsig_packed))
-    return launch_with(Rec12{(const cg_txsig_packed*)d_sig_table}, tb, d_checks, n_tx, d_verdicts, d_req_status,
+  tb.key_class = d.key_class;
+  tb.reqs = d.reqs;
+  tb.n_reqs = d.n_reqs;
+  tb.nodes = d.nodes;
+  tb.n_nodes = d.n_nodes;
+  if (d_sigs.packed())
+    return launch_with(Rec12{(const cg_txsig_packed*)d_sigs.p}, tb, d.checks, n_tx, d.verdicts, d.req_status,
                        (uint32_t*)d_ws, stream);
-  return launch_with(Rec24{(const cg_txsig*)d_sig_table}, tb, d_checks, n_tx, d_verdicts, d_req_status,
-                     (uint32_t*)d_ws, stream);
+  return launch_with(Rec24{(const cg_txsig*)d_sigs.p}, tb, d.checks, n_tx, d.verdicts, d.req_status, (uint32_t*)d_ws,
+                     stream);
 }
 
 }  // namespace cg

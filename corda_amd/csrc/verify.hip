@@ -383,15 +383,19 @@ static void families_needing_full(const KeyUses& src, uint32_t n_keys, const Key
   for (int f = 0; f < 3; ++f) need[f] = low[f] || over[f == 2 ? 0 : 1];
 }
 
-hipError_t launch_keyprep(const cg_key* d_keys, uint32_t n_keys, const uint8_t* d_arena, uint64_t arena_len,
-                          void* d_keyprep, hipStream_t stream, const Fork& fork, const cg_item* d_items,
-                          uint64_t n_items, const WidePool* wide, const KeyUses* src) {
+hipError_t launch_keyprep(const VerifyReq& r, void* d_keyprep, hipStream_t stream, const Fork& fork,
+                          const WidePool* wide, const KeyUses* src) {
+  const cg_key* d_keys = r.d_keys;
+  const uint32_t n_keys = r.n_keys;
+  const uint8_t* d_arena = r.d_arena;
+  const uint64_t arena_len = r.arena_len;
+  const cg_item* d_items = src ? nullptr : r.d_items;  // with `src` the items are not made yet
+  const uint64_t n_items = src ? src->n : r.n_items;
   // a call with no keys must not inherit the previous call's skip (k_mode_guard reads it)
   fork.pending.skip_mask = 0;
   for (int f = 0; f < 3; ++f) fork.pending.need_full[f] = true;
   if (n_keys == 0) return hipSuccess;
   const bool counted = d_items || src;  // tables sized by the call's key uses
-  if (!d_items && src) n_items = src->n;
   const KeyWs w = key_ws(d_keyprep, n_keys, counted ? wide : nullptr);
   // use counts first (main stream; the side streams fork after them)
   const uint32_t kl = n_keys > PLAN_CLASSES + 2 ? n_keys : PLAN_CLASSES + 2;
@@ -403,12 +407,12 @@ hipError_t launch_keyprep(const cg_key* d_keys, uint32_t n_keys, const uint8_t* 
   else if (src && src->counts)
     hipLaunchKernelGGL(k_key_counts, dim3((n_keys + 255) / 256), dim3(256), 0, stream, src->counts, n_keys, w.uses,
                        w.seen);
-  else if (src && src->sigs && src->n)
-    hipLaunchKernelGGL(k_key_uses_txsig<cg_txsig>, dim3((unsigned)((src->n + 255) / 256)), dim3(256), 0, stream,
-                       src->sigs, src->n, n_keys, w.uses, w.seen);
-  else if (src && src->sigs12 && src->n)
-    hipLaunchKernelGGL(k_key_uses_txsig<cg_txsig_packed>, dim3((unsigned)((src->n + 255) / 256)), dim3(256), 0,
-                       stream, src->sigs12, src->n, n_keys, w.uses, w.seen);
+  else if (src && src->sigs.p && src->n)
+    with_records(src->sigs, [&](auto* recs) {
+      using Rec = std::remove_const_t<std::remove_pointer_t<decltype(recs)>>;
+      hipLaunchKernelGGL(k_key_uses_txsig<Rec>, dim3((unsigned)((src->n + 255) / 256)), dim3(256), 0, stream, recs,
+                         src->n, n_keys, w.uses, w.seen);
+    });
   // every mode's builds and ladders unless this call's host counts prove a family has no row-0 /
   // quarter / full key; the classification checks that proof on the device (k_mode_guard)
   uint32_t skip_mask = 0;

@@ -234,32 +234,28 @@ size_t rsa_list_bytes(uint64_t n_items) {
   return 256 + al256((size_t)(n ? n : 1) * sizeof(uint32_t));
 }
 
-hipError_t launch_rsa_keyprep(const cg_key* d_keys, uint32_t n_keys, const uint8_t* d_arena, uint64_t arena_len,
-                              void* d_rsakeys, hipStream_t stream) {
-  if (n_keys == 0) return hipSuccess;
-  hipLaunchKernelGGL(k_rsa_keyprep, dim3(n_keys), dim3(64), 0, stream, d_keys, n_keys, d_arena, arena_len,
+hipError_t launch_rsa_keyprep(const VerifyReq& r, void* d_rsakeys, hipStream_t stream) {
+  if (r.n_keys == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_rsa_keyprep, dim3(r.n_keys), dim3(64), 0, stream, r.d_keys, r.n_keys, r.d_arena, r.arena_len,
                      (RsaKeyRec*)d_rsakeys);
   return hipGetLastError();
 }
 
-hipError_t launch_rsa_items(const cg_key* d_keys, uint32_t n_keys, const cg_item* d_items, uint64_t n_items,
-                            const uint8_t* d_arena, uint64_t arena_len, uint32_t mode, uint8_t* d_status,
-                            const void* d_rsakeys, void* d_rsalist, hipStream_t stream, const uint8_t* d_msgs,
-                            uint64_t msgs_len) {
-  if (n_keys == 0) return hipSuccess;
+hipError_t launch_rsa_items(const VerifyReq& r, const void* d_rsakeys, void* d_rsalist, hipStream_t stream) {
+  if (r.n_keys == 0) return hipSuccess;
   uint32_t* count = (uint32_t*)d_rsalist;
   uint32_t* list = (uint32_t*)((uint8_t*)d_rsalist + 256);
-  for (uint64_t f = 0; f < n_items; f += kRsaSegment) {
-    const uint32_t cnt = (uint32_t)(kRsaSegment < n_items - f ? kRsaSegment : n_items - f);
+  for (uint64_t f = 0; f < r.n_items; f += kRsaSegment) {
+    const uint32_t cnt = (uint32_t)(kRsaSegment < r.n_items - f ? kRsaSegment : r.n_items - f);
     hipError_t e = hipMemsetAsync(count, 0, sizeof(uint32_t), stream);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_rsa_select, dim3((cnt + 255) / 256), dim3(256), 0, stream, d_items + f, cnt, d_keys, n_keys,
-                       (const RsaKeyRec*)d_rsakeys, list, count);
+    hipLaunchKernelGGL(k_rsa_select, dim3((cnt + 255) / 256), dim3(256), 0, stream, r.d_items + f, cnt, r.d_keys,
+                       r.n_keys, (const RsaKeyRec*)d_rsakeys, list, count);
     // one wave per listed signature at most; the count is read on the device (no host round trip)
     const unsigned grid = walk_grid(((uint64_t)cnt + 3) / 4 * 256, 256, WALK_CAP(4));
-    hipLaunchKernelGGL(k_rsa_verify, dim3(grid), dim3(256), 0, stream, d_items + f, (const uint32_t*)list,
-                       (const uint32_t*)count, (const RsaKeyRec*)d_rsakeys, d_arena, arena_len, d_msgs, msgs_len, mode,
-                       d_status + f);
+    hipLaunchKernelGGL(k_rsa_verify, dim3(grid), dim3(256), 0, stream, r.d_items + f, (const uint32_t*)list,
+                       (const uint32_t*)count, (const RsaKeyRec*)d_rsakeys, r.d_arena, r.arena_len, r.d_msgs,
+                       r.msgs_len, r.mode, r.d_status + f);
   }
   return hipGetLastError();
 }

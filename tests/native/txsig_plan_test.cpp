@@ -38,6 +38,12 @@ uint64_t tp_bounds(uint64_t n_sigs, uint64_t chunk, int chunk_set, uint64_t firs
   return b.size();
 }
 
+uint64_t tp_equal_bounds(uint64_t n, uint64_t per, uint64_t* out, uint64_t cap) {
+  const std::vector<uint64_t> b = cg::equal_bounds(n, per);
+  for (uint64_t i = 0; i < b.size() && i < cap; ++i) out[i] = b[i];
+  return b.size();
+}
+
 uint32_t tp_sample_override(uint32_t x) { return cg::sample_override(x); }
 uint32_t tp_sample_block(uint32_t x) { return cg::sample_block(x); }
 uint32_t tp_sample_rate(uint32_t s_override, uint64_t n_sigs, uint32_t n_keys) {

@@ -479,3 +479,116 @@ def test_device_call_ordered_on_caller_stream(bridge):
     """)
     r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=240)
     assert r.returncode == 0 and "ORDERED_OK" in r.stdout, r.stdout[-2000:] + r.stderr[-3000:]
+
+
+# ---- the chunk boundaries of every form with chunk_items = 256
+# Where a context with chunk_items = 256 cuts n signatures (cordagpu.cpp, txsig_plan.h), written out here:
+# the host forms take 1/6 first and split the rest into as many chunks as equal chunks of at most 256
+# would make; the 24-byte device form makes those equal chunks; the 12-byte device forms round them up
+# to whole 256-record blocks, so their last chunk is the remainder (1 at 257, 37 at 549).
+CHUNK_BOUNDS = {
+    "host": {256: [0, 256], 257: [0, 42, 149, 257], 549: [0, 91, 243, 396, 549]},
+    "device24": {256: [0, 256], 257: [0, 129, 257], 549: [0, 183, 366, 549]},
+    "device12": {256: [0, 256], 257: [0, 256, 257], 549: [0, 256, 512, 549]},
+}
+CHUNK_FORMS = {"host24": "host", "host12": "host", "device24": "device24", "device12": "device12",
+               "required_host": "host", "required_device": "device12"}
+
+
+@pytest.fixture(scope="module")
+def chunked(engine):
+    """549 signatures (Ed25519, P-256, secp256k1) over a 1 024-item signable pool, sorted by id and grouped
+    into transactions of up to 3 signatures with one leaf requirement each; the signature on either side
+    of every chunk boundary of every form and size is corrupted by hand, besides the pool's own corrupted
+    ones. Statuses: the C oracle on the materialised SignableData. A context with chunk_items = 256."""
+    from corda_amd import signable
+    from corda_amd.engine import Engine
+    from tools.workload import wl
+    pool, labels, schemes = wl.notary_pool(1 << 10, ed_keys=24, ec_keys=12, seed=515, nthreads=8, sig_group=4)
+    ids, id_idx = wl.pool_ids(pool, len(signable.template(1, 4)[0]))
+    idx = np.random.default_rng(516).integers(0, pool.n, 549)
+    idx = idx[np.argsort(id_idx[idx], kind="stable")]
+    tb = wl.tx_sig_stream(pool, schemes, idx, ids, id_idx, nthreads=8)
+    of_id = id_idx[idx].astype(np.int64)
+    start = ((np.arange(549) - np.searchsorted(of_id, of_id, side="left")) % 3) == 0
+    tx_of = np.cumsum(start) - 1
+    sigs = tb.sigs.copy()
+    sigs["tx_idx"] = tx_of
+    arena = tb.arena.copy()
+    edges = sorted({e for per_n in CHUNK_BOUNDS.values() for b in per_n.values() for x in b for e in (x - 1, x)
+                    if 0 <= e < 549})
+    for e in edges:  # the last byte of the signature: Ed25519's S, the DER's s
+        arena[int(sigs["sig_off"][e]) + int(sigs["sig_len"][e]) - 1] ^= 0x40
+    tb = B.TxSigBatch(tb.keys, ids[of_id[start]], sigs, tb.tmpls, arena)
+    status = c_oracle.verify_batch(txsig_util.to_message_batch(tb), B.MODE_DOVERIFY, 8)
+    assert np.all(status[edges] != B.VALID) and 0.5 < np.mean(status == B.VALID) < 0.95
+    assert len(np.unique(tb.keys["scheme"][sigs["key_idx"]])) == 3
+    with Engine(0, chunk_items=256) as eng:
+        yield eng, tb, status
+
+
+@pytest.mark.parametrize("n_sigs", [256, 257, 549])
+@pytest.mark.parametrize("form", list(CHUNK_FORMS))
+def test_chunk_boundaries_of_every_form(chunked, form, n_sigs):
+    """n_sigs = 256: one chunk that ends exactly at n; 257: a last chunk of one signature (12-byte device
+    forms); 549: three or four chunks, so both item-workspace halves are used twice, with a short last
+    chunk. Every status equals the oracle's, the corrupted signatures beside each boundary included, and
+    the required-signatures forms' verdicts equal the CPU lane function's over the oracle's statuses."""
+    import torch
+    import txverdict_cases as C
+    eng, tb549, status549 = chunked
+    bounds = CHUNK_BOUNDS[CHUNK_FORMS[form]][n_sigs]
+    assert bounds[0] == 0 and bounds[-1] == n_sigs and all(0 < b - a <= 256 for a, b in zip(bounds, bounds[1:]))
+    tb = B.TxSigBatch(tb549.keys, tb549.ids, np.ascontiguousarray(tb549.sigs[:n_sigs]), tb549.tmpls, tb549.arena)
+    pb, want_st = tb.packed(), status549[:n_sigs]
+    assert all(want_st[e] != B.VALID for b in bounds[1:-1] for e in (b - 1, b))
+    # one leaf requirement per transaction: the first signer's key, or (odd transactions) its neighbour's
+    n_tx = int(tb.sigs["tx_idx"][-1]) + 1
+    checks = np.zeros(n_tx, B.TX_CHECK_DTYPE)
+    checks["first_sig"] = np.searchsorted(tb.sigs["tx_idx"], np.arange(n_tx))
+    checks["n_sigs"] = np.bincount(tb.sigs["tx_idx"], minlength=n_tx)
+    checks["first_req"], checks["n_req"] = np.arange(n_tx), 1
+    nodes = np.zeros(n_tx, B.REQ_NODE_DTYPE)
+    nodes["a"] = (tb.sigs["key_idx"][checks["first_sig"]] + np.arange(n_tx) % 2) % len(tb.keys)
+    reqs = np.arange(n_tx, dtype=np.uint32)
+    want_v = C.run_native(C.case(pb.sigs, want_st, pb.keys, None, checks, reqs, nodes))
+    dev = torch.device("cuda", 0)
+    up = lambda x: torch.from_numpy(np.ascontiguousarray(x).view(np.uint8)).to(dev)  # noqa: E731
+    sd = torch.full((n_sigs,), 255, dtype=torch.uint8, device=dev)
+    verdicts = None
+    if form == "host24":
+        st = eng.verify_tx_signatures(tb)
+    elif form == "host12":
+        st = eng.verify_tx_signatures_packed(pb)
+    elif form == "required_host":
+        vd, rs, st = eng.verify_required_signatures_packed(pb, checks, reqs, nodes, want_status=True)
+        verdicts = vd, rs
+    elif form == "device24":
+        kd, ijd, sgd, ad = up(tb.keys), up(tb.ids), up(tb.sigs), up(tb.arena)
+        eng.verify_tx_signatures_device(kd.data_ptr(), len(tb.keys), ijd.data_ptr(), tb.n_ids, sgd.data_ptr(), n_sigs,
+                                        tb.tmpls, ad.data_ptr(), tb.arena.size, sd.data_ptr())
+    else:  # the 12-byte device forms: the stream behind the keys and templates in one arena, 16-aligned
+        off = (pb.arena.size + 15) & ~15
+        arena = np.concatenate([pb.arena, np.zeros(off - pb.arena.size, np.uint8), pb.stream, np.zeros(64, np.uint8)])
+        kd, ijd, sgd, ad = up(pb.keys), up(pb.ids), up(pb.sigs), up(arena)
+        if form == "device12":
+            eng.verify_tx_signatures_packed_device(kd.data_ptr(), len(pb.keys), ijd.data_ptr(), pb.n_ids,
+                                                   sgd.data_ptr(), n_sigs, off, pb.stream.size, pb.tmpls,
+                                                   ad.data_ptr(), arena.size, sd.data_ptr())
+        else:
+            ckd, rqd, ndd = up(checks), up(reqs), up(nodes)
+            vdd = torch.zeros(8 * n_tx, dtype=torch.uint8, device=dev)
+            rsd = torch.zeros(n_tx, dtype=torch.uint8, device=dev)
+            eng.verify_required_signatures_packed_device(
+                kd.data_ptr(), len(pb.keys), ijd.data_ptr(), pb.n_ids, sgd.data_ptr(), n_sigs, off, pb.stream.size,
+                pb.tmpls, ad.data_ptr(), arena.size, 0, ckd.data_ptr(), n_tx, rqd.data_ptr(), n_tx, ndd.data_ptr(),
+                n_tx, sd.data_ptr(), vdd.data_ptr(), rsd.data_ptr())
+            torch.cuda.synchronize()
+            verdicts = vdd.cpu().numpy().view(B.TX_VERDICT_DTYPE), rsd.cpu().numpy()
+    if "device" in form:
+        torch.cuda.synchronize()
+        st = sd.cpu().numpy()
+    bad = np.flatnonzero(st != want_st)
+    assert bad.size == 0, f"{form}, {n_sigs} signatures, chunks {bounds}: statuses differ at {bad[:8]}"
+    if verdicts is not None:
+        C.assert_same(verdicts, want_v, what=f"{form}, {n_sigs} signatures")

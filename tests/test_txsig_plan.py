@@ -36,6 +36,8 @@ def _lib():
     L = ctypes.CDLL(SO)
     L.tp_bounds.argtypes = [U64, U64, ctypes.c_int, U64, VP, U64, VP]
     L.tp_bounds.restype = U64
+    L.tp_equal_bounds.argtypes = [U64, U64, VP, U64]
+    L.tp_equal_bounds.restype = U64
     for f, n in ((L.tp_sample_override, 1), (L.tp_sample_block, 1)):
         f.argtypes = [U32] * n
         f.restype = U32
@@ -138,6 +140,21 @@ def test_chunk_bounds_match_the_model_over_a_sweep():
         for chunk_set in (False, True):
             for fd in (0, 1, 2, 6, 8):
                 assert _bounds(n, chunk, chunk_set, fd) == _bounds_model(n, chunk, chunk_set, fd)
+
+
+@pytest.mark.parametrize("per", [1, 256, 40_001])
+def test_equal_bounds(per):
+    """equal_bounds(n, per) = {0, per, 2 per, ..., n}: the bounds and the chunk sizes equal the closed forms
+    launch_chunked used before it took a bounds vector (chunk k = per items from k per, the last one the rest)."""
+    for n in sorted({per - 1, per, per + 1, 2 * per, 2 * per + 1, 3 * per - 1, 1} - {0}):
+        out = np.zeros(8, dtype=np.uint64)
+        m = _lib().tp_equal_bounds(n, per, out.ctypes.data, len(out))
+        b = [int(x) for x in out[:m]]
+        nch = -(-n // per)
+        assert b[0] == 0 and b[-1] == n and len(b) == nch + 1, (n, per, b)
+        assert all(b[k + 1] - b[k] == per for k in range(nch - 1)) and 0 < b[-1] - b[-2] <= per, (n, per, b)
+        for k in range(nch):
+            assert b[k] == k * per and b[k + 1] - b[k] == min(per, n - k * per), (n, per, k, b)
 
 
 # ---------------------------------------------------------------- key-use counts
