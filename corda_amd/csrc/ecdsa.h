@@ -583,7 +583,7 @@ CG_HD bool der_int(const Src& b, uint32_t n, uint32_t* i, u256w& out, bool* in_r
   (*i)++;
   uint32_t ln;
   if (!der_len(b, n, i, &ln)) return false;
-  if (ln == 0 || *i + ln > n) return false;
+  if (ln == 0 || ln > n - *i) return false;  // *i <= n here; `*i + ln` would wrap for a 4-byte length near 2^32
   const uint32_t c0 = b.byte(*i);
   const uint32_t c1 = ln > 1 ? b.byte(*i + 1) : 0;
   if (ln > 1 && ((c0 == 0 && c1 < 0x80u) || (c0 == 0xffu && c1 >= 0x80u))) return false;
