@@ -437,96 +437,108 @@ struct ChunkOpts {
   bool prepare_blocks = false;
 };
 
-// Key tables once for the whole call (sized by every item's key use), then the items in chunks:
-// chunk k = items [bounds[k], bounds[k + 1]) (bounds[0] = 0, the last one = r.n_items).
-hipError_t launch_chunked(cg_ctx* c, const cg::VerifyReq& r, const std::vector<uint64_t>& bounds, hipStream_t s,
-                          const ChunkOpts& o) {
-  if (r.n_items == 0) return hipSuccess;
-  const cg::WidePool wp = wide_for(c, r.n_keys, r.n_items);
-  hipError_t e = c->eng->launch_keyprep(r, c->keyprep.p, s, c->fork, &wp, o.uses);
-  if (e == hipSuccess) e = rsa_keyprep(c, r, s);
-  // the RSA pass over the whole call, after the last chunk's back
-  auto rsa_pass = [&](hipError_t x) {
-    if (x == hipSuccess) c->kc_open = false;  // every kernel of the call is enqueued, the cache's commits among them
-    return x != hipSuccess ? x : rsa_items(c, r, s);
-  };
-  // `per` (the largest chunk) sizes the item workspaces
-  const uint64_t nch = bounds.size() - 1, per = cg::largest_chunk(bounds);
-  auto at = [&](uint64_t k) { return bounds[k]; };
-  auto cnt = [&](uint64_t k) { return bounds[k + 1] - bounds[k]; };
-  // chunk k's item workspace: half k % 2 when the buffer holds two (ensure_ws), else the one
-  const bool two = nch > 1 && c->itemws.cap >= 2 * item_half_bytes(c, per);
-  const cg::ItemArgs call = {r, c->keyprep.p, c->itemws.p, c->btab, &wp};
-  auto chunk = [&](uint64_t k) {
-    cg::ItemArgs a = call;
-    a.d_items = r.d_items + at(k);
-    a.n_items = cnt(k);
-    a.d_status = r.d_status + at(k);
-    a.d_item_ws = (uint8_t*)c->itemws.p + (two ? (k & 1) * item_half_bytes(c, per) : 0);
+// launch_schedule.h's engine over a context: one call's request, chunk bounds and workspaces. Each
+// method enqueues through the context's engine build on the call's stream `s`.
+struct CallEng {
+  using Error = hipError_t;
+  static constexpr Error kOk = hipSuccess;
+  using Clock = std::chrono::steady_clock;
+  cg_ctx* c;
+  const cg::VerifyReq& r;
+  hipStream_t s;
+  const cg::WidePool* wp;               // null: no pools (prepared keys)
+  const std::vector<uint64_t>& bounds;  // chunk k = items [bounds[k], bounds[k + 1])
+  const ChunkOpts& o;
+  uint64_t half_bytes = 0;              // of one item workspace when the buffer holds two
+  bool closes_cache = true;             // the call claimed wide-table cache slots (wide_for)
+  Clock::time_point h0;                 // CG_HOST_TRACE: the host's time to enqueue a chunk
+  double prep_ms = 0, front_ms = 0, back_ms = 0;
+  const char* where = "launch_items";   // the failing step's name in the error text
+
+  static double ms(Clock::time_point a, Clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); }
+  // chunk k's items and status bytes, over item workspace `half`
+  cg::ItemArgs chunk(unsigned k, int half) const {
+    cg::ItemArgs a = {r, c->keyprep.p, c->itemws.p, c->btab, wp};
+    a.d_items = r.d_items + bounds[k];
+    a.n_items = bounds[k + 1] - bounds[k];
+    a.d_status = r.d_status + bounds[k];
+    a.d_item_ws = (uint8_t*)c->itemws.p + (size_t)half * half_bytes;
     return a;
-  };
-  auto plan = [&](uint64_t k) { return c->eng->launch_items_plan(chunk(k), s, c->fork); };
-  // (the device tx-signature forms with both first chunks' items and plans before the table builds,
-  // as pre_plan does for the batch forms, measured slower: 388.3 vs 392.1 M sigs/s over 3 pairs,
-  // profiles/r06/preplan: chunk 0's Ed25519 ladder then starts earlier but shares the chip with chunk
-  // 1's ECDSA fronts, 12.5 vs 11.9 ms of ladder per step; the chip is already full in phase 1)
-  const bool pre_plan = two && !o.prepare;
-  double prep_ms = 0;  // CG_HOST_TRACE: the host's time in chunk k's prepare hook
-  auto front = [&](uint64_t k) {
-    if (o.prepare) {
-      const auto p0 = std::chrono::steady_clock::now();
-      const hipError_t w = (*o.prepare)(k, at(k), cnt(k));
-      prep_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - p0).count();
-      if (w != hipSuccess) return w;
-    }
-    return c->eng->launch_items_front(chunk(k), s, c->fork, pre_plan && k < 2);
-  };
-  // chunk k + 1's front (plan, hashes, ECDSA prep) before chunk k's back (ladders): the first
-  // chunk's wait for the key tables is spent on the next chunk's fronts. Without a prepare hook the
-  // first two plans sort before the table builds start (their look-back stalls behind the builds);
-  // with one, the builds start first: they overlap the preparation of the first chunk.
-  if (e == hipSuccess && pre_plan) e = plan(0);
-  if (e == hipSuccess && pre_plan) e = plan(1);
-  // The host forms start the table builds now, so that they overlap the first chunk's copies. The
-  // device forms have no copy to hide: their builds start after the first chunk's plan
-  // (launch_items_front), whose onesweep look-back otherwise stalls behind the builds.
-  if (e == hipSuccess && o.prepare && o.prepare_blocks) e = c->eng->launch_key_tables(c->fork, s);
-  auto back = [&](uint64_t k) {
+  }
+  Error at(const char* w, Error e) {
+    if (e != hipSuccess) where = w;
+    return e;
+  }
+  Error keyprep() { return at("launch_keyprep", c->eng->launch_keyprep(r, c->keyprep.p, s, c->fork, wp, o.uses)); }
+  Error rsa_keyprep() { return at("launch_rsa_keyprep", ::rsa_keyprep(c, r, s)); }
+  Error key_tables() { return c->eng->launch_key_tables(c->fork, s); }
+  Error prepare(unsigned k) {
+    h0 = Clock::now();
+    const hipError_t w = (*o.prepare)(k, bounds[k], bounds[k + 1] - bounds[k]);
+    prep_ms = ms(h0, Clock::now());
+    return w;
+  }
+  Error plan(unsigned k, int half) { return c->eng->launch_items_plan(chunk(k, half), s, c->fork); }
+  Error front(unsigned k, int half, bool planned) {
+    if (!o.prepare) h0 = Clock::now();
+    const hipError_t e = c->eng->launch_items_front(chunk(k, half), s, c->fork, planned);
+    front_ms = ms(h0, Clock::now());
+    return e;
+  }
+  Error back(unsigned k, int half) {
+    const auto h1 = Clock::now();
     if (k == 0 && c->htrace && c->backt[0]) {  // chunk 0's front done; every table family built
       hipEventRecord(c->backt[0], s);
       hipStream_t t = c->copy2;  // idle by now: the marker waits there, nothing else does
       for (int q = 0; q < 3; ++q) hipStreamWaitEvent(t, c->fork.ready[q], 0);
       hipEventRecord(c->backt[1], t);
     }
-    c->fork.mark = c->htrace && 3 * k + 2 < c->fbt.size() ? c->fbt[3 * k + 2] : nullptr;  // before the joins
-    const hipError_t x = c->eng->launch_items_back(chunk(k), s, c->fork);
+    c->fork.mark = c->htrace && 3 * (size_t)k + 2 < c->fbt.size() ? c->fbt[3 * k + 2] : nullptr;  // before the joins
+    const hipError_t x = c->eng->launch_items_back(chunk(k, half), s, c->fork);
     c->fork.mark = nullptr;
-    if (c->htrace && 3 * k + 1 < c->fbt.size()) hipEventRecord(c->fbt[3 * k + 1], s);  // back k ends
+    if (c->htrace && 3 * (size_t)k + 1 < c->fbt.size()) hipEventRecord(c->fbt[3 * k + 1], s);  // back k ends
+    back_ms = ms(h1, Clock::now());
     return x;
-  };
-  if (o.prepare_blocks) {
-    // host copies in the prepare hook block the enqueuing thread: chunk k's back goes in before
-    // chunk k + 1's copy, so the device runs chunk k's ladders during it (with chunk k + 1's front
-    // first, chunk k's ladders waited for chunk k + 1's copy: profiles/r03/v5 timeline)
-    for (uint64_t k = 0; k < nch && e == hipSuccess; ++k) {
-      const auto h0 = std::chrono::steady_clock::now();
-      e = front(k);
-      const auto h1 = std::chrono::steady_clock::now();
-      if (e == hipSuccess) e = back(k);
-      if (c->htrace)  // CG_HOST_TRACE: the host's time to enqueue chunk k (its front includes the copies)
-        fprintf(stderr, "[cg host] chunk %llu enqueue: front %.3f ms (prepare %.3f, with the copies), back %.3f ms\n",
-                (unsigned long long)k, std::chrono::duration<double, std::milli>(h1 - h0).count(), prep_ms,
-                std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - h1).count());
-    }
-    return rsa_pass(e);
   }
-  if (e == hipSuccess) e = front(0);
-  for (uint64_t k = 0; k < nch && e == hipSuccess; ++k) {
-    if (!two && k > 0) e = front(k);
-    if (two && k + 1 < nch && e == hipSuccess) e = front(k + 1);
-    if (e == hipSuccess) e = back(k);
+  void chunk_enqueued(unsigned k) const {
+    if (c->htrace)  // CG_HOST_TRACE: the host's time to enqueue chunk k (its front includes the copies)
+      fprintf(stderr, "[cg host] chunk %llu enqueue: front %.3f ms (prepare %.3f, with the copies), back %.3f ms\n",
+              (unsigned long long)k, front_ms, prep_ms, back_ms);
   }
-  return rsa_pass(e);
+  // the RSA pass over the whole call, after the last chunk's back
+  Error rsa_pass(Error x) {
+    if (x == hipSuccess && closes_cache) c->kc_open = false;  // every kernel of the call is enqueued, the cache's commits among them
+    return x != hipSuccess ? x : at("launch_rsa_items", rsa_items(c, r, s));
+  }
+  Error wait(cgs::Stream, cgs::Event e) {  // the main stream for a family's tables
+    return at("hipStreamWaitEvent", hipStreamWaitEvent(s, c->fork.ready[e - cgs::EV_READY0], 0));
+  }
+};
+
+// Key tables once for the whole call (sized by every item's key use), then the items in chunks:
+// chunk k = items [bounds[k], bounds[k + 1]) (bounds[0] = 0, the last one = r.n_items). The order
+// of the enqueues is launch_schedule.h's `chunked`.
+// (the device tx-signature forms with both first chunks' items and plans before the table builds,
+// as the batch forms have them, measured slower: 388.3 vs 392.1 M sigs/s over 3 pairs,
+// profiles/r06/preplan: chunk 0's Ed25519 ladder then starts earlier but shares the chip with chunk
+// 1's ECDSA fronts, 12.5 vs 11.9 ms of ladder per step; the chip is already full in phase 1)
+// (host copies in a blocking prepare hook: with chunk k + 1's front ahead of chunk k's back, chunk
+// k's ladders waited for chunk k + 1's copy: profiles/r03/v5 timeline)
+hipError_t launch_chunked(cg_ctx* c, const cg::VerifyReq& r, const std::vector<uint64_t>& bounds, hipStream_t s,
+                          const ChunkOpts& o) {
+  if (r.n_items == 0) return hipSuccess;
+  const cg::WidePool wp = wide_for(c, r.n_keys, r.n_items);
+  // `per` (the largest chunk) sizes the item workspaces: chunk k's is half k % 2 when the buffer
+  // holds two (ensure_ws), else the one
+  const uint64_t per = cg::largest_chunk(bounds);
+  CallEng g = {c, r, s, &wp, bounds, o};
+  g.half_bytes = item_half_bytes(c, per);
+  cgs::CallPlan p;
+  p.chunks = (unsigned)(bounds.size() - 1);
+  p.two = p.chunks > 1 && c->itemws.cap >= 2 * g.half_bytes;
+  p.hook = o.prepare != nullptr;
+  p.hook_blocks = o.prepare_blocks;
+  return cgs::chunked(g, p);
 }
 
 // ---- host-buffer verify: which arena bytes each pipeline chunk needs (txsig_plan.h)
@@ -1011,8 +1023,12 @@ int cg_prepare_keys_device(cg_ctx* c, const cg_key* d_keys, uint32_t n_keys, con
   HIP_TRY(call.open(hip_stream), "hipStreamWaitEvent");
   hipStream_t s = call.stream();
   const cg::VerifyReq r = {d_keys, n_keys, nullptr, 0, d_arena, arena_len, CG_MODE_DOVERIFY, nullptr};  // no items yet
-  HIP_TRY(c->eng->launch_keyprep(r, c->keyprep.p, s, c->fork, nullptr, nullptr), "launch_keyprep");
-  HIP_TRY(rsa_keyprep(c, r, s), "launch_rsa_keyprep");
+  // the call ends with the main stream behind every family's table builds (launch_schedule.h
+  // prepare_keys): `done` then covers the side streams' reads of the caller's key bytes
+  const std::vector<uint64_t> none = {0};
+  const ChunkOpts o;
+  CallEng keys = {c, r, s, nullptr, none, o};
+  HIP_TRY(cgs::prepare_keys(keys, n_keys != 0), keys.where);
   HIP_TRY(call.close(), "hipEventRecord");
   return CG_OK;
 }
@@ -1035,14 +1051,12 @@ int cg_verify_items_device(cg_ctx* c, const cg_key* d_keys, uint32_t n_keys, con
   HIP_TRY(call.open(hip_stream), "hipStreamWaitEvent");
   hipStream_t s = call.stream();
   const uint64_t per = chunk_of(c, n_items);
-  cg::ItemArgs a = {r, c->keyprep.p, c->itemws.p, c->btab, nullptr};
-  for (uint64_t f = 0; f < n_items; f += per) {
-    a.d_items = d_items + f;
-    a.n_items = per < n_items - f ? per : n_items - f;
-    a.d_status = d_status + f;
-    HIP_TRY(c->eng->launch_items(a, s, c->fork), "launch_items");
-  }
-  HIP_TRY(rsa_items(c, r, s), "launch_rsa_items");
+  std::vector<uint64_t> bounds = {0};  // chunks of `per`, the last one shorter
+  for (uint64_t f = 0; f < n_items; f += per) bounds.push_back(per < n_items - f ? f + per : n_items);
+  const ChunkOpts o;
+  CallEng items = {c, r, s, nullptr, bounds, o};
+  items.closes_cache = false;
+  HIP_TRY(cgs::verify_items(items, (unsigned)(bounds.size() - 1)), items.where);
   HIP_TRY(call.close(), "hipEventRecord");
   return CG_OK;
 }

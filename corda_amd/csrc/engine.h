@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../include/cordagpu.h"
+#include "launch_schedule.h"
 
 // Types shared by every build of the kernels. The radix-dependent translation units (verify.hip,
 // verify_ed.hip, verify_ec.hip, plan_sort.hip) are compiled once per fixed-base table radix, the extra
@@ -93,17 +94,14 @@ struct StageTimer {
 
 // Key-table builds deferred by launch_keyprep until the first chunk's plan is sorted (the sort's
 // decoupled look-back stalls when the table builds hold the SIMDs), then enqueued by launch_items.
-struct PendingTabs {
-  bool on = false;
+// The schedule's part (launch_schedule.h Pending: deferred or not, which families need row-0 / full
+// tables (false only when the host counts prove none does: KeyUses::host_counts), the skip mask) and
+// what the builds' launchers need.
+struct PendingTabs : cgs::Pending {
   const cg_key* keys = nullptr;
   uint32_t n_keys = 0;
   void* keyprep = nullptr;
   WidePool wide;
-  // per side stream (0 r1, 1 k1, 2 Ed25519): whether any key of the family gets row-0 / full
-  // tables; false only when the host counts prove none does (KeyUses::host_counts), so the
-  // near-empty table launch does not queue behind the wide builds for a slot
-  bool need_full[3] = {true, true, true};
-  uint32_t skip_mask = 0;  // bit f: !need_full[f] (k_key_classify checks it, k_mode_guard enforces it)
 };
 
 struct Fork {

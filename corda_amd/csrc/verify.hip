@@ -331,36 +331,6 @@ hipError_t init_btab(void* d_btab, void* d_scratch, hipStream_t stream) {
   return ec_init_const(d_btab, d_scratch, stream);
 }
 
-// The deferred table builds, forked from `stream` at this point: Ed25519 first (its ladder runs
-// first), the two curves after it (their ladders run after the Ed25519 ladder and finish); per
-// family the wide tables, then the full / row-0 ones.
-static hipError_t launch_pending_tabs(const Fork& fork, hipStream_t stream) {
-  PendingTabs& p = fork.pending;
-  if (!p.on) return hipSuccess;
-  p.on = false;
-  const KeyWs w = key_ws(p.keyprep, p.n_keys, &p.wide);
-  hipError_t e = hipEventRecord(fork.planned, stream);
-  if (e != hipSuccess) return e;
-  // Each family's builds follow its own row-base chains on its side stream and wait for no other
-  // family: the chains' raised issue priority (keyws.h chain_prio) keeps the builds from slowing
-  // them, and the curves' builds beside the Ed25519 ones are done before the first chunk's fronts.
-  // Per family the wide builds go first: the full / row-0 grids are near-empty and, launched ahead,
-  // queue behind the challenge hashes and stall the wide builds behind them.
-  for (int k : {2, 0, 1}) {
-    e = hipStreamWaitEvent(fork.side[k], fork.planned, 0);
-    if (e != hipSuccess) return e;
-    for (int full = 0; full < 2; ++full) {
-      if (full && !p.need_full[k]) continue;
-      if (k == 2) ed_launch_keyprep_tabs(p.keys, p.n_keys, w, fork.side[2], full, !full);
-      else ec_launch_keyprep_tabs(k == 0 ? CG_CURVE_R1 : CG_CURVE_K1, p.keys, p.n_keys, w, fork.side[k], full, !full);
-    }
-    e = hipEventRecord(fork.ready[k], fork.side[k]);
-    if (e != hipSuccess) return e;
-  }
-  return e;
-}
-
-hipError_t launch_key_tables(const Fork& fork, hipStream_t stream) { return launch_pending_tabs(fork, stream); }
 
 // k_key_classify's outcome from the host counts: does any key of family f (0 r1, 1 k1, 2 Ed25519)
 // end in row-0 or full-table mode? Mirrors the kernel (a counted key has u >= 1; wide when u >=
@@ -383,186 +353,266 @@ static void families_needing_full(const KeyUses& src, uint32_t n_keys, const Key
   for (int f = 0; f < 3; ++f) need[f] = low[f] || over[f == 2 ? 0 : 1];
 }
 
+// What the key stages of one call launch over.
+struct KeyArgs {
+  const VerifyReq& r;
+  const cg_item* d_items;  // null: the items are not made yet (`src`), or there are none
+  uint64_t n_items;
+  const KeyUses* src;
+  KeyWs w;
+  uint32_t all;  // k_key_init: every key counts as used by everything (no counts)
+};
+
+// launch_schedule.h over HIP: the enums as this call's streams, the fork's events and the
+// launchers. The table builds run from what launch_keyprep left in fork.pending, the item stages
+// over one chunk's ItemArgs.
+struct HipOps {
+  using Error = hipError_t;
+  static constexpr Error kOk = hipSuccess;
+  hipStream_t main;
+  const Fork& fork;
+  const KeyArgs* key = nullptr;
+  const ItemArgs* a = nullptr;
+  KeyWs w{};   // of the chunk's keys (with `a`)
+  ItemWs iw{};
+
+  HipOps(hipStream_t s, const Fork& f, const KeyArgs* k, const ItemArgs* items) : main(s), fork(f), key(k), a(items) {
+    if (!a) return;
+    w = key_ws((void*)a->d_keyprep, a->n_keys, a->wide);
+    iw = item_ws(a->d_item_ws, a->n_items);
+  }
+  hipStream_t st(cgs::Stream s) const { return s == cgs::MAIN ? main : fork.side[s - cgs::SIDE0]; }
+  hipEvent_t ev(cgs::Event e) const {
+    switch (e) {
+      case cgs::EV_START: return fork.start;
+      case cgs::EV_PLANNED: return fork.planned;
+      case cgs::EV_READY0: case cgs::EV_READY1: case cgs::EV_READY2: return fork.ready[e - cgs::EV_READY0];
+      case cgs::EV_FRONT: return fork.front;
+      case cgs::EV_ROW0_0: case cgs::EV_ROW0_1: case cgs::EV_ROW0_2: return fork.row0[e - cgs::EV_ROW0_0];
+      case cgs::EV_EC_FRONT_GO: return fork.ec_front_go;
+      case cgs::EV_EC_FRONT_DONE0: case cgs::EV_EC_FRONT_DONE1: return fork.ec_front_done[e - cgs::EV_EC_FRONT_DONE0];
+      default: return nullptr;
+    }
+  }
+  Error record(cgs::Event e, cgs::Stream s) { return hipEventRecord(ev(e), st(s)); }
+  Error wait(cgs::Stream s, cgs::Event e) { return hipStreamWaitEvent(st(s), ev(e), 0); }
+  bool mid_hook() const { return fork.mid_front != nullptr; }
+  void before_joins() {
+    if (fork.mark) hipEventRecord(fork.mark, main);
+  }
+
+  Error run(cgs::Stage stage, cgs::Stream on, int, int) {
+    hipStream_t s = st(on);
+    switch (stage) {
+      // ---- key stages
+      case cgs::ST_KEY_INIT: {
+        const uint32_t n = key->r.n_keys, kl = n > PLAN_CLASSES + 2 ? n : PLAN_CLASSES + 2;
+        hipLaunchKernelGGL(k_key_init, dim3((kl + 255) / 256), dim3(256), 0, s, n, key->all, key->w.uses, key->w.seen,
+                           key->w.full_count, key->w.wide_idx, key->w.wide_count);
+        return kOk;
+      }
+      case cgs::ST_KEY_USES:
+        hipLaunchKernelGGL(k_key_uses, dim3((unsigned)((key->n_items + 255) / 256)), dim3(256), 0, s, key->d_items,
+                           key->n_items, key->r.n_keys, key->w.uses, key->w.seen);
+        return kOk;
+      case cgs::ST_KEY_COUNTS:
+        hipLaunchKernelGGL(k_key_counts, dim3((key->r.n_keys + 255) / 256), dim3(256), 0, s, key->src->counts,
+                           key->r.n_keys, key->w.uses, key->w.seen);
+        return kOk;
+      case cgs::ST_KEY_USES_TXSIG:
+        with_records(key->src->sigs, [&](auto* recs) {
+          using Rec = std::remove_const_t<std::remove_pointer_t<decltype(recs)>>;
+          hipLaunchKernelGGL(k_key_uses_txsig<Rec>, dim3((unsigned)((key->src->n + 255) / 256)), dim3(256), 0, s, recs,
+                             key->src->n, key->r.n_keys, key->w.uses, key->w.seen);
+        });
+        return kOk;
+      case cgs::ST_KC_BEGIN:
+        hipLaunchKernelGGL(k_kc_begin, dim3(2), dim3(KC_BLOCK), 0, s, key->w.kc);
+        return kOk;
+      case cgs::ST_KEY_CLASSIFY: {
+        const KeyWs& kw = key->w;
+        hipLaunchKernelGGL(k_key_classify, dim3((key->r.n_keys + 63) / 64), dim3(64), 0, s, key->r.d_keys, key->r.n_keys,
+                           kw.uses, (const uint8_t*)kw.seen, kw.full, kw.full_count, kw.wide_idx, kw.wide, kw.wide_count,
+                           kw.row0, kw.quart, kw.cap_ed, kw.cap_ec, kw.min_ed, kw.min_ec, fork.pending.skip_mask,
+                           key->r.d_arena, key->r.arena_len, kw.kc);
+        return kOk;
+      }
+      case cgs::ST_KC_CLAIM: {
+        const KeyWs& kw = key->w;
+        hipLaunchKernelGGL(k_kc_claim, dim3(2), dim3(KC_BLOCK), 0, s, key->r.d_keys, key->r.n_keys, key->r.d_arena,
+                           key->r.arena_len, kw.wide_idx, kw.wide, kw.wide_count, kw.full, kw.full_count, kw.row0,
+                           fork.pending.skip_mask, kw.kc);
+        return kOk;
+      }
+      // decodes and row-base chains (few waves, latency-bound)
+      case cgs::ST_CHAINS_R1: case cgs::ST_CHAINS_K1:
+        ec_launch_keyprep_chains(stage == cgs::ST_CHAINS_R1 ? CG_CURVE_R1 : CG_CURVE_K1, key->r.d_keys, key->r.n_keys,
+                                 key->r.d_arena, key->r.arena_len, key->w, s);
+        return kOk;
+      case cgs::ST_CHAINS_ED:
+        ed_launch_keyprep_chains(key->r.d_keys, key->r.n_keys, key->r.d_arena, key->r.arena_len, key->w, s);
+        return kOk;
+      // the tables (the wide ones hold every SIMD for milliseconds)
+      case cgs::ST_WIDE_TABS_R1: case cgs::ST_WIDE_TABS_K1: case cgs::ST_WIDE_TABS_ED:
+      case cgs::ST_FULL_TABS_R1: case cgs::ST_FULL_TABS_K1: case cgs::ST_FULL_TABS_ED: {
+        const PendingTabs& p = fork.pending;
+        const KeyWs pw = key_ws(p.keyprep, p.n_keys, &p.wide);
+        const bool full = stage >= cgs::ST_FULL_TABS_R1;
+        const int k = stage - (full ? cgs::ST_FULL_TABS_R1 : cgs::ST_WIDE_TABS_R1);
+        if (k == 2) ed_launch_keyprep_tabs(p.keys, p.n_keys, pw, s, full, !full);
+        else ec_launch_keyprep_tabs(k == 0 ? CG_CURVE_R1 : CG_CURVE_K1, p.keys, p.n_keys, pw, s, full, !full);
+        return kOk;
+      }
+      // the only key work on the main stream: Abyte for k_ed_hash (no decode)
+      case cgs::ST_ED_ABYTE:
+        ed_launch_key_abyte(key->r.d_keys, key->r.n_keys, key->r.d_arena, key->r.arena_len, key->w, s);
+        return kOk;
+      // ---- item stages
+      case cgs::ST_MISC_STATUS:
+        hipLaunchKernelGGL(k_misc_status, dim3((unsigned)((a->n_items + 255) / 256)), dim3(256), 0, s, a->d_items,
+                           a->n_items, a->d_keys, a->n_keys, a->d_status);
+        return kOk;
+      case cgs::ST_PLAN: {  // items sorted by (scheme class, key) (plan_sort.hip)
+        Error e = kOk;
+        CG_TIME(fork, CG_STAGE_PLAN, s, e = launch_plan(a->d_items, a->n_items, a->d_keys, a->n_keys, w, iw, s));
+        return e;
+      }
+      case cgs::ST_MID_HOOK: return (*fork.mid_front)();  // (the hook clears itself)
+      case cgs::ST_EC_FRONT_R1: case cgs::ST_EC_FRONT_K1: {
+        const bool r1 = stage == cgs::ST_EC_FRONT_R1;
+        CG_TIME(fork, r1 ? CG_STAGE_R1_FRONT : CG_STAGE_K1_FRONT, s,
+                ec_launch_front(r1 ? CG_CURVE_R1 : CG_CURVE_K1, a->d_items, a->n_items, a->d_arena, a->arena_len, a->mode,
+                                a->d_status, w, a->d_msgs, a->msgs_len, iw, s));
+        return kOk;
+      }
+      case cgs::ST_ED_FRONT:
+        CG_TIME(fork, CG_STAGE_ED_HASH, s,
+                ed_launch_front(a->d_items, a->n_items, a->d_arena, a->arena_len, a->mode, a->d_status, w, a->d_msgs,
+                                a->msgs_len, iw, s));
+        return kOk;
+      case cgs::ST_ROW0_LADDER_ED:
+        CG_TIME(fork, CG_STAGE_ED_LADDER_ROW0, s,
+                ed_launch_ladder(false, a->d_items, a->n_items, a->d_status, w, iw, a->d_btab, s));
+        return kOk;
+      case cgs::ST_ROW0_LADDER_R1: case cgs::ST_ROW0_LADDER_K1: {
+        const bool r1 = stage == cgs::ST_ROW0_LADDER_R1;
+        CG_TIME(fork, r1 ? CG_STAGE_R1_LADDER_ROW0 : CG_STAGE_K1_LADDER_ROW0, s,
+                ec_launch_ladder(r1 ? CG_CURVE_R1 : CG_CURVE_K1, false, a->d_items, a->n_items, a->d_status, w, iw,
+                                 a->d_btab, s));
+        return kOk;
+      }
+      case cgs::ST_FULL_LADDER_ED:
+        CG_TIME(fork, CG_STAGE_ED_LADDER, s,
+                ed_launch_ladder(true, a->d_items, a->n_items, a->d_status, w, iw, a->d_btab, s));
+        return kOk;
+      case cgs::ST_WIDE_LADDER_ED:
+        CG_TIME(fork, CG_STAGE_ED_LADDER_WIDE, s,
+                ed_launch_ladder_wide(a->d_items, a->n_items, a->d_status, w, iw, a->d_btab, s));
+        return kOk;
+      // (16 items per lane share an inversion: ~1.6 waves per SIMD, latency-bound)
+      case cgs::ST_ED_FINISH:
+        CG_TIME(fork, CG_STAGE_ED_FINISH, s,
+                ed_launch_finish(a->d_items, a->n_items, a->d_arena, a->arena_len, a->d_status, iw, s));
+        return kOk;
+      case cgs::ST_FULL_LADDER_R1: case cgs::ST_FULL_LADDER_K1: {
+        const bool r1 = stage == cgs::ST_FULL_LADDER_R1;
+        CG_TIME(fork, r1 ? CG_STAGE_R1_LADDER : CG_STAGE_K1_LADDER, s,
+                ec_launch_ladder(r1 ? CG_CURVE_R1 : CG_CURVE_K1, true, a->d_items, a->n_items, a->d_status, w, iw,
+                                 a->d_btab, s));
+        return kOk;
+      }
+      case cgs::ST_WIDE_LADDER_R1: case cgs::ST_WIDE_LADDER_K1: {
+        const bool r1 = stage == cgs::ST_WIDE_LADDER_R1;
+        CG_TIME(fork, r1 ? CG_STAGE_R1_LADDER_WIDE : CG_STAGE_K1_LADDER_WIDE, s,
+                ec_launch_ladder_wide(r1 ? CG_CURVE_R1 : CG_CURVE_K1, a->d_items, a->n_items, a->d_status, w, iw,
+                                      a->d_btab, s));
+        return kOk;
+      }
+      case cgs::ST_MODE_GUARD:  // after every ladder and the finish of this chunk
+        hipLaunchKernelGGL(k_mode_guard, dim3(64), dim3(256), 0, s, (const uint32_t*)iw.ranges, (const uint32_t*)iw.perm,
+                           (const uint32_t*)w.full_count, fork.pending.skip_mask, a->d_status);
+        return kOk;
+      default: return hipErrorInvalidValue;  // the RSA passes and the prepare hook are cordagpu.cpp's
+    }
+  }
+};
+using Sched = cgs::Schedule<HipOps>;
+
+static cgs::Chunk chunk_of(const HipOps& ops) {
+  cgs::Chunk c;
+  c.wide_ed = ops.w.cap_ed != 0;
+  c.wide_ec = ops.w.cap_ec != 0;
+  return c;
+}
+
+// The table builds launch_keyprep deferred (launch_schedule.h key_tables).
+hipError_t launch_key_tables(const Fork& fork, hipStream_t stream) {
+  HipOps ops(stream, fork, nullptr, nullptr);
+  return Sched(ops, fork.pending).key_tables();
+}
+
 hipError_t launch_keyprep(const VerifyReq& r, void* d_keyprep, hipStream_t stream, const Fork& fork,
                           const WidePool* wide, const KeyUses* src) {
-  const cg_key* d_keys = r.d_keys;
   const uint32_t n_keys = r.n_keys;
-  const uint8_t* d_arena = r.d_arena;
-  const uint64_t arena_len = r.arena_len;
   const cg_item* d_items = src ? nullptr : r.d_items;  // with `src` the items are not made yet
   const uint64_t n_items = src ? src->n : r.n_items;
-  // a call with no keys must not inherit the previous call's skip (k_mode_guard reads it)
-  fork.pending.skip_mask = 0;
-  for (int f = 0; f < 3; ++f) fork.pending.need_full[f] = true;
-  if (n_keys == 0) return hipSuccess;
   const bool counted = d_items || src;  // tables sized by the call's key uses
-  const KeyWs w = key_ws(d_keyprep, n_keys, counted ? wide : nullptr);
+  const KeyArgs key = {r, d_items, n_items, src, key_ws(d_keyprep, n_keys, counted ? wide : nullptr), counted ? 0u : 1u};
+  cgs::KeyPlan k;
+  k.any_keys = n_keys != 0;
+  k.counted = counted;
   // use counts first (main stream; the side streams fork after them)
-  const uint32_t kl = n_keys > PLAN_CLASSES + 2 ? n_keys : PLAN_CLASSES + 2;
-  hipLaunchKernelGGL(k_key_init, dim3((kl + 255) / 256), dim3(256), 0, stream, n_keys, counted ? 0u : 1u, w.uses,
-                     w.seen, w.full_count, w.wide_idx, w.wide_count);
-  if (d_items && n_items)
-    hipLaunchKernelGGL(k_key_uses, dim3((unsigned)((n_items + 255) / 256)), dim3(256), 0, stream, d_items, n_items,
-                       n_keys, w.uses, w.seen);
-  else if (src && src->counts)
-    hipLaunchKernelGGL(k_key_counts, dim3((n_keys + 255) / 256), dim3(256), 0, stream, src->counts, n_keys, w.uses,
-                       w.seen);
-  else if (src && src->sigs.p && src->n)
-    with_records(src->sigs, [&](auto* recs) {
-      using Rec = std::remove_const_t<std::remove_pointer_t<decltype(recs)>>;
-      hipLaunchKernelGGL(k_key_uses_txsig<Rec>, dim3((unsigned)((src->n + 255) / 256)), dim3(256), 0, stream, recs,
-                         src->n, n_keys, w.uses, w.seen);
-    });
+  if (d_items && n_items) k.uses = cgs::ST_KEY_USES;
+  else if (src && src->counts) k.uses = cgs::ST_KEY_COUNTS;
+  else if (src && src->sigs.p && src->n) k.uses = cgs::ST_KEY_USES_TXSIG;
   // every mode's builds and ladders unless this call's host counts prove a family has no row-0 /
   // quarter / full key; the classification checks that proof on the device (k_mode_guard)
-  uint32_t skip_mask = 0;
-  if (!d_items && src && src->counts && src->host_counts && src->host_keys)
-    families_needing_full(*src, n_keys, w, fork.pending.need_full);
+  if (n_keys && !d_items && src && src->counts && src->host_counts && src->host_keys)
+    families_needing_full(*src, n_keys, key.w, k.need_full);
   // CG_TEST_SKIP_FAMILIES=<mask> (tests only): skip those families' row-0 / quarter / full work as
   // if the host counts had proved it unneeded, so that the device check can be seen to catch it
   static const uint32_t test_skip = [] {
     const char* v = getenv("CG_TEST_SKIP_FAMILIES");
     return v ? (uint32_t)strtoul(v, nullptr, 0) & 7u : 0u;
   }();
-  for (int f = 0; f < 3; ++f) {
-    if ((test_skip >> f) & 1u) fork.pending.need_full[f] = false;
-    if (!fork.pending.need_full[f]) skip_mask |= 1u << f;
-  }
-  fork.pending.skip_mask = skip_mask;
+  for (int f = 0; f < 3; ++f)
+    if ((test_skip >> f) & 1u) k.need_full[f] = false;
   // the wide-table cache (key_cache.h): its index before the classification probes it, the claim
-  // pass after; all on this stream, ahead of the fork
-  if (w.kc.on()) hipLaunchKernelGGL(k_kc_begin, dim3(2), dim3(KC_BLOCK), 0, stream, w.kc);
-  hipLaunchKernelGGL(k_key_classify, dim3((n_keys + 63) / 64), dim3(64), 0, stream, d_keys, n_keys, w.uses,
-                     (const uint8_t*)w.seen, w.full, w.full_count, w.wide_idx, w.wide, w.wide_count, w.row0,
-                     w.quart, w.cap_ed, w.cap_ec, w.min_ed, w.min_ec, skip_mask, d_arena, arena_len, w.kc);
-  if (w.kc.on())
-    hipLaunchKernelGGL(k_kc_claim, dim3(2), dim3(KC_BLOCK), 0, stream, d_keys, n_keys, d_arena, arena_len, w.wide_idx,
-                       w.wide, w.wide_count, w.full, w.full_count, w.row0, skip_mask, w.kc);
-  hipError_t e = hipEventRecord(fork.start, stream);
-  for (int k = 0; k < 3 && e == hipSuccess; ++k) e = hipStreamWaitEvent(fork.side[k], fork.start, 0);
-  if (e != hipSuccess) return e;
-  // now: decodes and row-base chains (few waves, latency-bound)
-  ec_launch_keyprep_chains(CG_CURVE_R1, d_keys, n_keys, d_arena, arena_len, w, fork.side[0]);
-  ec_launch_keyprep_chains(CG_CURVE_K1, d_keys, n_keys, d_arena, arena_len, w, fork.side[1]);
-  ed_launch_keyprep_chains(d_keys, n_keys, d_arena, arena_len, w, fork.side[2]);
-  // the tables (the wide ones hold every SIMD for milliseconds), wide first, then full / row 0:
-  // after the first chunk's plan sort when items follow (its decoupled look-back stalls behind
-  // them), else now
-  fork.pending.on = true;
-  fork.pending.keys = d_keys;
-  fork.pending.n_keys = n_keys;
-  fork.pending.keyprep = d_keyprep;
-  fork.pending.wide = counted && wide ? *wide : WidePool{};
-  if (!counted) e = launch_pending_tabs(fork, stream);
-  if (e != hipSuccess) return e;
-  // the only key work on the main stream: Abyte for k_ed_hash (no decode)
-  ed_launch_key_abyte(d_keys, n_keys, d_arena, arena_len, w, stream);
-  return hipGetLastError();
+  // pass after; all on the main stream, ahead of the fork
+  k.cache = key.w.kc.on();
+  k.wide_ed = key.w.cap_ed != 0;
+  k.wide_ec = key.w.cap_ec != 0;
+  // what the table builds launch over, now or after the first chunk's plan sort when items follow
+  // (its decoupled look-back stalls behind them)
+  if (n_keys) {
+    fork.pending.keys = r.d_keys;
+    fork.pending.n_keys = n_keys;
+    fork.pending.keyprep = d_keyprep;
+    fork.pending.wide = counted && wide ? *wide : WidePool{};
+  }
+  HipOps ops(stream, fork, &key, nullptr);
+  const hipError_t e = Sched(ops, fork.pending).keyprep(k);
+  return e != hipSuccess || n_keys == 0 ? e : hipGetLastError();
 }
 
 hipError_t launch_items_plan(const ItemArgs& a, hipStream_t stream, const Fork& fork) {
   if (a.n_items == 0) return hipSuccess;
-  const uint32_t B = 256;
-  const uint64_t grid = (a.n_items + B - 1) / B;
-  const KeyWs w = key_ws((void*)a.d_keyprep, a.n_keys, a.wide);
-  const ItemWs iw = item_ws(a.d_item_ws, a.n_items);
-  hipLaunchKernelGGL(k_misc_status, dim3((unsigned)grid), dim3(B), 0, stream, a.d_items, a.n_items, a.d_keys,
-                     a.n_keys, a.d_status);
-  // plan: items sorted by (scheme class, key) (plan_sort.hip)
-  hipError_t e = hipSuccess;
-  CG_TIME(fork, CG_STAGE_PLAN, stream, e = launch_plan(a.d_items, a.n_items, a.d_keys, a.n_keys, w, iw, stream));
-  return e;
+  HipOps ops(stream, fork, nullptr, &a);
+  return Sched(ops, fork.pending).items_plan(chunk_of(ops));
 }
 
 hipError_t launch_items_front(const ItemArgs& a, hipStream_t stream, const Fork& fork, bool planned) {
   if (a.n_items == 0) return hipSuccess;
-  const KeyWs w = key_ws((void*)a.d_keyprep, a.n_keys, a.wide);
-  const ItemWs iw = item_ws(a.d_item_ws, a.n_items);
-  hipError_t e = hipSuccess;
-  if (!planned) e = launch_items_plan(a, stream, fork);
-  if (e == hipSuccess) e = launch_pending_tabs(fork, stream);  // the first front starts the table builds
-  if (e == hipSuccess && fork.mid_front) e = (*fork.mid_front)();  // (the hook clears itself)
-  if (e != hipSuccess) return e;
-  // Each curve's ECDSA front (prep + s^-1: needs the decoded key, which its side stream decoded) on
-  // its side stream beside the challenge hashes (need only Abyte) here: the s^-1 batches leave ~1
-  // wave per SIMD, latency-bound alone. The side stream waits for everything enqueued on `stream`
-  // so far: this chunk's plan, and the ladders of the chunk two back, which read the item workspace
-  // this front writes. The curve's ladders join on ec_front_done (launch_items_back).
-  e = hipEventRecord(fork.ec_front_go, stream);
-  for (int k = 0; k < 2 && e == hipSuccess; ++k) {
-    const int curve = k == 0 ? CG_CURVE_R1 : CG_CURVE_K1;
-    e = hipStreamWaitEvent(fork.side[k], fork.ec_front_go, 0);
-    if (e != hipSuccess) break;
-    CG_TIME(fork, k == 0 ? CG_STAGE_R1_FRONT : CG_STAGE_K1_FRONT, fork.side[k],
-            ec_launch_front(curve, a.d_items, a.n_items, a.d_arena, a.arena_len, a.mode, a.d_status, w, a.d_msgs,
-                            a.msgs_len, iw, fork.side[k]));
-    e = hipEventRecord(fork.ec_front_done[k], fork.side[k]);
-  }
-  if (e != hipSuccess) return e;
-  CG_TIME(fork, CG_STAGE_ED_HASH, stream,
-          ed_launch_front(a.d_items, a.n_items, a.d_arena, a.arena_len, a.mode, a.d_status, w, a.d_msgs, a.msgs_len,
-                          iw, stream));
-  return hipGetLastError();
+  HipOps ops(stream, fork, nullptr, &a);
+  const hipError_t e = Sched(ops, fork.pending).items_front(chunk_of(ops), planned);
+  return e != hipSuccess ? e : hipGetLastError();
 }
 
 hipError_t launch_items_back(const ItemArgs& a, hipStream_t stream, const Fork& fork) {
   if (a.n_items == 0) return hipSuccess;
-  const KeyWs w = key_ws((void*)a.d_keyprep, a.n_keys, a.wide);
-  const ItemWs iw = item_ws(a.d_item_ws, a.n_items);
-  // Row-0 ladders on the side streams, after their tables there and the hashes here. The full-table
-  // ladders stay on `stream`: a persistent full-GPU grid on a side stream holds every slot while
-  // this stream's next fronts wait.
-  hipError_t e = hipEventRecord(fork.front, stream);
-  for (int k = 0; k < 3 && e == hipSuccess; ++k) e = hipStreamWaitEvent(fork.side[k], fork.front, 0);
-  if (e != hipSuccess) return e;
-  // (a family whose host counts prove it has no row-0 / quarter key launches none: launch_keyprep)
-  const bool* nf = fork.pending.need_full;
-  if (nf[2])
-    CG_TIME(fork, CG_STAGE_ED_LADDER_ROW0, fork.side[2],
-            ed_launch_ladder(false, a.d_items, a.n_items, a.d_status, w, iw, a.d_btab, fork.side[2]));
-  if (nf[0])
-    CG_TIME(fork, CG_STAGE_R1_LADDER_ROW0, fork.side[0],
-            ec_launch_ladder(CG_CURVE_R1, false, a.d_items, a.n_items, a.d_status, w, iw, a.d_btab, fork.side[0]));
-  if (nf[1])
-    CG_TIME(fork, CG_STAGE_K1_LADDER_ROW0, fork.side[1],
-            ec_launch_ladder(CG_CURVE_K1, false, a.d_items, a.n_items, a.d_status, w, iw, a.d_btab, fork.side[1]));
-  for (int k = 0; k < 3 && e == hipSuccess; ++k) e = hipEventRecord(fork.row0[k], fork.side[k]);
-  if (e != hipSuccess) return e;
-  // full-table ladders on `stream`, each after its tables; the wide-table ladders right after
-  // their class's full-table one (same tables-ready event)
-  hipStreamWaitEvent(stream, fork.ready[2], 0);
-  CG_TIME(fork, CG_STAGE_ED_LADDER, stream,
-          ed_launch_ladder(true, a.d_items, a.n_items, a.d_status, w, iw, a.d_btab, stream));
-  if (w.cap_ed)
-    CG_TIME(fork, CG_STAGE_ED_LADDER_WIDE, stream,
-            ed_launch_ladder_wide(a.d_items, a.n_items, a.d_status, w, iw, a.d_btab, stream));
-  // The Ed25519 finish (16 items per lane share an inversion: ~1.6 waves per SIMD, latency-bound)
-  // on side stream 2, after the row-0 ladders there and the Ed25519 ladders enqueued here, beside
-  // the ECDSA ladders on this stream; row0[2] then marks its end.
-  e = hipEventRecord(fork.front, stream);
-  if (e == hipSuccess) e = hipStreamWaitEvent(fork.side[2], fork.front, 0);
-  if (e != hipSuccess) return e;
-  CG_TIME(fork, CG_STAGE_ED_FINISH, fork.side[2],
-          ed_launch_finish(a.d_items, a.n_items, a.d_arena, a.arena_len, a.d_status, iw, fork.side[2]));
-  e = hipEventRecord(fork.row0[2], fork.side[2]);
-  if (e != hipSuccess) return e;
-  for (int k = 0; k < 2; ++k) {  // each curve's ladders after its tables and its front
-    const int curve = k == 0 ? CG_CURVE_R1 : CG_CURVE_K1;
-    hipStreamWaitEvent(stream, fork.ready[k], 0);
-    hipStreamWaitEvent(stream, fork.ec_front_done[k], 0);
-    CG_TIME(fork, k == 0 ? CG_STAGE_R1_LADDER : CG_STAGE_K1_LADDER, stream,
-            ec_launch_ladder(curve, true, a.d_items, a.n_items, a.d_status, w, iw, a.d_btab, stream));
-    if (w.cap_ec)
-      CG_TIME(fork, k == 0 ? CG_STAGE_R1_LADDER_WIDE : CG_STAGE_K1_LADDER_WIDE, stream,
-              ec_launch_ladder_wide(curve, a.d_items, a.n_items, a.d_status, w, iw, a.d_btab, stream));
-  }
-  // join the side streams: the row-0 ladders and the finish
-  if (fork.mark) hipEventRecord(fork.mark, stream);
-  for (int k = 0; k < 3; ++k) hipStreamWaitEvent(stream, fork.row0[k], 0);
-  if (fork.pending.skip_mask)  // after every ladder and the finish of this chunk
-    hipLaunchKernelGGL(k_mode_guard, dim3(64), dim3(256), 0, stream, (const uint32_t*)iw.ranges,
-                       (const uint32_t*)iw.perm, (const uint32_t*)w.full_count, fork.pending.skip_mask, a.d_status);
-  return hipGetLastError();
+  HipOps ops(stream, fork, nullptr, &a);
+  const hipError_t e = Sched(ops, fork.pending).items_back(chunk_of(ops));
+  return e != hipSuccess ? e : hipGetLastError();
 }
 
 hipError_t launch_items(const ItemArgs& a, hipStream_t stream, const Fork& fork) {

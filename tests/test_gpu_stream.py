@@ -134,6 +134,50 @@ def test_pool_two_contexts_and_drill_fault(pool):
         assert np.array_equal(ep.verify(b), ref)
 
 
+def test_prepared_keys_survive_the_caller_reusing_its_key_bytes():
+    """cg_prepare_keys_device ends with the context's stream behind the side streams' decodes and
+    table builds, so its end on the caller's stream is the end of its reads of the caller's key
+    bytes, and the next call may rewrite the key workspace (the launch schedule). On one
+    caller stream, with no pause: prepare key set A, prepare key set B (as many keys, other bytes),
+    fill the arena B was prepared from with 0xFF, then verify B's items over a second arena, in
+    which the key bytes are 0xFF too (no item stage reads key bytes: k_ec_prep and k_ed_hash take
+    the key from the key workspace). Thousands of keys per family keep the decodes in flight while
+    the fill is enqueued.
+    This is the end-to-end witness of what tests/test_launch_schedule.py proves on the CPU. It
+    depends on timing: without the joins a kind schedule still gives the oracle's verdicts, and an
+    unkind one gives CG_KEY_INVALID verdicts, never worse (the one run made without them had 5983 of
+    the 8192 verdicts wrong)."""
+    import torch
+    from corda_amd.engine import Engine
+    from tools.workload import wl
+    a, _, _ = wl.notary_pool(1 << 12, ed_keys=3000, ec_keys=2000, seed=901, nthreads=16)
+    b, _, _ = wl.notary_pool(1 << 13, ed_keys=3000, ec_keys=2000, seed=902, nthreads=16)
+    assert len(a.keys) == len(b.keys) >= 7000 and not np.array_equal(a.arena[:4096], b.arena[:4096])
+    ref = c_oracle.verify_batch(b, B.MODE_DOVERIFY, 16)
+    assert (ref == B.VALID).any() and (ref == B.INVALID).any()
+    items_arena = b.arena.copy()
+    for k in b.keys:
+        items_arena[int(k["off"]):int(k["off"]) + int(k["len"])] = 0xFF
+    dev = torch.device("cuda", 0)
+    up = lambda x: torch.from_numpy(np.ascontiguousarray(x).view(np.uint8)).to(dev)  # noqa: E731
+    ka, aa, kb, ab, ib, ab2 = (up(x) for x in (a.keys, a.arena, b.keys, b.arena, b.items, items_arena))
+    sd = torch.full((b.n,), 255, dtype=torch.uint8, device=dev)
+    s = torch.cuda.Stream(device=dev)
+    torch.cuda.synchronize()
+    with Engine(0, chunk_items=3000) as eng:
+        with torch.cuda.stream(s):
+            eng.prepare_keys_device(ka.data_ptr(), len(a.keys), aa.data_ptr(), a.arena.size, stream=s.cuda_stream)
+            eng.prepare_keys_device(kb.data_ptr(), len(b.keys), ab.data_ptr(), b.arena.size, stream=s.cuda_stream)
+            ab.fill_(0xFF)
+            aa.fill_(0xFF)
+            eng.verify_items_device(kb.data_ptr(), len(b.keys), ib.data_ptr(), b.n, ab2.data_ptr(), b.arena.size,
+                                    sd.data_ptr(), stream=s.cuda_stream)
+            got = sd.clone()
+        torch.cuda.synchronize()
+    got = got.cpu().numpy()
+    assert np.array_equal(got, ref), f"{np.count_nonzero(got != ref)} of {b.n} verdicts differ from the oracle's"
+
+
 def test_device_forms_on_a_caller_stream():
     """Every device form no other test runs on a caller's stream: cg_prepare_keys_device +
     cg_verify_items_device, cg_sha256_batch_device, cg_tx_ids_device, cg_verify_transactions_device,
