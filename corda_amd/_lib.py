@@ -180,6 +180,25 @@ def lib():
                 L.cg_table_bytes.restype = u64
                 L.cg_table_choice.argtypes = [u64, u64]
                 L.cg_table_choice.restype = u32
+            if hasattr(L, "cg_signers_load"):  # older builds (A/B variants) lack the Ed25519 signer
+                L.cg_signers_load.argtypes = [vp, vp, u32, vp]
+                L.cg_signers_load.restype = i32
+                L.cg_signers_clear.argtypes = [vp]
+                L.cg_signers_clear.restype = i32
+                L.cg_sign_tx_ids.argtypes = [vp, vp, u64, vp, u64, vp, u32, vp, u64, vp, vp]
+                L.cg_sign_tx_ids.restype = i32
+                L.cg_sign_tx_ids_device.argtypes = [vp, vp, u64, vp, u64, vp, u32, vp, u64, vp, vp, vp]
+                L.cg_sign_tx_ids_device.restype = i32
+                L.cg_sign_batch.argtypes = [vp, vp, u64, vp, u64, vp, vp]
+                L.cg_sign_batch.restype = i32
+                if pool:
+                    L.cg_pool_signers_load.argtypes = [vp, vp, u32, vp]
+                    L.cg_pool_signers_load.restype = i32
+                    L.cg_pool_signers_clear.argtypes = [vp]
+                    L.cg_pool_signers_clear.restype = i32
+                    L.cg_pool_sign_tx_ids.argtypes = [vp, vp, u64, vp, u64, vp, u32, vp, u64, vp, vp,
+                                                      ctypes.POINTER(cg_pool_stats)]
+                    L.cg_pool_sign_tx_ids.restype = i32
             if hasattr(L, "cg_rsa_key_bits"):  # older builds (A/B variants) lack the RSA path
                 L.cg_rsa_key_bits.argtypes = [ctypes.c_char_p, u32]
                 L.cg_rsa_key_bits.restype = u32

@@ -24,6 +24,10 @@ TMPL_DTYPE = np.dtype([("prefix_off", "<u8"), ("suffix_off", "<u8"), ("prefix_le
 # 4-byte-aligned end of the one before it)
 TXSIG12_DTYPE = np.dtype([("tx_idx", "<u4"), ("key_idx", "<u4"), ("sig_len", "<u2"), ("tmpl", "<u2")])
 assert TXSIG12_DTYPE.itemsize == 12
+# cg_sign_req / cg_sign_item (include/cordagpu.h): the Ed25519 signer's requests
+SIGN_REQ_DTYPE = np.dtype([("tx_idx", "<u4"), ("signer", "<u2"), ("tmpl", "<u2")])
+SIGN_ITEM_DTYPE = np.dtype([("msg_off", "<u8"), ("msg_len", "<u4"), ("signer", "<u4")])
+assert SIGN_REQ_DTYPE.itemsize == 8 and SIGN_ITEM_DTYPE.itemsize == 16
 # tear-offs (cg_pmt_node / cg_filtered_leaf / cg_filtered_tx)
 PMT_NODE_DTYPE = np.dtype([("hash_off", "<u8"), ("kind", "<u4"), ("reserved", "<u4")])
 FLEAF_DTYPE = np.dtype([("off", "<u8"), ("nonce_off", "<u8"), ("len", "<u4"), ("flags", "<u4")])
@@ -340,6 +344,57 @@ class TxSigBuilder(BatchBuilder):
             tmpls[i] = t
         ids = np.frombuffer(b"".join(self._ids), dtype=np.uint8).copy() if self._ids else np.zeros(0, np.uint8)
         return TxSigBatch(b.keys, ids, sigs, tmpls, b.arena)
+
+
+class SignRequests:
+    """cg_sign_tx_ids input: ``ids`` (uint8 [n_ids * 32]), ``reqs`` (SIGN_REQ_DTYPE: tx_idx indexes
+    ids, signer the loaded signer set, tmpl indexes tmpls), ``tmpls`` (TMPL_DTYPE), ``arena`` (uint8:
+    the template bytes)."""
+
+    def __init__(self, ids, reqs, tmpls, arena):
+        self.ids = np.ascontiguousarray(ids, dtype=np.uint8).reshape(-1)
+        self.reqs, self.tmpls, self.arena = reqs, tmpls, arena
+
+    @property
+    def n(self):
+        return len(self.reqs)
+
+    @property
+    def n_ids(self):
+        return self.ids.size // 32
+
+
+class SignRequestBuilder(BatchBuilder):
+    """Packs Crypto.doSign(keyPair, SignableData(txId, metadata)) requests the way a JVM caller of
+    cg_sign_tx_ids would: one id per distinct tx id, one template per distinct SignatureMetadata
+    (its SignableData prefix / suffix), then one 8-byte request per signature."""
+
+    def __init__(self):
+        super().__init__()
+        self._ids, self._id_index = [], {}
+        self._tmpls, self._tmpl_index = [], {}
+        self._reqs = []
+
+    tx_id = TxSigBuilder.tx_id
+    template = TxSigBuilder.template
+
+    def add_request(self, signer, tx_idx, tmpl_idx):
+        if not 0 <= signer <= 0xFFFF:
+            raise ValueError("cg_sign_req.signer is 16-bit")
+        self._reqs.append((tx_idx, signer, tmpl_idx))
+        return len(self._reqs) - 1
+
+    def build(self):
+        b = super().build()
+        reqs = np.zeros(len(self._reqs), dtype=SIGN_REQ_DTYPE)
+        if self._reqs:
+            arr = np.array(self._reqs, dtype=np.uint64)
+            reqs["tx_idx"], reqs["signer"], reqs["tmpl"] = arr[:, 0], arr[:, 1], arr[:, 2]
+        tmpls = np.zeros(len(self._tmpls), dtype=TMPL_DTYPE)
+        for i, t in enumerate(self._tmpls):
+            tmpls[i] = t
+        ids = np.frombuffer(b"".join(self._ids), dtype=np.uint8).copy() if self._ids else np.zeros(0, np.uint8)
+        return SignRequests(ids, reqs, tmpls, b.arena)
 
 
 class RequirementBuilder:

@@ -31,6 +31,20 @@ i2p GroupElement) -> IllegalArgumentException("not a valid point"); an X.509 key
 Crypto.decodePublicKey (Crypto.kt:349-356, the ECDSA Kryo path Kryo.kt:388-398) ->
 InvalidKeySpecException("This public key cannot be decoded, ...").
 
+Signing (Crypto.kt:395-402, :415-422), EDDSA_ED25519_SHA512 only, on the GPU:
+  * ``Crypto.do_sign(private_key, clear_data)`` -- doSign(privateKey, clearData): an unsupported scheme
+    -> IllegalArgumentException; empty clear data -> Exception("Signing of an empty array is not
+    permitted!"); returns the 64 signature bytes i2p's EdDSAEngine.engineSign writes (RFC 8032).
+  * ``Crypto.do_sign_tx(key_pair, signable_data)`` -- doSign(keyPair, signableData): a pair whose halves
+    have different schemes -> IllegalArgumentException("Metadata schemeCodeName: ... is not aligned with
+    the key type: ..."); returns a TransactionSignature. The mirror also refuses a pair whose public
+    key is not the private key's (the Abyte ``Engine.load_signers`` returns).
+  * ``Crypto.sign_all(key_pair, tx_ids, metadata)`` -- the batch form: NotaryService.sign(txId)
+    (NotaryService.kt:77-80) for many ids in one call.
+  A private key of another scheme raises UnsupportedOperationException, as SPHINCS verification does:
+  there is no host ECDSA / RSA signer in this mirror (BC draws k and the PSS salt at random, so there is
+  nothing bit-exact to reproduce; a JVM caller keeps its own Crypto.doSign for them).
+
 Public keys are ``PublicKey(scheme, encoded, fmt)`` (fmt: raw / SPKI / SEC1), the byte forms a JVM
 caller hands over JNI; two PublicKeys are equal when their X.509 encodings are (as JVM keys are),
 and ``CompositeKey`` (corda_amd/composite.py) is a PublicKey too.
@@ -63,7 +77,7 @@ SCHEME_CODE_NAMES = {
 GPU_SCHEMES = (ECDSA_SECP256K1_SHA256, ECDSA_SECP256R1_SHA256, EDDSA_ED25519_SHA512)
 HOST_EXCEPTION = 240  # mirror-only status: decided on the host with an exception (see verify_batch_ex)
 
-__all__ = ["Crypto", "PublicKey", "BatchItem", "TransactionSignature", "SignatureException", "InvalidKeyException",
+__all__ = ["Crypto", "PublicKey", "PrivateKey", "KeyPair", "SignableData", "BatchItem", "TransactionSignature", "SignatureException", "InvalidKeyException",
            "IllegalArgumentException", "InvalidKeySpecException", "UnsupportedOperationException", "HOST_EXCEPTION"]
 
 
@@ -98,6 +112,38 @@ class PublicKey:
         return f"PublicKey({SCHEME_CODE_NAMES.get(self.scheme, self.scheme)}, {self.spki().hex()[-16:]})"
 
 
+@dataclass(frozen=True, eq=False)
+class PrivateKey:
+    """A private key as the node's key store holds it. EDDSA_ED25519_SHA512: ``encoded`` is the 32-byte
+    seed of EdDSAPrivateKeySpec(seed)."""
+    scheme: int
+    encoded: bytes
+
+    def __eq__(self, other):
+        return isinstance(other, PrivateKey) and self.scheme == other.scheme and self.encoded == other.encoded
+
+    def __hash__(self):
+        return hash((self.scheme, self.encoded))
+
+    def __repr__(self):  # never the key bytes
+        return f"PrivateKey({SCHEME_CODE_NAMES.get(self.scheme, self.scheme)})"
+
+
+@dataclass(frozen=True)
+class KeyPair:
+    """java.security.KeyPair"""
+    public: PublicKey
+    private: PrivateKey
+
+
+@dataclass(frozen=True)
+class SignableData:
+    """SignableData(txId, SignatureMetadata(platformVersion, schemeNumberID)) (SignableData.kt:13)."""
+    tx_id: bytes
+    platform_version: int = 1
+    scheme_number_id: int = 4
+
+
 @dataclass(frozen=True)
 class TransactionSignature:
     """TransactionSignature(bytes, by, SignatureMetadata(platformVersion, schemeNumberID))
@@ -128,6 +174,9 @@ class _Crypto:
         self._engine = None
         self._lock = threading.Lock()
         self.last_errors = {}
+        self._signers = []       # the private keys loaded into the engine, by signer index
+        self._signer_pub = []    # their Abytes
+        self._signer_engine = None
 
     def engine(self):
         with self._lock:
@@ -324,6 +373,91 @@ class _Crypto:
     def is_valid(self, public_key, signature_data, clear_data):
         """Crypto.isValid(publicKey, signatureData, clearData) (Crypto.kt:536 -> :553-559)."""
         return self._one(public_key, signature_data, clear_data, B.MODE_ISVALID)
+
+    # ------------------------------------------------------------------ signing
+    def _sign_scheme(self, private_key, clear_len):
+        """doSign's checks in its order (Crypto.kt:396-398), then the mirror's own limit."""
+        if private_key.scheme not in SCHEME_CODE_NAMES or private_key.scheme == COMPOSITE_KEY:
+            raise IllegalArgumentException(f"Unsupported key/algorithm for schemeCodeName: {private_key.scheme}")
+        if clear_len == 0:
+            raise Exception("Signing of an empty array is not permitted!")
+        if private_key.scheme != EDDSA_ED25519_SHA512:
+            raise UnsupportedOperationException(
+                f"no signer for scheme {SCHEME_CODE_NAMES[private_key.scheme]} in this mirror; the JVM caller keeps "
+                "its own Crypto.doSign")
+        if len(private_key.encoded) != 32:
+            raise InvalidKeyException("an Ed25519 private key is a 32-byte seed")
+
+    def _signer(self, private_key):
+        """(signer index, Abyte) of a key in the engine's signer set, loading it when it is new."""
+        eng = self.engine()
+        with self._lock:
+            if self._signer_engine is not eng:
+                self._signers, self._signer_pub, self._signer_engine = [], [], eng
+            if private_key not in self._signers:
+                keys = self._signers + [private_key]
+                self._signer_pub = eng.load_signers([k.encoded for k in keys])
+                self._signers = keys
+            i = self._signers.index(private_key)
+            return i, self._signer_pub[i]
+
+    def forget_signers(self):
+        """Zeroes and frees the engine's signer set (cg_signers_clear)."""
+        with self._lock:
+            if self._signer_engine is not None:
+                self._signer_engine.clear_signers()
+            self._signers, self._signer_pub, self._signer_engine = [], [], None
+
+    @staticmethod
+    def _sign_status(status):
+        if status == B.EMPTY:
+            raise Exception("Signing of an empty array is not permitted!")
+        if status != 0:
+            raise RuntimeError(f"item not signed (status {status})")
+
+    def do_sign(self, private_key, clear_data):
+        """Crypto.doSign(privateKey, clearData) (Crypto.kt:395-402)."""
+        clear_data = bytes(clear_data)
+        self._sign_scheme(private_key, len(clear_data))
+        i, _ = self._signer(private_key)
+        sigs, st = self.engine().sign([(i, clear_data)])
+        self._sign_status(int(st[0]))
+        return sigs[0].tobytes()
+
+    def _aligned_signer(self, key_pair):
+        """The key-pair check of Crypto.kt:416-419, then the signer index."""
+        sig_key = self.find_signature_scheme(key_pair.private)
+        sig_meta = self.find_signature_scheme(key_pair.public)
+        if sig_key != sig_meta:
+            raise IllegalArgumentException(f"Metadata schemeCodeName: {SCHEME_CODE_NAMES[sig_meta]} is not aligned with "
+                                           f"the key type: {SCHEME_CODE_NAMES[sig_key]}.")
+        self._sign_scheme(key_pair.private, 1)
+        i, abyte = self._signer(key_pair.private)
+        if K.canonical_spki(EDDSA_ED25519_SHA512, B.KEY_RAW, abyte) != key_pair.public.spki():
+            raise IllegalArgumentException("The public key of this pair is not the private key's.")
+        return i
+
+    def do_sign_tx(self, key_pair, signable_data):
+        """Crypto.doSign(keyPair, signableData) (Crypto.kt:415-422) -> TransactionSignature."""
+        return self.sign_all(key_pair, [signable_data.tx_id],
+                             (signable_data.platform_version, signable_data.scheme_number_id))[0]
+
+    def sign_all(self, key_pair, tx_ids, metadata=(1, 4)):
+        """NotaryService.sign(txId) (NotaryService.kt:77-80) for every id in one call:
+        Crypto.doSign(keyPair, SignableData(txId, SignatureMetadata(*metadata))) each."""
+        from . import signable
+        signer = self._aligned_signer(key_pair)
+        if not tx_ids:
+            return []
+        pv, sid = metadata
+        b = B.SignRequestBuilder()
+        t = b.template(*signable.template(pv, sid))
+        for tx_id in tx_ids:
+            b.add_request(signer, b.tx_id(tx_id), t)
+        sigs, st = self.engine().sign_tx_ids(b.build())
+        for s in st:
+            self._sign_status(int(s))
+        return [TransactionSignature(sigs[j].tobytes(), key_pair.public, pv, sid) for j in range(len(tx_ids))]
 
     def do_verify_tx(self, tx_id, ts):
         """Crypto.doVerify(txId, transactionSignature) (Crypto.kt:499-502)."""

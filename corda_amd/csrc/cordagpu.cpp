@@ -179,6 +179,11 @@ struct cg_ctx : cg::CallState<HipStreams> {
   DevBuf txvws, txvio;
   // tear-offs: leaf-hash workspace
   DevBuf ftxws;
+  // The Ed25519 signer (sign_ed.hip). signers: the expanded keys, an allocation of its own made by
+  // cg_signers_load and zeroed before it is freed (secret: a, prefix); a context that never signs
+  // allocates neither. signws: a chunk's r column and digit slots, zeroed behind every sign call.
+  DevBuf signers, signws;
+  uint32_t n_signers = 0;
   // host-buffer verify: one event per pipeline chunk (seg); timing events for cg_stats (tev)
   // a second stream on a hardware queue of its own, idle in every schedule: the CG_HOST_TRACE marker
   // "tables built" waits there (launch_chunked)
@@ -851,11 +856,24 @@ int cg_open(cg_ctx** out, const cg_config* cfg) {
   return CG_OK;
 }
 
+// The signer store zeroed, then freed (cg_signers_clear, a reload, cg_close), after the device has
+// finished whatever still reads it.
+static void signers_drop(cg_ctx* c) {
+  c->n_signers = 0;
+  if (!c->signers.p) return;
+  (void)hipDeviceSynchronize();
+  (void)hipMemset(c->signers.p, 0, c->signers.cap);
+  (void)hipDeviceSynchronize();
+  c->signers.release();
+}
+
 void cg_close(cg_ctx* c) {
   if (!c) return;
   if (c->counted) --g_live_ctx;
   hipSetDevice(c->device);
   if (c->stream) hipStreamSynchronize(c->stream);
+  signers_drop(c);
+  c->signws.release();
   c->keyprep.release();
   c->itemws.release();
   c->wide.release();
@@ -2071,6 +2089,178 @@ int cg_verify_filtered(cg_ctx* c, const cg_filtered_tx* ftxs, uint64_t n_ftx, co
   return CG_OK;
 }
 
+// ---------------------------------------------------------------- Ed25519 signing (sign_ed.hip)
+static_assert(sizeof(cg_sign_req) == 8 && sizeof(cg_sign_item) == 16, "sign request layouts");
+
+// With the ctx lock held. The store: [expanded keys][seeds 32 n][Abytes 32 n]; the seeds are zeroed on
+// the stream right behind the expansion.
+static int signers_load_locked(cg_ctx* c, const uint8_t* seeds, uint32_t n, uint8_t* pubkeys_out) {
+  if (const int rc = enter(c, "cg_signers_load")) return rc;
+  signers_drop(c);
+  const size_t keys_b = (c->eng->signer_bytes() * n + 255) & ~(size_t)255, seeds_b = 32 * (size_t)n;
+  HIP_TRY(c->signers.ensure_exact(keys_b + 2 * seeds_b), "hipMalloc(signers)");
+  uint8_t* base = (uint8_t*)c->signers.p;
+  uint8_t *d_seeds = base + keys_b, *d_pub = d_seeds + seeds_b;
+  hipStream_t s = c->stream;
+  hipError_t e;
+  {
+    Call call(c, Call::kHost);
+    e = call.open();
+    if (e == hipSuccess) e = hipMemcpyAsync(d_seeds, seeds, seeds_b, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = c->eng->launch_signer_expand(d_seeds, n, base, d_pub, c->btab, s);
+    if (e == hipSuccess) e = hipMemsetAsync(d_seeds, 0, seeds_b, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(pubkeys_out, d_pub, seeds_b, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = call.close();
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+  }
+  if (e != hipSuccess) {
+    signers_drop(c);  // nothing half-loaded, no seed left behind
+    return hip_fail(e, "cg_signers_load");
+  }
+  c->n_signers = n;
+  return CG_OK;
+}
+
+int cg_signers_load(cg_ctx* c, const uint8_t* seeds, uint32_t n, uint8_t* pubkeys_out) {
+  if (!c) return fail(CG_ERR_ARG, "cg_signers_load: ctx is NULL");
+  if (n == 0 || n > CG_SIGNERS_MAX) return fail(CG_ERR_ARG, "cg_signers_load: 1 .. CG_SIGNERS_MAX signers");
+  if (!seeds || !pubkeys_out) return fail(CG_ERR_ARG, "cg_signers_load: NULL buffer");
+  std::lock_guard<std::mutex> g(c->mu);
+  return signers_load_locked(c, seeds, n, pubkeys_out);
+}
+
+int cg_signers_clear(cg_ctx* c) {
+  if (!c) return fail(CG_ERR_ARG, "cg_signers_clear: ctx is NULL");
+  std::lock_guard<std::mutex> g(c->mu);
+  HIP_TRY(hipSetDevice(c->device), "hipSetDevice");
+  signers_drop(c);
+  return CG_OK;
+}
+
+// One sign call: the caller's tables, all in host memory or all in HBM but the templates. `fused`: reqs
+// are cg_sign_req over SignableData splices of ids, else cg_sign_item over arena bytes.
+struct SignReq {
+  const void* reqs;
+  uint64_t n;
+  bool fused;
+  const uint8_t* ids;
+  uint64_t n_ids;
+  const cg_signable_tmpl* tmpls;
+  uint32_t n_tmpls;
+  const uint8_t* arena;
+  uint64_t arena_len;
+  uint8_t* sigs;
+  uint8_t* status;
+  size_t req_bytes() const { return fused ? sizeof(cg_sign_req) : sizeof(cg_sign_item); }
+};
+
+static int sign_args(const char* fn, cg_ctx* c, const SignReq& q, bool host) {
+  if (!c) return fail(CG_ERR_ARG, "%s: ctx is NULL", fn);
+  if (q.n && (!q.reqs || !q.sigs || !q.status)) return fail(CG_ERR_ARG, "%s: NULL request / signature / status buffer", fn);
+  if (q.n_ids && !q.ids) return fail(CG_ERR_ARG, "%s: ids is NULL", fn);
+  if (q.n_tmpls && !q.tmpls) return fail(CG_ERR_ARG, "%s: templates is NULL", fn);
+  if (q.n_tmpls > 0x10000u) return fail(CG_ERR_ARG, "%s: more than 65536 templates (cg_sign_req.tmpl is 16-bit)", fn);
+  if (host && q.arena_len && !q.arena) return fail(CG_ERR_ARG, "%s: arena is NULL", fn);
+  return CG_OK;
+}
+
+static hipError_t ensure_sign_ws(cg_ctx* c, const SignReq& q, uint64_t slot) {
+  return ensure_all({{&c->signws, c->eng->sign_ws_bytes(chunk_of(c, q.n))},
+                     {&c->msgs, q.fused ? cg::tx_msgs_head(q.n_tmpls, slot) : 1},
+                     {&c->tmpls, sizeof(cg_signable_tmpl) * (q.n_tmpls ? q.n_tmpls : 1)}});
+}
+
+// Every launch of a sign call over the device tables `d` on `s`: the templates' images, then each chunk
+// of at most the context's chunk items over the one sign workspace, which is zeroed behind the last
+// kernel whatever happened before (it holds every r of the last chunk).
+static hipError_t launch_sign_call(cg_ctx* c, const SignReq& d, uint64_t slot, hipStream_t s) {
+  hipError_t e = hipSuccess;
+  const cg_signable_tmpl* dt = (const cg_signable_tmpl*)c->tmpls.p;
+  if (d.fused) {
+    if (d.n_tmpls) e = hipMemcpyAsync(c->tmpls.p, d.tmpls, sizeof(cg_signable_tmpl) * d.n_tmpls, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess)
+      e = cg::launch_tx_sig_templates(dt, d.n_tmpls, d.arena, d.arena_len, slot, d.ids, d.n_ids, (uint8_t*)c->msgs.p, s);
+  }
+  const std::vector<uint64_t> bounds = cg::equal_bounds(d.n, chunk_of(c, d.n));
+  for (size_t k = 0; e == hipSuccess && k + 1 < bounds.size(); ++k) {
+    const uint64_t first = bounds[k], cnt = bounds[k + 1] - first;
+    const cg::SignArgs a = {(const uint8_t*)d.reqs + first * d.req_bytes(), cnt, d.fused, c->signers.p, c->n_signers,
+                            d.arena, d.arena_len, (const uint8_t*)c->msgs.p, dt, d.n_tmpls, d.n_ids,
+                            d.sigs + 64 * first, d.status + first, c->signws.p, c->btab};
+    e = c->eng->launch_sign(a, s);
+  }
+  const hipError_t z = hipMemsetAsync(c->signws.p, 0, c->eng->sign_ws_bytes(chunk_of(c, d.n)), s);
+  return e != hipSuccess ? e : z;
+}
+
+static int sign_device(const char* fn, cg_ctx* c, const SignReq& d, void* hip_stream) {
+  if (const int a = sign_args(fn, c, d, false)) return a;
+  if (d.n == 0) return CG_OK;
+  std::lock_guard<std::mutex> g(c->mu);
+  if (const int rc = enter(c, fn)) return rc;
+  if (c->n_signers == 0) return fail(CG_ERR_ARG, "%s: no signers loaded (cg_signers_load)", fn);
+  const uint64_t slot = tmpl_slot(d.tmpls, d.n_tmpls);
+  HIP_TRY(ensure_sign_ws(c, d, slot), "hipMalloc(sign workspace)");
+  Call call(c, Call::kDevice);
+  HIP_TRY(call.open(hip_stream), "hipStreamWaitEvent");
+  HIP_TRY(launch_sign_call(c, d, slot, call.stream()), "launch_sign");
+  HIP_TRY(call.close(), "hipEventRecord");
+  return CG_OK;
+}
+
+// A host-buffer sign call with the ctx lock held (cg_sign_tx_ids, cg_sign_batch, the pool form).
+static int sign_host_locked(const char* fn, cg_ctx* c, const SignReq& h) {
+  if (const int rc = enter(c, fn)) return rc;
+  if (c->n_signers == 0) return fail(CG_ERR_ARG, "%s: no signers loaded (cg_signers_load)", fn);
+  const uint64_t slot = tmpl_slot(h.tmpls, h.n_tmpls);
+  HIP_TRY(ensure_sign_ws(c, h, slot), "hipMalloc(sign workspace)");
+  hipStream_t s = c->stream;
+  Call call(c, Call::kHost);
+  HIP_TRY(call.open(), "hipStreamWaitEvent");
+  HIP_TRY(stage(c->items, h.reqs, h.req_bytes() * h.n, s), "H2D sign requests");
+  HIP_TRY(stage(c->arena, h.arena, h.arena_len, s, arena_room(h.arena_len)), "H2D arena");
+  HIP_TRY(stage(c->h_ids, h.ids, 32 * h.n_ids, s), "H2D ids");
+  HIP_TRY(c->aux0.ensure(64 * h.n), "hipMalloc(signatures)");
+  HIP_TRY(c->status.ensure(h.n), "hipMalloc(status)");
+  SignReq d = h;
+  d.reqs = c->items.p;
+  d.arena = (const uint8_t*)c->arena.p;
+  d.ids = (const uint8_t*)c->h_ids.p;
+  d.sigs = (uint8_t*)c->aux0.p;
+  d.status = (uint8_t*)c->status.p;
+  HIP_TRY(launch_sign_call(c, d, slot, s), "launch_sign");
+  HIP_TRY(hipMemcpyAsync(h.sigs, d.sigs, 64 * h.n, hipMemcpyDeviceToHost, s), "D2H signatures");
+  HIP_TRY(hipMemcpyAsync(h.status, d.status, h.n, hipMemcpyDeviceToHost, s), "D2H status");
+  HIP_TRY(call.close(), "hipEventRecord");
+  HIP_TRY(hipStreamSynchronize(s), "hipStreamSynchronize");
+  return CG_OK;
+}
+
+static int sign_host(const char* fn, cg_ctx* c, const SignReq& h) {
+  if (const int a = sign_args(fn, c, h, true)) return a;
+  if (h.n == 0) return CG_OK;
+  std::lock_guard<std::mutex> g(c->mu);
+  return sign_host_locked(fn, c, h);
+}
+
+int cg_sign_tx_ids(cg_ctx* c, const uint8_t* ids, uint64_t n_ids, const cg_sign_req* reqs, uint64_t n,
+                   const cg_signable_tmpl* tmpls, uint32_t n_tmpls, const uint8_t* arena, uint64_t arena_len,
+                   uint8_t* sigs_out, uint8_t* status_out) {
+  return sign_host("cg_sign_tx_ids", c, {reqs, n, true, ids, n_ids, tmpls, n_tmpls, arena, arena_len, sigs_out, status_out});
+}
+
+int cg_sign_tx_ids_device(cg_ctx* c, const uint8_t* d_ids, uint64_t n_ids, const cg_sign_req* d_reqs, uint64_t n,
+                          const cg_signable_tmpl* tmpls, uint32_t n_tmpls, const uint8_t* d_arena, uint64_t arena_len,
+                          uint8_t* d_sigs, uint8_t* d_status, void* hip_stream) {
+  return sign_device("cg_sign_tx_ids_device", c,
+                     {d_reqs, n, true, d_ids, n_ids, tmpls, n_tmpls, d_arena, arena_len, d_sigs, d_status}, hip_stream);
+}
+
+int cg_sign_batch(cg_ctx* c, const cg_sign_item* items, uint64_t n, const uint8_t* arena, uint64_t arena_len,
+                  uint8_t* sigs_out, uint8_t* status_out) {
+  return sign_host("cg_sign_batch", c, {items, n, false, nullptr, 0, nullptr, 0, arena, arena_len, sigs_out, status_out});
+}
+
 // ---------------------------------------------------------------- several devices (pool.h)
 struct cg_pool {
   std::vector<cg_ctx*> ctx;
@@ -2126,10 +2316,10 @@ int cg_pool_inject_fault(cg_pool* p, uint32_t slot, int on) {
 }
 
 // pool_run over one shard function; stats and the error message as cg_pool_verify_batch
-static int pool_call(cg_pool* p, uint64_t n_items, uint8_t* status_out, cg_pool_stats* stats, const char* name,
-                     const std::function<int(cg_ctx*, uint64_t, uint64_t)>& shard) {
+// with the pool lock held
+static int pool_call_locked(cg_pool* p, uint64_t n_items, uint8_t* status_out, cg_pool_stats* stats, const char* name,
+                            const std::function<int(cg_ctx*, uint64_t, uint64_t)>& shard) {
   const auto t0 = std::chrono::steady_clock::now();
-  std::lock_guard<std::mutex> g(p->mu);
   std::vector<std::string> errs(p->ctx.size());
   cg::PoolReport rep;
   const int rc = cg::pool_run(p->healthy, n_items, status_out,
@@ -2164,6 +2354,11 @@ static int pool_call(cg_pool* p, uint64_t n_items, uint8_t* status_out, cg_pool_
     g_err = m;
   }
   return rc;
+}
+static int pool_call(cg_pool* p, uint64_t n_items, uint8_t* status_out, cg_pool_stats* stats, const char* name,
+                     const std::function<int(cg_ctx*, uint64_t, uint64_t)>& shard) {
+  std::lock_guard<std::mutex> g(p->mu);
+  return pool_call_locked(p, n_items, status_out, stats, name, shard);
 }
 
 int cg_pool_verify_tx_signatures(cg_pool* p, const cg_key* keys, uint32_t n_keys, const uint8_t* ids, uint64_t n_ids,
@@ -2209,6 +2404,79 @@ int cg_pool_verify_transactions(cg_pool* p, const cg_tx* txs, uint64_t n_tx, con
     return r;
   });
   if (stats) stats->not_run = rc == CG_OK ? 0 : n_sigs;
+  return rc;
+}
+
+// The signer set on every slot. A slot whose load fails with a device fault is marked unhealthy (it
+// holds no set: a later sign call on it is refused, and the pool moves on as for a fault).
+int cg_pool_signers_load(cg_pool* p, const uint8_t* seeds, uint32_t n, uint8_t* pubkeys_out) {
+  const char* fn = "cg_pool_signers_load";
+  if (!p) return fail(CG_ERR_ARG, "%s: pool is NULL", fn);
+  if (p->ctx.empty()) return fail(CG_ERR_ARG, "%s: empty pool", fn);
+  if (n == 0 || n > CG_SIGNERS_MAX) return fail(CG_ERR_ARG, "%s: 1 .. CG_SIGNERS_MAX signers", fn);
+  if (!seeds || !pubkeys_out) return fail(CG_ERR_ARG, "%s: NULL buffer", fn);
+  std::lock_guard<std::mutex> g(p->mu);
+  std::vector<uint8_t> pub(32 * (size_t)n);
+  bool any = false;
+  int last = CG_ERR_DEVICE;
+  for (size_t k = 0; k < p->ctx.size(); ++k) {
+    cg_ctx* c = p->ctx[k];
+    std::lock_guard<std::mutex> gc(c->mu);
+    const bool drill = c->fault;  // the drill fails every call; the set is loaded all the same, for the
+    c->fault = false;             // moment the drill is cleared
+    const int rc = signers_load_locked(c, seeds, n, any ? pub.data() : pubkeys_out);
+    c->fault = drill;
+    if (rc == CG_OK) any = true;
+    else if (rc == CG_ERR_DEVICE) p->healthy[k] = 0;
+    if (rc != CG_OK) last = rc;
+  }
+  return any ? CG_OK : last;
+}
+
+int cg_pool_signers_clear(cg_pool* p) {
+  if (!p) return fail(CG_ERR_ARG, "cg_pool_signers_clear: pool is NULL");
+  std::lock_guard<std::mutex> g(p->mu);
+  for (cg_ctx* c : p->ctx) {
+    std::lock_guard<std::mutex> gc(c->mu);
+    if (hipSetDevice(c->device) == hipSuccess) signers_drop(c);
+  }
+  return CG_OK;
+}
+
+// The whole call on one live slot, and on a device fault the next one (cg_pool_verify_transactions'
+// pattern: pool_run over a single unit).
+int cg_pool_sign_tx_ids(cg_pool* p, const uint8_t* ids, uint64_t n_ids, const cg_sign_req* reqs, uint64_t n,
+                        const cg_signable_tmpl* tmpls, uint32_t n_tmpls, const uint8_t* arena, uint64_t arena_len,
+                        uint8_t* sigs_out, uint8_t* status_out, cg_pool_stats* stats) {
+  const char* fn = "cg_pool_sign_tx_ids";
+  if (!p) return fail(CG_ERR_ARG, "%s: pool is NULL", fn);
+  if (p->ctx.empty()) return fail(CG_ERR_ARG, "%s: empty pool", fn);
+  const SignReq h = {reqs, n, true, ids, n_ids, tmpls, n_tmpls, arena, arena_len, sigs_out, status_out};
+  if (const int a = sign_args(fn, p->ctx[0], h, true)) return a;
+  if (n == 0) return CG_OK;
+  std::lock_guard<std::mutex> g(p->mu);  // one scope: the signer sets cannot change between the check and the call
+  bool any = false;
+  for (cg_ctx* c : p->ctx) {
+    std::lock_guard<std::mutex> gc(c->mu);
+    any = any || c->n_signers != 0;
+  }
+  // no signers anywhere: the caller's mistake, and nothing is written
+  if (!any) return fail(CG_ERR_ARG, "%s: no signers loaded (cg_pool_signers_load)", fn);
+  auto blank = [&]() {
+    memset(status_out, CG_NOT_RUN, n);
+    memset(sigs_out, 0, 64 * n);
+  };
+  blank();
+  uint8_t unit = CG_NOT_RUN;
+  const int rc = pool_call_locked(p, 1, &unit, stats, fn, [&](cg_ctx* c, uint64_t, uint64_t) {
+    // a slot whose load failed holds no set: it refuses the call as a slot without capacity does
+    // (pool.h: the call moves to the next live slot, the slot's health is untouched)
+    if (!c->fault && c->n_signers == 0) return fail(CG_ERR_NOMEM, "%s: this slot holds no signer set (its load failed)", fn);
+    const int r = sign_host_locked(fn, c, h);
+    if (r != CG_OK) blank();
+    return r;
+  });
+  if (stats) stats->not_run = rc == CG_OK ? 0 : n;
   return rc;
 }
 

@@ -442,14 +442,19 @@ CG_HD void ed_double_scalar_rows(ge_p2& out, const uint32_t eh[16], const uint32
   }
 }
 
-// encode (X:Y:Z) given zi = 1/Z, compare with R bytes
-CG_HD int ed_encode_cmp(const ge_p2& P, const fe& zi, const uint32_t rw[8]) {
+// encode (X:Y:Z) given zi = 1/Z (GroupElement.toByteArray: y with x's sign in bit 255)
+CG_HD void ed_encode(uint32_t enc[8], const ge_p2& P, const fe& zi) {
   fe x, y;
   fe_mul(x, P.X, zi);
   fe_mul(y, P.Y, zi);
-  uint32_t enc[8];
   fe_tobytes_words(enc, y);
   enc[7] |= (uint32_t)fe_isnegative(x) << 31;
+}
+
+// encode (X:Y:Z) given zi = 1/Z, compare with R bytes
+CG_HD int ed_encode_cmp(const ge_p2& P, const fe& zi, const uint32_t rw[8]) {
+  uint32_t enc[8];
+  ed_encode(enc, P, zi);
   uint32_t diff = 0;
   for (int i = 0; i < 8; ++i) diff |= enc[i] ^ rw[i];
   return diff == 0 ? ED_ST_VALID : ED_ST_INVALID;

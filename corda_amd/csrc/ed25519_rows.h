@@ -967,6 +967,65 @@ CG_HD void ed_add_b_wide9(ge_p2& q, const ge_p3& R, const uint32_t* esb, const E
   ge9_to_p2(q, R9);
 }
 
+// s B from the identity over the constant radix-2^ED_WIDE_BW table alone (the signer's r B and a B:
+// EdDSAEngine.engineSign, EdDSAPrivateKeySpec): esb = s's signed digits (sc_recode_wb, s < 2^253),
+// one entry per row by |digit|, the first through ge9_from_niels_half, no doublings; a zero digit adds
+// TB.ident. 10 / 11 / 12 rows at radix 2^26 / 2^24 / 2^22.
+CG_HD void ed_fixed_base9(ge_p2& out, const uint32_t* esb, const EdBWideTab& TB) {
+  ge9_p3 R;
+  for (int u = 0; u < EdWideCfg::kBDigits; ++u) {
+    const int dg = sc_digit_at<EdWideCfg::kBBits>(esb, u);
+    const int dp = dg < 0 ? -dg : dg;
+    const ge9_niels n = dp == 0 ? TB.ident : TB.t[u][dp - 1];
+    if (u == 0) ge9_from_niels_half(R, n, dg < 0);
+    else if (u + 1 < EdWideCfg::kBDigits) ge9_madd_half<true>(R, R, n, dg < 0);
+    else ge9_madd_half<false>(R, R, n, dg < 0);
+  }
+  ge9_to_p2(out, R);
+}
+
+// A signer as the context keeps it (EdDSAPrivateKeySpec(seed)): h = SHA-512(seed), a = h[0..32)
+// clamped (the raw scalar, not reduced: sc_muladd takes it so), prefix = h[32..64), abyte = the
+// encoding of a B. a and prefix are secret.
+struct EdSigner {
+  uint32_t a[8], prefix[8], abyte[8];
+};
+// a, prefix and the table digits of a mod L (a itself may reach 2^255, past the recoding's 2^253)
+CG_HD void ed_signer_scalars(EdSigner& sg, uint32_t* esb, const uint32_t seed[8]) {
+  uint64_t s[8], w[16];
+  sha512_init(s);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) w[j] = ((uint64_t)CG_BSWAP32(seed[2 * j]) << 32) | CG_BSWAP32(seed[2 * j + 1]);
+  w[4] = 0x8000000000000000ULL;
+#pragma unroll
+  for (int j = 5; j < 15; ++j) w[j] = 0;
+  w[15] = 256;
+  sha512_compress(s, w);
+  uint32_t h[16];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    h[2 * k] = CG_BSWAP32((uint32_t)(s[k] >> 32));
+    h[2 * k + 1] = CG_BSWAP32((uint32_t)s[k]);
+  }
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    sg.a[k] = h[k];
+    sg.prefix[k] = h[8 + k];
+  }
+  sg.a[0] &= 0xfffffff8u;
+  sg.a[7] = (sg.a[7] & 0x3fffffffu) | 0x40000000u;
+  uint32_t am[8];
+  sc_reduce256(am, sg.a);
+  sc_recode_wb<ED_WIDE_BW, EdWideCfg::kBBits>(esb, EdWideCfg::kBPackedWords, am);
+}
+CG_HD void ed_signer_expand(EdSigner& sg, const uint32_t seed[8], const EdBWideTab& TB) {
+  uint32_t esb[EdWideCfg::kBPackedWords];
+  ed_signer_scalars(sg, esb, seed);
+  ge_p2 A;
+  ed_fixed_base9(A, esb, TB);
+  ed_encode_affine(sg.abyte, A.X, A.Y, A.Z);
+}
+
 template <int W, int K, bool Signed = false, class RowA, class PickA, class PickB>
 CG_HD void ed_double_scalar_fw(ge_p2& out, const uint32_t* eh, const uint32_t* esb, const RowA& TA,
                                const EdBWideTab& TB, PickA pick_a, PickB pick_b) {

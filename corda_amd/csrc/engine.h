@@ -169,6 +169,28 @@ struct KeyUses {
   const uint32_t* host_counts = nullptr;
 };
 
+// One chunk of an Ed25519 sign call (sign_ed.hip): the chunk's requests (cg_sign_req over SignableData
+// splices when `fused`, else cg_sign_item over arena bytes), the context's signer store, and the chunk's
+// signature and status bytes. d_ws holds sign_ws_bytes(n) bytes; d_msgs / d_tmpls (fused only) are the
+// splice workspace launch_tx_sig_templates made and the template table it was made from.
+struct SignArgs {
+  const void* d_reqs;
+  uint64_t n;
+  bool fused;
+  const void* d_signers;
+  uint32_t n_signers;
+  const uint8_t* d_arena;
+  uint64_t arena_len;
+  const uint8_t* d_msgs;
+  const cg_signable_tmpl* d_tmpls;
+  uint32_t n_tmpls;
+  uint64_t n_ids;
+  uint8_t* d_sigs;
+  uint8_t* d_status;
+  void* d_ws;
+  const void* d_btab;
+};
+
 // One build of the radix-dependent kernels: the entry points cordagpu.cpp calls through a context's
 // variant (cg_config.table_bytes_max picks it at cg_open). Each build defines cg::variant() (renamed
 // cg24::variant() / cg22::variant() in the others).
@@ -192,6 +214,12 @@ struct EngineVariant {
   hipError_t (*launch_items_plan)(const ItemArgs& a, hipStream_t stream, const Fork& fork);
   hipError_t (*launch_items_front)(const ItemArgs& a, hipStream_t stream, const Fork& fork, bool planned);
   hipError_t (*launch_items_back)(const ItemArgs& a, hipStream_t stream, const Fork& fork);
+  // the Ed25519 signer (sign_ed.hip)
+  size_t (*signer_bytes)();
+  size_t (*sign_ws_bytes)(uint64_t n);
+  hipError_t (*launch_signer_expand)(const uint8_t* d_seeds, uint32_t n, void* d_signers, uint8_t* d_pubkeys,
+                                     const void* d_btab, hipStream_t stream);
+  hipError_t (*launch_sign)(const SignArgs& a, hipStream_t stream);
 };
 
 }  // namespace cgt
@@ -202,6 +230,7 @@ using cgt::EngineVariant;
 using cgt::Fork;
 using cgt::ItemArgs;
 using cgt::PendingTabs;
+using cgt::SignArgs;
 using cgt::SigTable;
 using cgt::StageTimer;
 using cgt::VerifyReq;
@@ -254,6 +283,16 @@ hipError_t launch_items(const ItemArgs& a, hipStream_t stream, const Fork& fork)
 hipError_t launch_items_plan(const ItemArgs& a, hipStream_t stream, const Fork& fork);
 hipError_t launch_items_front(const ItemArgs& a, hipStream_t stream, const Fork& fork, bool planned);
 hipError_t launch_items_back(const ItemArgs& a, hipStream_t stream, const Fork& fork);
+
+// The Ed25519 signer (sign_ed.hip; EdDSAEngine.engineSign behind Crypto.doSign). The signer store holds
+// signer_bytes() per signer (launch_signer_expand fills it from the 32-byte seeds and writes each key's
+// 32-byte Abyte to d_pubkeys); launch_sign signs one chunk over a workspace of sign_ws_bytes(n) bytes,
+// which holds secrets (every r and its table digits) until the caller zeroes it.
+size_t signer_bytes();
+size_t sign_ws_bytes(uint64_t n);
+hipError_t launch_signer_expand(const uint8_t* d_seeds, uint32_t n, void* d_signers, uint8_t* d_pubkeys,
+                                const void* d_btab, hipStream_t stream);
+hipError_t launch_sign(const SignArgs& a, hipStream_t stream);
 
 // RSA_SHA256 (verify_rsa.hip; radix-independent, used only by contexts opened with CG_FLAG_RSA).
 // Key records for a key table (launch_rsa_keyprep fills them: accepted keys get their Montgomery

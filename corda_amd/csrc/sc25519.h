@@ -133,6 +133,36 @@ CG_HD void sc_sub(uint32_t r[8], const uint32_t a[8], const uint32_t b[8]) {
   }
 }
 
+// S = (r + k a) mod L, the signer's scalar (i2p ScalarOps.multiplyAndAdd behind
+// EdDSAEngine.engineSign). k < L, r < L, a < 2^255: a is the raw clamped secret scalar, not reduced.
+// The 8 x 8-word product plus r is below 2^508 + 2^253, so it fits the 16 words sc_reduce512 takes.
+CG_HD void sc_muladd(uint32_t S[8], const uint32_t k[8], const uint32_t a[8], const uint32_t r[8]) {
+  uint32_t x[16];
+  uint64_t acc_lo = 0;  // column accumulator as 96-bit: (acc_hi:acc_lo)
+  uint32_t acc_hi = 0;
+#pragma unroll
+  for (int c = 0; c < 16; ++c) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const int j = c - i;
+      if (j < 0 || j > 7) continue;
+      const uint64_t p = (uint64_t)k[i] * a[j];
+      const uint64_t s = acc_lo + p;
+      acc_hi += (s < p);
+      acc_lo = s;
+    }
+    if (c < 8) {
+      const uint64_t s = acc_lo + r[c];
+      acc_hi += (s < (uint64_t)r[c]);
+      acc_lo = s;
+    }
+    x[c] = (uint32_t)acc_lo;
+    acc_lo = (acc_lo >> 32) | ((uint64_t)acc_hi << 32);
+    acc_hi = 0;
+  }
+  sc_reduce512(S, x);
+}
+
 // 2^256 mod L
 CG_HD uint32_t sc_R1w(int i) {
   const uint32_t R1[8] = {0x8d98951du, 0xd6ec3174u, 0x737dcf70u, 0xc6ef5bf4u,

@@ -322,27 +322,29 @@ struct SpliceLd {
   }
 };
 
-// SHA-512(prefix64 || msg) where prefix64 is 16 little-endian words (e.g. R || Abyte).
+// SHA-512(prefix || msg) where the prefix is PW little-endian words: 16 (R || Abyte, the verifier's
+// and the signer's challenge) or 8 (the signer's secret prefix h[32..64), EdDSAEngine.engineSign's r).
 // Output: the 64 digest bytes as 16 little-endian words (ready for sc_reduce512).
 // The message is read as aligned 16-byte chunks (33 dwords per 128-byte block) and realigned with
 // one funnel shift per word, instead of two dword loads per word (round 1: 136 loads per
 // 270-byte message, the challenge kernel's memory-wait share was ~0.3).
-template <class Ld>
-CG_HD void sha512_prefix64_ld(uint32_t out[16], const uint32_t prefix[16], const Ld& ld, uint64_t msg_off,
-                              uint64_t msg_len) {
+template <int PW, class Ld>
+CG_HD void sha512_prefix_ld(uint32_t out[16], const uint32_t prefix[PW], const Ld& ld, uint64_t msg_off,
+                            uint64_t msg_len) {
+  static_assert(PW == 8 || PW == 16, "a 32- or 64-byte prefix");
   uint64_t s[8];
   sha512_init(s);
-  const uint64_t n = 64 + msg_len;
+  const uint64_t n = 4 * PW + msg_len;
   const uint64_t nblocks = (n + 17 + 127) >> 7;
   const uint64_t base = msg_off & ~(uint64_t)3;
   const uint32_t sh8 = (uint32_t)(msg_off & 3) * 8u;
   for (uint64_t blk = 0; blk < nblocks; ++blk) {
-    // message words k0 .. k0 + 31 of this block (k0 = 32 blk - 16; block 0 starts with the prefix)
-    const int64_t k0 = (int64_t)blk * 32 - 16;
+    // message words k0 .. k0 + 31 of this block (k0 = 32 blk - PW; block 0 starts with the prefix)
+    const int64_t k0 = (int64_t)blk * 32 - PW;
     uint32_t W[36];  // aligned dwords k0 .. k0 + 35
 #pragma unroll
     for (int t = 0; t < 9; ++t) {
-      if (blk == 0 && t < 4) {
+      if (blk == 0 && t < PW / 4) {
         W[4 * t] = W[4 * t + 1] = W[4 * t + 2] = W[4 * t + 3] = 0u;
       } else {
         ld.dwords4(&W[4 * t], base + (uint64_t)(k0 + 4 * t) * 4);
@@ -391,29 +393,37 @@ CG_HD void sha512_prefix64_ld(uint32_t out[16], const uint32_t prefix[16], const
   }
 }
 
-// SHA-512(prefix64 || M) for M a SignableData splice (SpliceLd: base 0, zero past the message):
+template <class Ld>
+CG_HD void sha512_prefix64_ld(uint32_t out[16], const uint32_t prefix[16], const Ld& ld, uint64_t msg_off,
+                              uint64_t msg_len) {
+  sha512_prefix_ld<16>(out, prefix, ld, msg_off, msg_len);
+}
+
+// SHA-512(prefix || M) for M a SignableData splice (SpliceLd: base 0, zero past the message):
 // the padding byte is ORed into its word, so no word tests the length, and with wk1 != nullptr
 // (a wave-uniform TmplW512 record, the template's prefix covering M[64, 192)) block 1 runs from
-// its precomputed schedule (sha512_compress_wk).
-template <class Ld>
-CG_HD void sha512_prefix64_splice(uint32_t out[16], const uint32_t prefix[16], const Ld& ld, uint32_t msg_len,
-                                  const uint64_t* wk1) {
+// its precomputed schedule (sha512_compress_wk). The schedule belongs to the 64-byte prefix alone: the
+// 32-byte (secret) prefix puts other message bytes into block 1 and never takes it.
+template <int PW, class Ld>
+CG_HD void sha512_prefix_splice(uint32_t out[16], const uint32_t prefix[PW], const Ld& ld, uint32_t msg_len,
+                                const uint64_t* wk1) {
+  static_assert(PW == 8 || PW == 16, "a 32- or 64-byte prefix");
   uint64_t s[8];
   sha512_init(s);
-  const uint64_t n = 64ull + msg_len;
+  const uint64_t n = 4ull * PW + msg_len;
   const uint32_t nblocks = (uint32_t)((n + 17u + 127u) >> 7);
   const int mw = (int)(msg_len >> 2);
   const uint32_t mk = 0x80u << (8u * (msg_len & 3u));
   for (uint32_t blk = 0; blk < nblocks; ++blk) {
-    if (blk == 1 && wk1 != nullptr) {
+    if (PW == 16 && blk == 1 && wk1 != nullptr) {
       sha512_compress_wk(s, wk1);
       continue;
     }
-    const int k0 = (int)blk * 32 - 16;  // message word of the block's first word (block 0: prefix first)
+    const int k0 = (int)blk * 32 - PW;  // message word of the block's first word (block 0: prefix first)
     uint32_t W[32];
 #pragma unroll
     for (int q = 0; q < 8; ++q) {
-      if (blk == 0 && q < 4) {
+      if (blk == 0 && q < PW / 4) {
         W[4 * q] = W[4 * q + 1] = W[4 * q + 2] = W[4 * q + 3] = 0u;
       } else {
         ld.dwords4(&W[4 * q], (uint64_t)(k0 + 4 * q) * 4u);
@@ -423,7 +433,7 @@ CG_HD void sha512_prefix64_splice(uint32_t out[16], const uint32_t prefix[16], c
     uint32_t be[32];
 #pragma unroll
     for (int j = 0; j < 32; ++j) {
-      const uint32_t w = (blk == 0 && j < 16) ? prefix[j] : (W[j] | (j == km ? mk : 0u));
+      const uint32_t w = (blk == 0 && j < PW) ? prefix[j] : (W[j] | (j == km ? mk : 0u));
       be[j] = CG_BSWAP32(w);
     }
     if (blk + 1 == nblocks) {
@@ -442,6 +452,12 @@ CG_HD void sha512_prefix64_splice(uint32_t out[16], const uint32_t prefix[16], c
     out[2 * k] = CG_BSWAP32((uint32_t)(s[k] >> 32));
     out[2 * k + 1] = CG_BSWAP32((uint32_t)s[k]);
   }
+}
+
+template <class Ld>
+CG_HD void sha512_prefix64_splice(uint32_t out[16], const uint32_t prefix[16], const Ld& ld, uint32_t msg_len,
+                                  const uint64_t* wk1) {
+  sha512_prefix_splice<16>(out, prefix, ld, msg_len, wk1);
 }
 
 CG_HD void sha512_prefix64_msg(uint32_t out[16], const uint32_t prefix[16], const uint8_t* arena,

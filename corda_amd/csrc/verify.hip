@@ -626,7 +626,8 @@ const EngineVariant& variant() {
   static const EngineVariant v = {(uint32_t)ED_WIDE_BW, upload_constants, keyprep_bytes, wide_bytes, wide_slot_bytes,
                                   make_wide_pool, wide_slots, key_cache_bytes, btab_bytes, btab_scratch_bytes, init_btab, item_ws_bytes,
                                   launch_keyprep, launch_key_tables, launch_items, launch_items_plan,
-                                  launch_items_front, launch_items_back};
+                                  launch_items_front, launch_items_back,
+                                  signer_bytes, sign_ws_bytes, launch_signer_expand, launch_sign};
   return v;
 }
 

@@ -13,6 +13,7 @@
 //   k_ed_finish          16 items per lane: batch inversion, encode, byte compare
 // Replaces, per item, i2p EdDSAEngine.engineVerify behind Crypto.isValid
 // (core/src/main/kotlin/net/corda/core/crypto/Crypto.kt:553-559, scheme :120-133).
+#include "ed_lds.h"
 #include "keyws.h"
 
 namespace cg {
@@ -453,8 +454,6 @@ struct PickGlobal {
 // 2 x 4-B chunks, chunk c of lane l at wave_base + 64 * off_c + size_c * l (the DMA's
 // lane-linear destination), 7680 B per wave. Only the 16-B and 4-B DMA forms are used: a
 // first cut with 12-B chunks read back wrong entries.
-typedef __attribute__((address_space(3))) void* cg_lds_ptr;
-typedef __attribute__((address_space(1))) void* cg_gbl_ptr;
 
 struct EdOps {
   static constexpr int kNa1 = (EdCfg::kDigits - 1 + ED_K - 1) / ED_K;  // A rows, window 1
@@ -496,11 +495,6 @@ __device__ __forceinline__ int ed_op_digit(uint32_t w, int sh, bool is_b) {
   return EdWideCfg::kBBits == 16 ? (int)(int16_t)(uint16_t)(w >> sh) : (int)w;
 }
 
-// wave_lds_off: the wave's LDS image as a wave-uniform LDS byte offset (readfirstlane'd once
-// by the caller), so the per-chunk M0 values are scalar adds, not VALU readfirstlanes
-__device__ __forceinline__ cg_lds_ptr ed_lds_at(uint32_t wave_lds_off, uint32_t b) {
-  return (cg_lds_ptr)(uintptr_t)(wave_lds_off + b);
-}
 __device__ __forceinline__ void ed_glds_niels(const ge_niels* src, uint32_t wave_lds_off) {
   const uint8_t* s = (const uint8_t*)src;
 #pragma unroll
@@ -524,33 +518,11 @@ __device__ __forceinline__ void ed_lds_niels(ge_niels& n, const uint8_t* wave_ld
   d[29] = *(const uint32_t*)(wave_lds + 64 * 116 + 4 * lane);
 }
 
-// the radix-2^29 wide-table entries (fe9.h, 112 B): 7 x 16-B chunks, the same lane-linear image
-__device__ __forceinline__ void ed_glds_niels9(const ge9_niels* src, uint32_t wave_lds_off) {
-  const uint8_t* s = (const uint8_t*)src;
-#pragma unroll
-  for (int c = 0; c < 7; ++c)
-    __builtin_amdgcn_global_load_lds((cg_gbl_ptr)(s + 16 * c), ed_lds_at(wave_lds_off, 64 * 16 * c), 16, 0, 0);
-}
-__device__ __forceinline__ void ed_lds_niels9(ge9_niels& n, const uint8_t* wave_lds, uint32_t lane) {
-  uint32_t* d = (uint32_t*)&n;
-#pragma unroll
-  for (int c = 0; c < 7; ++c) {
-    const uint4 v = *(const uint4*)(wave_lds + 64 * 16 * c + 16 * lane);
-    d[4 * c] = v.x;
-    d[4 * c + 1] = v.y;
-    d[4 * c + 2] = v.z;
-    if (c < 6) d[4 * c + 3] = v.w;  // the pad dword stays unread
-  }
-}
 static_assert(64 * 7 * 16 <= EdOps::kWaveBytes, "the LDS image (7 chunks a lane) holds either entry form");
 
 __device__ __forceinline__ const ge_niels* ed_op_src(const EdTab& TA, int row, int d) {
   const int a = d < 0 ? -d : d;
   return &TA.t[row][a > 0 ? a - 1 : 0];
-}
-__device__ __forceinline__ const ge9_niels* ed_b_src(const EdBWideTab& TB, int row, int d) {
-  const int a = d < 0 ? -d : d;
-  return a > 0 ? &TB.t[row][a - 1] : &TB.ident;  // a zero digit adds the identity entry
 }
 
 // The 55 A additions in radix 2^25.5 (full-table entries), then the 12 B additions in radix 2^29

@@ -12,6 +12,7 @@ import numpy as np
 from . import _lib
 from .batch import COMPONENT_DTYPE, FLEAF_DTYPE, FTX_DTYPE, KEY_DTYPE, PMT_NODE_DTYPE, MODE_DOVERIFY, SPAN_DTYPE, TMPL_DTYPE, TX_DTYPE, TXSIG_DTYPE
 from .batch import REQ_NODE_DTYPE, TX_CHECK_DTYPE, TX_VERDICT_DTYPE, TXSIG12_DTYPE
+from .batch import SIGN_ITEM_DTYPE, SIGN_REQ_DTYPE
 
 
 def _p(a):
@@ -253,6 +254,50 @@ class Engine:
                                                        stream or None)
         _lib.check(rc, "cg_verify_tx_signatures_device")
 
+    # ------------------------------------------------------------------ Ed25519 signing
+    def load_signers(self, seeds):
+        """cg_signers_load: EdDSAPrivateKeySpec(seed) for each 32-byte seed; replaces the context's signer
+        set and returns each key's 32-byte Abyte, for the key-pair check of Crypto.kt:416-419. The
+        seeds (bytes-like objects) are copied once, into the array handed to the C ABI, and that array is
+        zeroed before this returns; the caller's objects are not touched."""
+        return _load_signers(_lib.lib().cg_signers_load, "cg_signers_load", self._h, seeds)
+
+    def clear_signers(self):
+        _lib.check(_lib.lib().cg_signers_clear(self._h), "cg_signers_clear")
+
+    def sign_tx_ids(self, sr):
+        """Batch Crypto.doSign(keyPair, SignableData(txId, metadata)) (cg_sign_tx_ids, Crypto.kt:415-422;
+        NotaryService.kt:77-80): ``sr`` is a batch.SignRequests. Returns (signatures uint8 [n, 64],
+        status uint8 [n]); a request that was not signed has 64 zero bytes."""
+        assert sr.reqs.dtype == SIGN_REQ_DTYPE and sr.tmpls.dtype == TMPL_DTYPE
+        sigs = np.zeros(64 * sr.n, dtype=np.uint8)
+        st = np.full(sr.n, 255, dtype=np.uint8)
+        rc = _lib.lib().cg_sign_tx_ids(self._h, _p(sr.ids), sr.n_ids, _p(sr.reqs), sr.n, _p(sr.tmpls), len(sr.tmpls),
+                                       _p(sr.arena), sr.arena.size, _p(sigs), _p(st))
+        _lib.check(rc, "cg_sign_tx_ids")
+        return sigs.reshape(-1, 64), st
+
+    def sign_tx_ids_device(self, d_ids, n_ids, d_reqs, n, tmpls, d_arena, arena_len, d_sigs, d_status, stream=0):
+        """Asynchronous device form; `tmpls` is a host TMPL_DTYPE array (template bytes in the arena)."""
+        assert tmpls.dtype == TMPL_DTYPE
+        rc = _lib.lib().cg_sign_tx_ids_device(self._h, d_ids, n_ids, d_reqs, n, _p(tmpls), len(tmpls), d_arena,
+                                              arena_len, d_sigs, d_status, stream or None)
+        _lib.check(rc, "cg_sign_tx_ids_device")
+
+    def sign(self, signer_msgs):
+        """Batch Crypto.doSign(privateKey, clearData) (cg_sign_batch, Crypto.kt:395-402) over
+        (signer index, message bytes) pairs. Returns (signatures uint8 [n, 64], status uint8 [n])."""
+        n = len(signer_msgs)
+        spans, arena = self._spans([m for _, m in signer_msgs])
+        items = np.zeros(n, dtype=SIGN_ITEM_DTYPE)
+        items["msg_off"], items["msg_len"] = spans["off"], spans["len"]
+        items["signer"] = [s for s, _ in signer_msgs]
+        sigs = np.zeros(64 * n, dtype=np.uint8)
+        st = np.full(n, 255, dtype=np.uint8)
+        rc = _lib.lib().cg_sign_batch(self._h, _p(items), n, _p(arena), arena.size - 8, _p(sigs), _p(st))
+        _lib.check(rc, "cg_sign_batch")
+        return sigs.reshape(-1, 64), st
+
     # ------------------------------------------------------------------ per-transaction verdicts
     def tx_verdicts(self, sig_table, status, keys, checks, reqs, nodes, key_class=None):
         """cg_tx_verdicts: verifySignaturesExcept's two steps reduced on the device from one status byte
@@ -298,6 +343,25 @@ class Engine:
             d_arena, arena_len, mode, d_key_class or None, d_checks, n_tx, d_reqs or None, n_reqs, d_nodes or None,
             n_nodes, d_status, d_verdicts, d_req_status or None, stream or None)
         _lib.check(rc, "cg_verify_required_signatures_packed_device")
+
+
+def _load_signers(fn, what, h, seeds):
+    # each seed goes straight from the caller's object into the one array the C ABI reads: no joined or
+    # converted intermediate holds the seeds. That array is zeroed below; the caller's own objects are its own.
+    seeds = list(seeds)
+    views = [np.frombuffer(s, dtype=np.uint8) for s in seeds]
+    if not views or any(v.size != 32 for v in views):
+        raise ValueError("an Ed25519 private key is a 32-byte seed; at least one is needed")
+    buf = np.zeros(32 * len(seeds), dtype=np.uint8)
+    for i, v in enumerate(views):
+        buf[32 * i:32 * i + 32] = v
+    pub = np.zeros(32 * len(seeds), dtype=np.uint8)
+    try:
+        rc = fn(h, _p(buf), len(seeds), _p(pub))
+    finally:
+        ctypes.memset(buf.ctypes.data, 0, buf.size)  # the staging copy (the caller's bytes are its own)
+    _lib.check(rc, what)
+    return [pub[32 * i:32 * i + 32].tobytes() for i in range(len(seeds))]
 
 
 def _check_tables(checks, reqs, nodes, key_class, n_keys):
@@ -425,6 +489,28 @@ class EnginePool:
         if rc != 0 and not allow_partial:
             _lib.check(rc, "cg_pool_verify_transactions")
         return ids.reshape(-1, 32), txst, sst
+
+    def load_signers(self, seeds):
+        """cg_pool_signers_load: the signer set on every slot; returns each key's Abyte."""
+        return _load_signers(_lib.lib().cg_pool_signers_load, "cg_pool_signers_load", self._h, seeds)
+
+    def clear_signers(self):
+        _lib.check(_lib.lib().cg_pool_signers_clear(self._h), "cg_pool_signers_clear")
+
+    def sign_tx_ids(self, sr, allow_partial=False):
+        """cg_pool_sign_tx_ids: the whole call on one healthy slot, the next one on a device fault.
+        Returns (signatures uint8 [n, 64], status uint8 [n]) as Engine.sign_tx_ids."""
+        assert sr.reqs.dtype == SIGN_REQ_DTYPE and sr.tmpls.dtype == TMPL_DTYPE
+        sigs = np.zeros(64 * sr.n, dtype=np.uint8)
+        st = np.full(sr.n, 255, dtype=np.uint8)
+        stats = _lib.cg_pool_stats()
+        rc = _lib.lib().cg_pool_sign_tx_ids(self._h, _p(sr.ids), sr.n_ids, _p(sr.reqs), sr.n, _p(sr.tmpls),
+                                            len(sr.tmpls), _p(sr.arena), sr.arena.size, _p(sigs), _p(st),
+                                            ctypes.byref(stats))
+        self.last_stats = {k: getattr(stats, k) for k, _ in _lib.cg_pool_stats._fields_ if k != "reserved"}
+        if rc != 0 and not allow_partial:
+            _lib.check(rc, "cg_pool_sign_tx_ids")
+        return sigs.reshape(-1, 64), st
 
     def verify_requeue(self, batch, mode=MODE_DOVERIFY, between=None):
         """The JVM binding's re-queue (CryptoBatch.kt verifyBatch): on CG_ERR_DEVICE only the items left

@@ -626,6 +626,59 @@ int cg_verify_filtered_device(cg_ctx* ctx, const cg_filtered_tx* d_ftxs, uint64_
                               uint64_t n_nodes, const cg_filtered_leaf* d_leaves, uint64_t n_leaves,
                               const uint8_t* d_arena, uint64_t arena_len, uint8_t* d_status, void* hip_stream);
 
+/* ---- Ed25519 signing: the batch form of Crypto.doSign for EDDSA_ED25519_SHA512, the notary's own
+ * step after it has checked a transaction's signatures:
+ *   NotaryService.sign(txId)   core/.../node/services/NotaryService.kt:77-80
+ *     = keyManagementService.sign(SignableData(txId, SignatureMetadata(platformVersion, schemeNumberID)), key)
+ *     -> Crypto.doSign(keyPair, signableData)            core/.../crypto/Crypto.kt:415-422
+ *     -> Crypto.doSign(privateKey, clearData)            Crypto.kt:395-402
+ *     -> i2p 0.2.0 EdDSAEngine.engineSign: RFC 8032's deterministic signature
+ *          r = SHA-512(h[32..64) || M) mod L, R = r B, S = (r + SHA-512(R || A || M) a) mod L
+ *   (the BFT notary signs the same way, BFTSMaRt.kt:249-255). The output is byte for byte what the JVM
+ *   writes. ECDSA and RSA signing stay on the host: BC draws k and the PSS salt from SecureRandom.
+ * A context holds a signer set: private keys the node keeps in its own process
+ * (PersistentKeyManagementService.kt:84-95), loaded once and named by index in every request. The seeds,
+ * the expanded keys and every nonce r are secret: the signer store is a device allocation of its own,
+ * zeroed before it is freed (cg_signers_clear, a reload, cg_close); a sign call zeroes the nonces and
+ * their table digits on the stream before it returns. The fixed-base table is read at addresses that
+ * depend on r, so the access pattern is not constant-time: this signer is for keys the node already holds
+ * in memory, not a stand-in for an HSM.
+ * Statuses: 0 signature written; CG_EMPTY msg_len == 0 (Crypto.kt:398 "Signing of an empty array is not
+ * permitted!"); CG_NOT_RUN a signer, id or template index out of range, or bytes outside the arena. An
+ * item that is not signed gets 64 zero bytes. With no signers loaded a sign call is CG_ERR_ARG and
+ * writes nothing; n == 0 is a no-op. */
+#define CG_SIGNERS_MAX 65535
+/* EdDSAPrivateKeySpec(seed): replaces the context's signer set with the n keys of `seeds` (32 * n bytes).
+ * pubkeys_out (32 * n bytes) receives each key's Abyte, which the caller compares with keyPair.public
+ * (Crypto.kt:416-419 refuses a key pair whose halves do not belong together). */
+int cg_signers_load(cg_ctx* ctx, const uint8_t* seeds, uint32_t n, uint8_t* pubkeys_out); /* no host copy is kept */
+/* Zeroes and frees the signer set (a no-op when none is loaded). */
+int cg_signers_clear(cg_ctx* ctx);
+typedef struct cg_sign_req {
+  uint32_t tx_idx;  /* the id to sign, index into ids */
+  uint16_t signer;  /* index into the loaded signer set */
+  uint16_t tmpl;    /* SignatureMetadata template index */
+} cg_sign_req;      /* 8 bytes */
+/* Crypto.doSign(keyPair, SignableData(ids[tx_idx], tmpl)) (Crypto.kt:415-422; NotaryService.kt:77-80) for
+ * every request: the clear data is the template's prefix || id || suffix, spliced on the device as in
+ * cg_verify_tx_signatures. sigs_out: 64 * n bytes (R || S), status_out: n bytes. */
+int cg_sign_tx_ids(cg_ctx* ctx, const uint8_t* ids, uint64_t n_ids, const cg_sign_req* reqs, uint64_t n,
+                   const cg_signable_tmpl* tmpls, uint32_t n_tmpls, const uint8_t* arena, uint64_t arena_len,
+                   uint8_t* sigs_out, uint8_t* status_out);
+/* Device buffers in HBM except `tmpls` (a small host array); asynchronous on hip_stream. d_ids, d_reqs,
+ * d_arena and d_sigs must be 4-byte aligned. */
+int cg_sign_tx_ids_device(cg_ctx* ctx, const uint8_t* d_ids, uint64_t n_ids, const cg_sign_req* d_reqs, uint64_t n,
+                          const cg_signable_tmpl* tmpls, uint32_t n_tmpls, const uint8_t* d_arena,
+                          uint64_t arena_len, uint8_t* d_sigs, uint8_t* d_status, void* hip_stream);
+typedef struct cg_sign_item {
+  uint64_t msg_off;  /* clear data at arena[msg_off .. +msg_len) */
+  uint32_t msg_len;
+  uint32_t signer;   /* index into the loaded signer set */
+} cg_sign_item;      /* 16 bytes */
+/* Crypto.doSign(privateKey, clearData) (Crypto.kt:395-402; NotaryService.kt:73-75) over arena bytes. */
+int cg_sign_batch(cg_ctx* ctx, const cg_sign_item* items, uint64_t n, const uint8_t* arena, uint64_t arena_len,
+                  uint8_t* sigs_out, uint8_t* status_out);
+
 /* ---- Several devices in one process (the JVM process drives every GPU of the node).
  * A pool holds one cg_ctx per slot (a slot is a device ordinal; a device may appear twice).
  * cg_pool_verify_batch cuts the items into contiguous, equal shards, one per healthy slot, runs
@@ -687,6 +740,18 @@ int cg_pool_verify_required_signatures_packed(cg_pool* pool, const cg_key* keys,
                                               uint32_t n_reqs, const cg_req_node* nodes, uint32_t n_nodes,
                                               uint8_t* status_out, cg_tx_verdict* verdicts_out,
                                               uint8_t* req_status_out, cg_pool_stats* stats_opt);
+/* The signer set on every slot (cg_signers_load per slot; pubkeys_out from the first). A slot whose
+ * device fails is marked unhealthy; the call fails only when no slot could load the set. A slot that
+ * stayed healthy but could not load the set is passed over by cg_pool_sign_tx_ids. The library keeps no
+ * host copy of the seeds: they are copied from the caller's buffer to each device. */
+int cg_pool_signers_load(cg_pool* pool, const uint8_t* seeds, uint32_t n, uint8_t* pubkeys_out);
+int cg_pool_signers_clear(cg_pool* pool);
+/* cg_sign_tx_ids on a pool: not sharded, the whole call runs on the first healthy slot and, if that
+ * slot's device fails, on the next one (the cg_pool_verify_transactions pattern). When no slot could run
+ * it the status bytes are CG_NOT_RUN, the signatures zero, and the call returns CG_ERR_DEVICE. */
+int cg_pool_sign_tx_ids(cg_pool* pool, const uint8_t* ids, uint64_t n_ids, const cg_sign_req* reqs, uint64_t n,
+                        const cg_signable_tmpl* tmpls, uint32_t n_tmpls, const uint8_t* arena, uint64_t arena_len,
+                        uint8_t* sigs_out, uint8_t* status_out, cg_pool_stats* stats_opt);
 /* Failure drill: make every later call on `slot` fail as a device fault would (fail = 1), or
  * clear it and mark the slot healthy again (fail = 0). For tests and operational drills. */
 int cg_pool_inject_fault(cg_pool* pool, uint32_t slot, int fail);

@@ -156,6 +156,35 @@ JNIEXPORT jint JNICALL Java_net_corda_core_crypto_CryptoBatch_nativeVerifyTransa
                                 (uint8_t*)ADDR(tx_status_out), (uint8_t*)ADDR(sig_status_out));
 }
 
+/* EdDSAPrivateKeySpec(seed) for every 32-byte seed: the signer set of the context (cg_signers_load), or of
+ * every device of the pool (cg_pool_signers_load). pubkeys_out: each key's Abyte, which the binding
+ * compares with keyPair.public (Crypto.kt:416-419). The binding zeroes its seed buffer afterwards. */
+JNIEXPORT jint JNICALL Java_net_corda_core_crypto_CryptoBatch_nativeLoadSigners(JNIEnv* env, jobject self, jlong ctx,
+                                                                              jlong pool, jobject seeds, jint n,
+                                                                              jobject pubkeys_out) {
+  if (pool)
+    return cg_pool_signers_load((cg_pool*)(intptr_t)pool, (const uint8_t*)ADDR(seeds), (uint32_t)n,
+                                (uint8_t*)ADDR(pubkeys_out));
+  return cg_signers_load((cg_ctx*)(intptr_t)ctx, (const uint8_t*)ADDR(seeds), (uint32_t)n, (uint8_t*)ADDR(pubkeys_out));
+}
+
+/* Crypto.doSign(keyPair, SignableData(id, metadata)) over many ids (NotaryService.sign, NotaryService.kt:77-80):
+ * cg_sign_tx_ids (pool != 0: cg_pool_sign_tx_ids, the whole call on one healthy device, the next one on a
+ * device fault). sigs_out: 64 bytes per request, status_out: one byte per request. */
+JNIEXPORT jint JNICALL Java_net_corda_core_crypto_CryptoBatch_nativeSignTxIds(
+    JNIEnv* env, jobject self, jlong ctx, jlong pool, jobject ids, jlong n_ids, jobject reqs, jlong n, jobject tmpls,
+    jint n_tmpls, jobject arena, jlong arena_len, jobject sigs_out, jobject status_out) {
+  if (pool)
+    return cg_pool_sign_tx_ids((cg_pool*)(intptr_t)pool, (const uint8_t*)ADDR(ids), (uint64_t)n_ids,
+                               (const cg_sign_req*)ADDR(reqs), (uint64_t)n, (const cg_signable_tmpl*)ADDR(tmpls),
+                               (uint32_t)n_tmpls, (const uint8_t*)ADDR(arena), (uint64_t)arena_len,
+                               (uint8_t*)ADDR(sigs_out), (uint8_t*)ADDR(status_out), 0);
+  return cg_sign_tx_ids((cg_ctx*)(intptr_t)ctx, (const uint8_t*)ADDR(ids), (uint64_t)n_ids,
+                        (const cg_sign_req*)ADDR(reqs), (uint64_t)n, (const cg_signable_tmpl*)ADDR(tmpls),
+                        (uint32_t)n_tmpls, (const uint8_t*)ADDR(arena), (uint64_t)arena_len, (uint8_t*)ADDR(sigs_out),
+                        (uint8_t*)ADDR(status_out));
+}
+
 /* A direct buffer the node keeps across calls: pinned once (cg_host_register), so its bytes reach
  * every device by DMA without the runtime's CPU staging copy. */
 JNIEXPORT jint JNICALL Java_net_corda_core_crypto_CryptoBatch_nativeHostRegister(JNIEnv* env, jobject self,

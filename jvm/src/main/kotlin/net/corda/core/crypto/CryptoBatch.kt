@@ -11,15 +11,20 @@ import com.typesafe.config.Config
 import net.corda.core.crypto.composite.CompositeKey
 import net.corda.core.serialization.serialize
 import net.corda.core.transactions.SignedTransaction
+import net.i2p.crypto.eddsa.EdDSAPrivateKey
+import net.i2p.crypto.eddsa.EdDSAPublicKey
 import java.nio.ByteBuffer
 import java.nio.ByteOrder
 import java.security.InvalidKeyException
+import java.security.KeyPair
 import java.security.PublicKey
 import java.security.SignatureException
 import java.util.concurrent.TimeUnit
 import java.util.concurrent.atomic.AtomicInteger
+import java.util.concurrent.locks.ReentrantLock
 import java.util.concurrent.locks.ReentrantReadWriteLock
 import kotlin.concurrent.read
+import kotlin.concurrent.withLock
 import kotlin.concurrent.write
 
 data class BatchItem(val publicKey: PublicKey, val signatureData: ByteArray, val clearData: ByteArray)
@@ -101,6 +106,14 @@ object CryptoBatch {
                                                     keyClass: ByteBuffer, checks: ByteBuffer, nTx: Long,
                                                     reqs: ByteBuffer, nReqs: Int, nodes: ByteBuffer, nNodes: Int,
                                                     status: ByteBuffer?, verdicts: ByteBuffer, reqStatus: ByteBuffer): Int
+    /** cg_(pool_)signers_load: EdDSAPrivateKeySpec(seed) per 32-byte seed, the context's (every pool
+     *  device's) signer set; pubkeysOut receives each key's Abyte. */
+    private external fun nativeLoadSigners(ctx: Long, pool: Long, seeds: ByteBuffer, n: Int, pubkeysOut: ByteBuffer): Int
+    /** cg_(pool_)sign_tx_ids: Crypto.doSign(keyPair, SignableData(id, metadata)) per 8-byte request
+     *  (cg_sign_req: tx_idx, signer, tmpl); 64 signature bytes and one status byte per request. */
+    private external fun nativeSignTxIds(ctx: Long, pool: Long, ids: ByteBuffer, nIds: Long, reqs: ByteBuffer, n: Long,
+                                         tmpls: ByteBuffer, nTmpls: Int, arena: ByteBuffer, arenaLen: Long,
+                                         sigsOut: ByteBuffer, statusOut: ByteBuffer): Int
     private external fun nativeHostRegister(buf: ByteBuffer, len: Long): Int
     private external fun nativeHostUnregister(buf: ByteBuffer): Int
 
@@ -188,9 +201,10 @@ object CryptoBatch {
      *  returned (write lock). A later call opens a new one. */
     fun close() {
         rw.write {
-            if (ctx != 0L || pool != 0L) nativeClose(ctx, pool)
+            if (ctx != 0L || pool != 0L) nativeClose(ctx, pool)   // cg_close zeroes the signer store
             ctx = 0
             pool = 0
+            signerLock.withLock { signerHandle = 0 }
         }
     }
 
@@ -415,6 +429,116 @@ object CryptoBatch {
                       else null)
         record(stats, st)
         return st
+    }
+
+    // ---- Ed25519 signing (include/cordagpu.h, "Ed25519 signing"). The signer set lives in the open context
+    // (every device of the pool); signerHandle is the handle it was loaded into, so a context opened
+    // after close() gets the set again before its first sign call.
+    private const val CG_SIGNERS_MAX = 65535
+    private val signerLock = ReentrantLock()
+    private var signerKeys: List<KeyPair> = emptyList()
+    private var signerHandle = 0L
+
+    private fun isEd25519(k: KeyPair) = Crypto.findSignatureScheme(k.private) == Crypto.EDDSA_ED25519_SHA512 &&
+        Crypto.findSignatureScheme(k.public) == Crypto.EDDSA_ED25519_SHA512
+
+    /** The public half is the private half's A: checked on the JVM before a pair joins the signer set, so a
+     *  pair that does not belong together never reaches it (ensureSigners checks the device's Abyte too). */
+    private fun requireAligned(k: KeyPair) =
+        require((k.private as EdDSAPrivateKey).abyte.contentEquals((k.public as EdDSAPublicKey).abyte)) {
+            "the public key of this pair is not the private key's"
+        }
+
+    /** The notary's (node's) own Ed25519 key pairs, the keys PersistentKeyManagementService holds in this
+     *  process (PersistentKeyManagementService.kt:84-95), as the engine's signer set: loaded into the
+     *  device at the next signAll. Key pairs of other schemes are not accepted here; signAll signs with
+     *  them on the JVM. */
+    fun loadSigners(keyPairs: List<KeyPair>) {
+        require(keyPairs.size in 1..CG_SIGNERS_MAX) { "1..$CG_SIGNERS_MAX signers" }
+        require(keyPairs.all { isEd25519(it) }) { "the GPU signer takes EDDSA_ED25519_SHA512 key pairs only" }
+        keyPairs.forEach { requireAligned(it) }
+        signerLock.withLock {
+            signerKeys = keyPairs.toList()
+            signerHandle = 0
+        }
+    }
+
+    /** With signerLock held, inside withHandles: the set is in the open context. The device returns each
+     *  key's Abyte, and a pair whose public half is another key's is refused here, the way
+     *  Crypto.doSign(keyPair, signableData) refuses a misaligned pair (Crypto.kt:416-419). The seed
+     *  buffer is zeroed before it is released. */
+    private fun ensureSigners(c: Long, p: Long): Boolean {
+        val h = if (c != 0L) c else p
+        if (signerHandle == h) return true
+        val n = signerKeys.size
+        val seeds = direct(32 * n)
+        val pubs = direct(32 * n)
+        val rc = try {
+            signerKeys.forEach { seeds.put((it.private as EdDSAPrivateKey).seed) }
+            nativeLoadSigners(c, p, seeds, n, pubs)
+        } finally {
+            for (i in 0 until seeds.capacity()) seeds.put(i, 0)
+        }
+        if (rc != CG_OK) return false
+        val bad = signerKeys.indices.filter { i ->
+            val abyte = ByteArray(32).also { pubs.position(32 * i); pubs.get(it) }
+            !abyte.contentEquals((signerKeys[i].public as EdDSAPublicKey).abyte)
+        }
+        if (bad.isNotEmpty()) {
+            // the offending pairs leave the set, and the next sign call loads what remains (signerHandle
+            // stays 0), so one bad pair fails its own call and no later one
+            signerKeys = signerKeys.filterIndexed { i, _ -> i !in bad }
+            signerHandle = 0
+            throw IllegalArgumentException("signer ${bad.first()}: the public key is not the private key's")
+        }
+        signerHandle = h
+        return true
+    }
+
+    /** NotaryService.sign(txId) (NotaryService.kt:77-80; BFTSMaRt.kt:249-255) for many ids in one call:
+     *  Crypto.doSign(keyPair, SignableData(id, signatureMetadata)) each (Crypto.kt:415-422), byte for
+     *  byte what i2p's EdDSAEngine writes. A key pair that is not EDDSA_ED25519_SHA512 (BC draws ECDSA's k
+     *  and the PSS salt at random: nothing to reproduce), fewer ids than minBatch, a device fault, or
+     *  any non-zero status falls back to Crypto.doSign on the JVM for those ids, which also raises the
+     *  reference's own exceptions. */
+    fun signAll(keyPair: KeyPair, txIds: List<SecureHash>, signatureMetadata: SignatureMetadata): List<TransactionSignature> {
+        fun onJvm(id: SecureHash) = Crypto.doSign(keyPair, SignableData(id, signatureMetadata))
+        if (txIds.isEmpty()) return emptyList()
+        if (!isEd25519(keyPair) || txIds.size < config.minBatch) return txIds.map(::onJvm)
+        requireAligned(keyPair)
+        val (pre, suf) = signableTemplate(signatureMetadata)
+        val arena = direct(pre.size + suf.size + 16)
+        val tmpls = direct(24)
+        arena.align4(); val po = arena.position().toLong(); arena.put(pre)
+        arena.align4(); val so = arena.position().toLong(); arena.put(suf)
+        tmpls.putLong(po).putLong(so).putInt(pre.size).putInt(suf.size)
+        val n = txIds.size
+        val ids = direct(32 * n)
+        txIds.forEach { ids.put(it.bytes) }
+        val reqs = direct(8 * n)
+        val sigs = direct(64 * n)
+        val status = direct(n)
+        val rc = withHandles { c, p ->
+            signerLock.withLock {
+                var signer = signerKeys.indexOfFirst { it.public == keyPair.public && it.private == keyPair.private }
+                if (signer < 0 && signerKeys.size < CG_SIGNERS_MAX) {   // a key not announced with loadSigners joins the set
+                    signerKeys = signerKeys + keyPair
+                    signerHandle = 0
+                    signer = signerKeys.size - 1
+                }
+                if (signer < 0 || !ensureSigners(c, p)) CG_ERR_DEVICE
+                else {
+                    for (j in 0 until n) reqs.putInt(8 * j, j).putShort(8 * j + 4, signer.toShort()).putShort(8 * j + 6, 0)
+                    nativeSignTxIds(c, p, ids, n.toLong(), reqs, n.toLong(), tmpls, 1, arena, arena.position().toLong(),
+                                    sigs, status)
+                }
+            }
+        }
+        return txIds.mapIndexed { j, id ->
+            if (rc == CG_OK && status.get(j).toInt() == 0)
+                TransactionSignature(ByteArray(64).also { sigs.position(64 * j); sigs.get(it) }, keyPair.public, signatureMetadata)
+            else onJvm(id)
+        }
     }
 
     /** cg_verify_batch over tables already in the C ABI's layout (the out-of-process verifier's batch
