@@ -36,51 +36,17 @@ typedef int64_t ec9_acc;
 // signed 32 x 32 -> 64 term (v_mad_i64_i32 when accumulated)
 CG_HD ec9_acc ec9_t(uint32_t a, uint32_t b) { return (ec9_acc)((int64_t)(int32_t)a * (int64_t)(int32_t)b); }
 
-// opaque copies (round 5: every product pinned copies of its operands, because in a ladder loop the
-// compiler had widened loop-carried limb differences to 64 bits, as fe9.h saw). Round 6: the copies
-// cost a v_mov per limb whenever the operand stayed live (~110 per addition) and hid a square's
-// symmetry from the compiler; the products read their operands directly (EC9_PIN_COPIES restores the
-// copies for A/B: 329.9 vs 334.8 M sigs/s over 3 pairs, profiles/r06/ec_acc) and the ISA shows no
-// 64 x 64 multiply (tools/microbench/ec9_probe.hip)
-CG_HD void ec9_pin(f29& o, const f29& a) {
-#pragma unroll
-  for (int i = 0; i < 9; ++i) {
-    o.v[i] = a.v[i];
-#if defined(__HIP_DEVICE_COMPILE__)
-    asm volatile("" : "+v"(o.v[i]));
-#endif
-  }
-}
-
-// EC9_PIN_ACC (round 6, default 1): the running column sum made opaque after each term, so a
-// column's chain starts from the carry instead of being summed from 0 and joined by a separate 64-bit
-// add (fe9.h's FE9_PIN_ACC, adopted for the Ed25519 ladder in round 4); secp256k1's low columns then
-// run after the high ones as one chain with the fold terms first. Per addition 1790 -> 1661 (r1) /
-// 1786 -> 1657 (k1) static VALU (tools/microbench/ec9_probe.hip), ~1000 hazard s_nop 0 the other
-// waves fill; headline A/B over 3 pairs 334.8 -> 341.7 M sigs/s, r1 ladder 7.44 -> 7.14, k1 3.38 ->
-// 3.12 ms per step (profiles/r06/ec_acc). 0: the independent column sums (A/B).
-#ifndef EC9_PIN_ACC
-#define EC9_PIN_ACC 1
-#endif
-#ifndef EC9_SIGN_MUL
-#define EC9_SIGN_MUL 1
-#endif
-// EC9_SQR=1: squares as 45 MACs against a doubled copy (ec9_col); 0: as general products (A/B)
-#ifndef EC9_SQR
-#define EC9_SQR 1
-#endif
+// The running column sum is made opaque after each term, so a column's chain starts from the carry
+// instead of being summed from 0 and joined by a separate 64-bit add (as fe9.h's fe9_mul);
+// secp256k1's low columns then run after the high ones as one chain with the fold terms first.
 CG_HD void ec9_opaque(ec9_acc& x) {
 #if defined(__HIP_DEVICE_COMPILE__)
-  if (EC9_PIN_ACC) asm volatile("" : "+v"(x));
+  asm volatile("" : "+v"(x));
 #else
   (void)x;
 #endif
 }
 
-CG_HD void ec9_add(f29& r, const f29& a, const f29& b) {
-#pragma unroll
-  for (int i = 0; i < 9; ++i) r.v[i] = a.v[i] + b.v[i];
-}
 CG_HD void ec9_sub(f29& r, const f29& a, const f29& b) {
 #pragma unroll
   for (int i = 0; i < 9; ++i) r.v[i] = a.v[i] - b.v[i];
@@ -111,20 +77,9 @@ CG_HD void ec9_col(ec9_acc& acc, int k, const f29& a, const f29& b, const f29& c
 
 // ---------------------------------------------------------------- secp256r1: Montgomery
 template <bool Two, bool Add, bool Sq = false>
-CG_HD void ec9_mul_r1(f29& out, const f29& a0, const f29& b0, const f29& c0, const f29& d0, const f29& e) {
+CG_HD void ec9_mul_r1(f29& out, const f29& a, const f29& b, const f29& c, const f29& d, const f29& e) {
   constexpr uint32_t P7 = m29_limb(1, 0, 1, 7), P8 = m29_limb(1, 0, 1, 8);
   const uint32_t k9 = m29_opaque(1u << 9), k18 = m29_opaque(1u << 18);  // MACs, not shift pairs
-#ifdef EC9_PIN_COPIES
-  f29 a, b, c, d;
-  ec9_pin(a, a0);
-  ec9_pin(b, b0);
-  if (Two) {
-    ec9_pin(c, c0);
-    ec9_pin(d, d0);
-  }
-#else
-  const f29 &a = a0, &b = b0, &c = c0, &d = d0;
-#endif
   uint32_t q[9];
   ec9_acc acc = 0;
 #pragma unroll
@@ -153,28 +108,8 @@ CG_HD void ec9_mul_r1(f29& out, const f29& a0, const f29& b0, const f29& c0, con
 
 // ---------------------------------------------------------------- secp256k1: plain form, folded
 template <bool Two, bool Add, bool Sq = false>
-CG_HD void ec9_mul_k1(f29& out, const f29& a0, const f29& b0, const f29& c0, const f29& d0, const f29& e) {
+CG_HD void ec9_mul_k1(f29& out, const f29& a, const f29& b, const f29& c, const f29& d, const f29& e) {
   const uint32_t k31264 = m29_opaque(31264u), k256 = m29_opaque(256u);
-#ifdef EC9_PIN_COPIES
-  f29 a, b, c, d;
-  ec9_pin(a, a0);
-  ec9_pin(b, b0);
-  if (Two) {
-    ec9_pin(c, c0);
-    ec9_pin(d, d0);
-  }
-#else
-  const f29 &a = a0, &b = b0, &c = c0, &d = d0;
-#endif
-#if !EC9_PIN_ACC
-  ec9_acc col[9];
-#pragma unroll
-  for (int k = 0; k < 9; ++k) {
-    ec9_acc s = Add ? (ec9_acc)(int32_t)e.v[k] : 0;
-    ec9_col<Two, Sq>(s, k, a, b, c, d);
-    col[k] = s;
-  }
-#endif
   uint32_t H[8];
   ec9_acc acc = 0;
 #pragma unroll
@@ -188,7 +123,6 @@ CG_HD void ec9_mul_k1(f29& out, const f29& a0, const f29& b0, const f29& c0, con
   const uint32_t H8 = (uint32_t)(int32_t)acc;
   // H_m 2^{29 m} 2^261 = H_m 31264 (column m) + H_m 2^8 (column m + 1)
   uint32_t M[9];
-#if EC9_PIN_ACC
   // the low columns after the high ones: one chain from the carry, the fold terms and e first
   acc = 0;
 #pragma unroll
@@ -205,22 +139,6 @@ CG_HD void ec9_mul_k1(f29& out, const f29& a0, const f29& b0, const f29& c0, con
     M[j] = (uint32_t)acc & M29_MASK;
     acc >>= 29;
   }
-#else
-#pragma unroll
-  for (int m = 0; m < 8; ++m) {
-    col[m] += ec9_t(H[m], k31264);
-    col[m + 1] += ec9_t(H[m], k256);
-  }
-  col[8] += ec9_t(H8, k31264);
-  acc = 0;
-#pragma unroll
-  for (int j = 0; j < 9; ++j) {
-    acc += col[j];
-    EC9_CHK(acc);
-    M[j] = (uint32_t)acc & M29_MASK;
-    acc >>= 29;
-  }
-#endif
   // top (weight 2^261) = acc + H8 2^8, folded as (2^37 + 31264) at its 32-bit halves
   const ec9_acc top = acc + (ec9_acc)(int32_t)H8 * 256;
   FE_ASSERT(top > -((ec9_acc)1 << 40) && top < ((ec9_acc)1 << 40));
@@ -262,19 +180,11 @@ CG_HD void ec9_sqr_impl(f29& out, const f29& a, const f29& e) {
 }
 template <int C>
 CG_HD void ec9_sqr(f29& out, const f29& a) {
-#if EC9_SQR
   ec9_sqr_impl<C, false>(out, a, a);
-#else
-  ec9_mul<C>(out, a, a);
-#endif
 }
 template <int C>
 CG_HD void ec9_sqr_add(f29& out, const f29& a, const f29& e) {
-#if EC9_SQR
   ec9_sqr_impl<C, true>(out, a, e);
-#else
-  ec9_mul_add<C>(out, a, a, e);
-#endif
 }
 // a b + c d, one reduction
 template <int C>
@@ -372,7 +282,6 @@ CG_HD void jac_madd9(Jac& r, bool& inf, const f29& x2, const f29& y2, bool neg, 
   f29 Z1Z1, U2, ys, S2, H;
   ec9_sqr<C>(Z1Z1, r.Z);
   ec9_mul<C>(U2, x2, Z1Z1);
-#if EC9_SIGN_MUL
   // S2 = +-y2 Z1^3: each limb times an opaque +-1 (one v_mul_lo_u32 a limb, as fe9.h's
   // fe9_sign_mask) instead of a negation and a select (two)
   uint32_t sg = neg ? ~0u : 1u;
@@ -381,10 +290,6 @@ CG_HD void jac_madd9(Jac& r, bool& inf, const f29& x2, const f29& y2, bool neg, 
 #endif
 #pragma unroll
   for (int i = 0; i < 9; ++i) ys.v[i] = y2.v[i] * sg;
-#else
-#pragma unroll
-  for (int i = 0; i < 9; ++i) ys.v[i] = neg ? 0u - y2.v[i] : y2.v[i];  // S2 = +-y2 Z1^3
-#endif
   ec9_mul<C>(S2, ys, r.Z);
   ec9_mul<C>(S2, S2, Z1Z1);
   ec9_sub(H, U2, r.X);

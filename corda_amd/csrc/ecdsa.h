@@ -44,13 +44,6 @@ CG_HD bool u256_iszero(const u256w& a) {
   return o == 0;
 }
 
-CG_HD bool u256_eq(const u256w& a, const u256w& b) {
-  uint32_t o = 0;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) o |= a.w[i] ^ b.w[i];
-  return o == 0;
-}
-
 template <int C, int N>
 CG_HD bool u256_lt_mod(const u256w& a) {
   uint32_t br = 0;
@@ -207,9 +200,6 @@ CG_HD void jac_madd(Jac& r, const Jac& p, const f29& x2, const f29& y2, const Ec
 // X - delta and the Y3 / a = 0 D - X3 factors are semi-reduced (m29_sub2), used only as products'
 // operands; secp256r1's Z3 = 2 Y Z is one product instead of (Y + Z)^2 - gamma - delta. Same point
 // as jac_dbl.
-#ifndef CG_EC_DBL_LAZY  // 0: the round-3 v16 chains (A/B)
-#define CG_EC_DBL_LAZY 1
-#endif
 template <int C>
 CG_HD void jac_dbl_w(Jac& r, const Jac& p) {
   f29 t1, t2, t3, X3, Y3, Z3;
@@ -221,7 +211,6 @@ CG_HD void jac_dbl_w(Jac& r, const Jac& p) {
     m29_sub2<C, 0>(t1, p.X, delta);   // < 4m
     m29_add_lazy(t2, p.X, delta);     // < 4m
     m29_mul<C, 0>(alpha, t1, t2);
-#if CG_EC_DBL_LAZY
     // 3 (X - delta)(X + delta) as 2t (reduced) + t lazily: < 4m, a product operand only; 8 beta and
     // 8 gamma^2 as lazy sums of reduced 4 beta / 4 gamma^2, taken off in m29_sub_lazy3
     m29_add<C, 0>(t1, alpha, alpha);
@@ -239,23 +228,6 @@ CG_HD void jac_dbl_w(Jac& r, const Jac& p) {
     m29_sq<C, 0>(t2, t3);       // 4 gamma^2
     m29_add_lazy(t2, t2, t2);   // 8 gamma^2 < 4m
     m29_sub_lazy3<C, 0>(Y3, Y3, t2);
-#else
-    m29_add<C, 0>(t1, alpha, alpha);
-    m29_add<C, 0>(alpha, alpha, t1);  // 3 (X - delta)(X + delta)
-    m29_sq<C, 0>(X3, alpha);
-    m29_add<C, 0>(t1, beta, beta);
-    m29_add<C, 0>(t1, t1, t1);  // 4 beta
-    m29_add<C, 0>(t2, t1, t1);  // 8 beta
-    m29_sub<C, 0>(X3, X3, t2);
-    m29_add_lazy(t3, p.Z, p.Z);       // 2Z < 4m
-    m29_mul<C, 0>(Z3, p.Y, t3);       // 2 Y Z
-    m29_sub2<C, 0>(t1, t1, X3);       // 4 beta - X3, < 4m
-    m29_mul<C, 0>(Y3, alpha, t1);
-    m29_add_lazy(t3, gamma, gamma);
-    m29_sq<C, 0>(t2, t3);      // 4 gamma^2
-    m29_add<C, 0>(t2, t2, t2);  // 8 gamma^2
-    m29_sub<C, 0>(Y3, Y3, t2);
-#endif
   } else {  // a = 0 : dbl-2009-l
     f29 A, B, Cc, D, E, F;
     m29_sq<C, 0>(A, p.X);
@@ -266,7 +238,6 @@ CG_HD void jac_dbl_w(Jac& r, const Jac& p) {
     m29_sub<C, 0>(t1, t1, A);
     m29_sub<C, 0>(t1, t1, Cc);
     m29_add<C, 0>(D, t1, t1);
-#if CG_EC_DBL_LAZY
     // E = 3A as 2A (reduced) + A lazily (< 4m: F = E^2 and E (D - X3) stay under 16 m^2); 2D and 8C
     // as lazy sums of reduced values, taken off in m29_sub_lazy3
     m29_add<C, 0>(E, A, A);
@@ -280,19 +251,6 @@ CG_HD void jac_dbl_w(Jac& r, const Jac& p) {
     m29_add<C, 0>(t2, t2, t2);  // 4 C
     m29_add_lazy(t2, t2, t2);   // 8 C < 4m
     m29_sub_lazy3<C, 0>(Y3, Y3, t2);
-#else
-    m29_add<C, 0>(E, A, A);
-    m29_add<C, 0>(E, E, A);
-    m29_sq<C, 0>(F, E);
-    m29_add<C, 0>(t2, D, D);
-    m29_sub<C, 0>(X3, F, t2);
-    m29_sub2<C, 0>(t3, D, X3);        // < 4m
-    m29_mul<C, 0>(Y3, E, t3);
-    m29_add<C, 0>(t2, Cc, Cc);
-    m29_add<C, 0>(t2, t2, t2);
-    m29_add<C, 0>(t2, t2, t2);  // 8 C
-    m29_sub<C, 0>(Y3, Y3, t2);
-#endif
     m29_add_lazy(t3, p.Y, p.Y);
     m29_mul<C, 0>(Z3, t3, p.Z);
   }
@@ -301,18 +259,16 @@ CG_HD void jac_dbl_w(Jac& r, const Jac& p) {
   r.Z = Z3;
 }
 
-// r = p + (x2, +-y2) affine for the wide ladder: madd-2007-bl with fewer carry chains.
+// r = p + (x2, +-y2) affine for the wide ladder: madd-2004-hmv with few carry chains.
 //  * `inf` flags p = infinity (the ladder's start, or an exceptional P + (-P)) instead of testing Z;
 //  * the sign rides on S2 = +-y2 Z1^3 (m29_neg2: one chain);
-//  * H = U2 - X1 and V - X3 are semi-reduced (m29_sub2: one chain), both used only as
-//    multiplication operands against values < 4m;
-//  * Z3 = Z1 * 2H (one product) instead of (Z1 + H)^2 - Z1Z1 - HH (a square and two subtractions);
+//  * H = U2 - X1, r = S2 - Y1 and V - X3 are semi-reduced (m29_sub2: one chain), used only as
+//    multiplication operands against values < 4m (r^2 < 16 m^2);
+//  * HHH = H HH, V = X1 HH, X3 = r^2 - HHH - 2V, Y3 = r (V - X3) - Y1 HHH, Z3 = Z1 H: no 4HH, 2Y1 or
+//    2H (the same point as madd-2007-bl's, another Jacobian representative);
 //  * H == 0 (mod p), i.e. the exceptional cases, behind a limb-0 filter that honest inputs fail
 //    with probability ~3 / 2^29, so the wave skips the exact test.
 // Same point as jac_madd (the exceptional cases included: doubling, P + (-P) -> infinity).
-#ifndef CG_EC_MADD_LAZY  // 0: round-3 v15 chains, 1: lazy 4HH + three-chain X3, 2: madd-2004-hmv (A/B)
-#define CG_EC_MADD_LAZY 2
-#endif
 // Host-build counters of the exceptional cases (tests/native/host_kernels.cpp, tests/test_ec_exceptional.py):
 // jac_madd_w's doublings taken [0], infinities produced [1] and loads into an infinite accumulator
 // [2], and jac_madd9's entries into the exact path [3] (ec9.h). Compiled out of the device build.
@@ -334,17 +290,13 @@ CG_HD void jac_madd_w(Jac& r, bool& inf, const f29& x2, const f29& y2, bool neg,
     inf = false;
     return;
   }
-  f29 Z1Z1, U2, S2, H, HH, I, J, rr, V, t;
+  f29 Z1Z1, U2, S2, H, HH, HHH, rr, V, t;
   m29_sq<C, 0>(Z1Z1, r.Z);
   m29_mul<C, 0>(U2, x2, Z1Z1);
   m29_mul<C, 0>(S2, y2, r.Z);
   m29_mul<C, 0>(S2, S2, Z1Z1);
   if (neg) m29_neg2<C, 0>(S2, S2);
   m29_sub2<C, 0>(H, U2, r.X);
-#if CG_EC_MADD_LAZY == 2
-  // madd-2004-hmv: r = S2 - Y1 undoubled, so it may stay semi-reduced (r^2 < 16 m^2); no 4HH, 2Y1
-  // or 2H: HHH = H HH, V = X1 HH, X3 = r^2 - HHH - 2V, Y3 = r (V - X3) - Y1 HHH, Z3 = Z1 H (the
-  // same point as madd-2007-bl's, another Jacobian representative)
   m29_sub2<C, 0>(rr, S2, r.Y);
   if (m29_maybe_zero_semi<C, 0>(H)) {
     if (m29_zero_semi<C, 0>(H)) {
@@ -359,69 +311,18 @@ CG_HD void jac_madd_w(Jac& r, bool& inf, const f29& x2, const f29& y2, bool neg,
       return;
     }
   }
-  {
-    f29 HHH;
-    m29_sq<C, 0>(HH, H);
-    m29_mul<C, 0>(HHH, H, HH);
-    m29_mul<C, 0>(V, r.X, HH);
-    Jac o;
-    m29_sq<C, 0>(o.X, rr);
-    m29_add_lazy(t, HHH, V);  // HHH + 2V < 6m, limbs < 3 * 2^29
-    m29_add_lazy(t, t, V);
-    m29_sub_lazy3<C, 0>(o.X, o.X, t);
-    m29_sub2<C, 0>(t, V, o.X);
-    m29_mul<C, 0>(o.Y, rr, t);
-    m29_mul<C, 0>(t, r.Y, HHH);
-    m29_sub<C, 0>(o.Y, o.Y, t);
-    m29_mul<C, 0>(o.Z, r.Z, H);
-    r = o;
-    return;
-  }
-#endif
-  m29_sub<C, 0>(rr, S2, r.Y);
-  if (m29_maybe_zero_semi<C, 0>(H)) {
-    if (m29_zero_semi<C, 0>(H)) {
-      if (m29_iszero<C, 0>(rr)) {
-        EC_EXC_COUNT(0);
-        jac_dbl<C>(r, r);
-      } else {
-        EC_EXC_COUNT(1);
-        jac_set_inf<C>(r, K);
-        inf = true;
-      }
-      return;
-    }
-  }
   m29_sq<C, 0>(HH, H);
-#if CG_EC_MADD_LAZY
-  // 4 HH as lazy sums (< 8m, limbs < 2^31): its products are with H (< 4m) and X1 (< 2m), so
-  // a b < 32 m^2 < m R (m < 2^256), and a column stays below 9 * 2^60 + 9 * 2^58 + 2^35
-  m29_add_lazy(I, HH, HH);
-  m29_add_lazy(I, I, I);
-#else
-  m29_add<C, 0>(I, HH, HH);
-  m29_add_lazy(I, I, I);      // 4 HH (< 4m: multiply operand only)
-#endif
-  m29_mul<C, 0>(J, H, I);
-  m29_mul<C, 0>(V, r.X, I);
-  m29_add_lazy(rr, rr, rr);   // 2 (S2 - Y1) (multiply operand only)
+  m29_mul<C, 0>(HHH, H, HH);
+  m29_mul<C, 0>(V, r.X, HH);
   Jac o;
   m29_sq<C, 0>(o.X, rr);
-#if CG_EC_MADD_LAZY
-  m29_add_lazy(t, J, V);  // J + 2V < 6m, limbs < 3 * 2^29
+  m29_add_lazy(t, HHH, V);  // HHH + 2V < 6m, limbs < 3 * 2^29
   m29_add_lazy(t, t, V);
   m29_sub_lazy3<C, 0>(o.X, o.X, t);
-#else
-  m29_sub<C, 0>(o.X, o.X, J);
-  m29_add<C, 0>(t, V, V);
-  m29_sub<C, 0>(o.X, o.X, t);
-#endif
   m29_sub2<C, 0>(t, V, o.X);
   m29_mul<C, 0>(o.Y, rr, t);
-  m29_add_lazy(t, r.Y, r.Y);
-  m29_mul<C, 0>(t, t, J);
+  m29_mul<C, 0>(t, r.Y, HHH);
   m29_sub<C, 0>(o.Y, o.Y, t);
-  m29_add_lazy(H, H, H);      // 2H < 8m, limbs < 2^30: times Z1 < 2m
   m29_mul<C, 0>(o.Z, r.Z, H);
   r = o;
 }

@@ -16,16 +16,12 @@
 #include "ecdsa.h"
 
 #define EC_W 6
-#ifndef EC_WINDOWS  // windows per row; EC_ROWS = ceil(43 / EC_WINDOWS) (A/B builds: 11 and 4)
-#define EC_WINDOWS 4
-#endif
+#define EC_WINDOWS 4  // windows per row; EC_ROWS = ceil(43 / EC_WINDOWS)
 #define EC_DIGITS 43
 #define EC_ROWS ((EC_DIGITS + EC_WINDOWS - 1) / EC_WINDOWS)
 // quarter tables (keyws.h): EC_QWINDOWS windows per row, EC_QROWS rows (row j = 2^{66 j} Q), in
 // the first EC_QROWS rows of the key's EcRowTab
-#ifndef EC_QWINDOWS
 #define EC_QWINDOWS 11
-#endif
 #define EC_QROWS ((EC_DIGITS + EC_QWINDOWS - 1) / EC_QWINDOWS)
 #define EC_MULT 32
 #define EC_PACKED 11
@@ -133,55 +129,11 @@ struct EcRowScratch {
   f29 pre[EC_MULT];
 };
 
-// A G wide-table entry packed into 64 B (EC_GWIDE_PACK, A/B): x and y as canonical 256-bit values
-// (little-endian dwords), so a random gather is one 128-B line request instead of ~1.5 and the
-// table is 21.5 instead of 24.2 GB per curve; the ladder unpacks the 29-bit limbs (ec_unpack256).
-// Measured: ECDSA wide ladders 7.72 / 3.43 -> 7.79 / 3.46 ms per step (r1 / k1), headline within
-// noise (profiles/r05/ec_pack): the unpacking costs what the bytes saved; the 72-B entries stay.
-struct EcAffG64 {
-  uint32_t w[16];
-};
-CG_HD void ec_pack256(uint32_t* w, const f29& a) {  // a canonical (< 2^256)
-  uint64_t acc = 0;
-  int bits = 0, j = 0;
-#pragma unroll
-  for (int i = 0; i < 9; ++i) {
-    acc |= (uint64_t)a.v[i] << bits;
-    bits += 29;
-    if (bits >= 32) {
-      w[j++] = (uint32_t)acc;
-      acc >>= 32;
-      bits -= 32;
-    }
-  }
-  FE_ASSERT(j == 8 && acc == 0);
-}
-CG_HD void ec_unpack256(f29& a, const uint32_t* w) {
-#pragma unroll
-  for (int i = 0; i < 9; ++i) {
-    const int b = 29 * i, j = b >> 5, sh = b & 31;
-    const uint32_t lo = w[j], hi = j + 1 < 8 ? w[j + 1] : 0u;
-    a.v[i] = (uint32_t)((((uint64_t)hi << 32) | lo) >> sh) & M29_MASK;
-  }
-}
 template <int C>
 CG_HD void ec_put(EcAff& o, const f29& x, const f29& y) {
   o.x = x;
   o.y = y;
 }
-template <int C>
-CG_HD void ec_put(EcAffG64& o, const f29& x, const f29& y) {
-  f29 c;
-  m29_canon<C, 0>(c, x);
-  ec_pack256(o.w, c);
-  m29_canon<C, 0>(c, y);
-  ec_pack256(o.w + 8, c);
-}
-CG_HD void ec_pick(f29& x, f29& y, const EcAffG64* row, int a) {
-  ec_unpack256(x, row[a - 1].w);
-  ec_unpack256(y, row[a - 1].w + 8);
-}
-
 // cnt (<= EC_MULT) affine points first + k step, k = 0..cnt-1, with one batched inversion.
 template <int C, class Out>
 CG_HD void ec_multiples(Out* out, const Jac& first, const Jac& step, int cnt, EcRowScratch& s, const EcConsts& K) {
@@ -554,26 +506,10 @@ static_assert(EC_WIDE_GDIGITS * EC_WIDE_GW > 256, "G digits: room for the recodi
 struct EcWideTab {
   EcAff t[EC_WIDE_ROWS][EC_WIDE_MULT];  // t[j][k-1] = k 2^{8j} Q; t[32][k-1] = (128 + k) 2^{248} Q
 };
-// G entries: EC_GWIDE_ENTRY_BYTES 128 (A/B) pads each 72-B entry to one 128-B line (a random
-// gather then fetches one line instead of ~1.55, as the Ed25519 B entries, fe9.h GE9_NIELS_BYTES),
-// at 42.9 instead of 24.2 GB per curve. Measured slower: 336.3 -> 332.4 M sigs/s over 4 pairs
-// (profiles/r05/ecg128); the 72-B packing stays.
-#ifndef EC_GWIDE_ENTRY_BYTES
+// G entries keep the 72-B affine packing (a random gather fetches ~1.55 128-B lines)
 #define EC_GWIDE_ENTRY_BYTES 72
-#endif
-#ifndef EC_GWIDE_PACK
-#define EC_GWIDE_PACK 0
-#endif
-#if EC_GWIDE_PACK
-typedef EcAffG64 EcAffG;
-#elif EC_GWIDE_ENTRY_BYTES == 72
 typedef EcAff EcAffG;
-#else
-struct EcAffG : EcAff {
-  uint32_t pad[(EC_GWIDE_ENTRY_BYTES - 72) / 4];
-};
-static_assert(sizeof(EcAffG) == EC_GWIDE_ENTRY_BYTES, "padded G entry");
-#endif
+static_assert(sizeof(EcAffG) == EC_GWIDE_ENTRY_BYTES, "G entry");
 struct EcGWideTab {
   EcAffG t[EC_WIDE_GDIGITS][EC_WIDE_GMULT];  // t[u][k-1] = k 2^{EC_WIDE_GW u} G
 };
@@ -613,42 +549,6 @@ CG_HD int ec_digit_at(const uint32_t* packed, int t) {
   return Bits == 16 ? (int)(int16_t)(uint16_t)(packed[t >> 1] >> ((t & 1) * 16)) : (int)packed[t];
 }
 
-// The affine multiples first + k step, k = 0..cnt-1, one field inversion for the whole run. The
-// forward pass leaves X, Y in out[k], Z in z[k] and the running Z products in pre[k]; the backward
-// pass starts from inv = 1 / pre[cnt-1]. `step` is affine (x, y), so each step is a mixed addition.
-// The wide-table build runs the passes as separate kernels with one inversion per row between.
-template <int C>
-CG_HD void ec_multiples_fwd(EcAff* out, const Jac& first, const f29& sx, const f29& sy, int cnt, f29* z, f29* pre,
-                            const EcConsts& K) {
-  Jac acc = first;
-  for (int k = 0; k < cnt; ++k) {
-    if (k > 0) jac_madd<C>(acc, acc, sx, sy, K);  // acc == step goes through the doubling branch
-    out[k].x = acc.X;
-    out[k].y = acc.Y;
-    z[k] = acc.Z;
-    if (k == 0) pre[0] = acc.Z;
-    else m29_mul<C, 0>(pre[k], pre[k - 1], acc.Z);
-  }
-}
-
-template <int C>
-CG_HD void ec_multiples_bwd(EcAff* out, const f29& inv_all, int cnt, const f29* z, const f29* pre) {
-  f29 inv = inv_all;
-  for (int k = cnt - 1; k >= 0; --k) {
-    f29 zi, zi2, zi3;
-    if (k > 0) {
-      m29_mul<C, 0>(zi, inv, pre[k - 1]);
-      m29_mul<C, 0>(inv, inv, z[k]);
-    } else {
-      zi = inv;
-    }
-    m29_sq<C, 0>(zi2, zi);
-    m29_mul<C, 0>(zi3, zi2, zi);
-    m29_mul<C, 0>(out[k].x, out[k].x, zi2);
-    m29_mul<C, 0>(out[k].y, out[k].y, zi3);
-  }
-}
-
 // m * (x, y) for a small m >= 1 and an affine (x, y) (double-and-add, MSB first)
 template <int C>
 CG_HD void jac_small_mul_aff(Jac& r, const f29& x, const f29& y, uint32_t m, const EcConsts& K) {
@@ -658,17 +558,6 @@ CG_HD void jac_small_mul_aff(Jac& r, const f29& x, const f29& y, uint32_t m, con
     if ((m >> b) & 1u) jac_madd<C>(F, F, x, y, K);
   }
   r = F;
-}
-
-// Forward pass of multiples g * cnt + 1 .. (g + 1) * cnt of wide row j (row 32: 129..256 times the
-// top row's base 2^{248} Q); `base` is affine (k_ec_wide_chain normalises the row bases).
-template <int C>
-CG_HD void ec_wide_group_fwd(EcAff* out, const EcAff& base, int j, int g, int cnt, f29* z, f29* pre,
-                             const EcConsts& K) {
-  const uint32_t m = (j < EC_WIDE_DIGITS ? 0u : (uint32_t)EC_WIDE_MULT) + (uint32_t)(g * cnt) + 1u;
-  Jac F;
-  jac_small_mul_aff<C>(F, base.x, base.y, m, K);
-  ec_multiples_fwd<C>(out, F, base.x, base.y, cnt, z, pre, K);
 }
 
 // ---- wide-table build (as ed25519_rows.h "wide-table build"): one lane per (wide key, row j, group g
@@ -889,9 +778,8 @@ CG_HD void ec_wide_row_build(EcAff* out, const Park& pk, const EcAff& base, bool
 }
 // lanes per row (each walks 128 / EC_WIDE_ROW_LANES entries with its own inversion): more waves for
 // a latency-bound walk against one more scalar multiplication and inversion per extra lane
-#ifndef EC_WIDE_ROW_LANES
-#define EC_WIDE_ROW_LANES 2  // A/B 1 / 2 / 4 lanes: 218.6 / 226.7 / 226.6 and 222.7 / 234.8 / 223.4 M sigs/s (profiles/r03/ab_lanes)
-#endif
+// (1 / 2 / 4 lanes measured 218.6 / 226.7 / 226.6 and 222.7 / 234.8 / 223.4 M sigs/s, profiles/r03/ab_lanes)
+#define EC_WIDE_ROW_LANES 2
 static_assert(EC_WIDE_MULT % EC_WIDE_ROW_LANES == 0 && EC_WIDE_MULT / EC_WIDE_ROW_LANES >= 2, "row split");
 
 // in place: z[g] <- 1 / z[g] mod p for the NG products of one row (prefix products in pre[])
@@ -933,21 +821,6 @@ CG_HD void jac_batch_to_affine(EcAff* out, const Jac* P, int n, f29* pre, const 
     m29_mul<C, 0>(out[k].x, P[k].X, zi2);
     m29_mul<C, 0>(out[k].y, P[k].Y, zi3);
   }
-}
-
-// Inverses of G group products (one inversion): out[g] = 1 / t_g.
-template <int C, int G>
-CG_HD void m29_batch_invert_small(f29* out, const f29* t, const EcConsts& K) {
-  f29 pre[G];
-  pre[0] = t[0];
-  for (int g = 1; g < G; ++g) m29_mul<C, 0>(pre[g], pre[g - 1], t[g]);
-  f29 inv;
-  m29_inv<C, 0>(inv, pre[G - 1], K.one_p);
-  for (int g = G - 1; g > 0; --g) {
-    m29_mul<C, 0>(out[g], inv, pre[g - 1]);
-    m29_mul<C, 0>(inv, inv, t[g]);
-  }
-  out[0] = inv;
 }
 
 // u1 G over the constant radix-2^EC_WIDE_GW table (no doublings needed: added after the Q part)
@@ -1077,11 +950,4 @@ CG_HD void ec_gwide_group_from(Out* out, const Jac& P, int g, EcRowScratch& s, c
     if ((m >> b) & 1u) jac_add<C>(F, F, P, K);
   }
   ec_multiples<C>(out, F, P, EC_MULT, s, K);
-}
-
-template <int C, class Out>
-CG_HD void ec_gwide_group(Out* out, int u, int g, EcRowScratch& s, const EcConsts& K) {
-  Jac P = {K.gx, K.gy, K.one_p};
-  if (u > 0) jac_dbl_n<C>(P, P, EC_WIDE_GW * u);
-  ec_gwide_group_from<C>(out, P, g, s, K);
 }

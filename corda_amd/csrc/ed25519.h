@@ -47,12 +47,6 @@ CG_HD void ge_niels_identity(ge_niels& c) {
   fe_1(c.ymx);
   fe_0(c.xy2d);
 }
-// the identity as a half-scaled entry (ge_madd_half_signed)
-CG_HD void ge_niels_identity_half(ge_niels& c) {
-  fe_half(c.ypx);
-  fe_half(c.ymx);
-  fe_0(c.xy2d);
-}
 
 // i2p GroupElement(curve, byte[] s): y = s with bit 255 masked (y >= p accepted), x from
 // u/v; no square root -> KEY_INVALID; sign fix-up (x = 0 with sign bit 1 is accepted).
@@ -284,10 +278,6 @@ CG_HD void ed_consts_init(Ed25519Consts& C) {
 // B (constant, staged in LDS).
 struct EdRowTab {
   ge_niels t[8][8];  // t[j][k-1] = k * 2^{32j} * P, affine niels, tight
-};
-
-struct Ed25519Rows {
-  EdRowTab B;
 };
 
 // Normalise 8 extended points to affine niels with one inversion (Montgomery's trick). Half:

@@ -17,12 +17,8 @@
 // 2 windows (22 rows x 32 multiples per key, 6 doublings per item), B in signed radix 2^10
 // over a constant table (26 rows x 512).
 #define ED_W 6
-#ifndef ED_K  // windows per row (A/B builds: 11 gives 4 rows and 60 doublings per item)
-#define ED_K 2
-#endif
-#ifndef ED_WB
+#define ED_K 2  // windows per row
 #define ED_WB 10
-#endif
 
 template <int W, int K>
 struct EdRowsCfg {
@@ -175,21 +171,6 @@ CG_HD void ed_multiples_from(ge_niels* row, const ge_p3& first, const ge_p3& P, 
   ed_multiples_bwd<M>(row, inv, zpre, d2);
 }
 
-// Inverses of G group products t_g (one inversion, Montgomery's trick): out[g] = 1 / t_g.
-template <int G>
-CG_HD void fe_batch_invert_small(fe* out, const fe* t) {
-  fe pre[G];
-  fe_copy(pre[0], t[0]);
-  for (int g = 1; g < G; ++g) fe_mul(pre[g], pre[g - 1], t[g]);
-  fe inv;
-  fe_invert(inv, pre[G - 1]);
-  for (int g = G - 1; g > 0; --g) {
-    fe_mul(out[g], inv, pre[g - 1]);
-    fe_mul(inv, inv, t[g]);
-  }
-  fe_copy(out[0], inv);
-}
-
 template <int W, int K>
 CG_HD void ed_rows_w_init(EdRowTabW<W, K>& T, const ge_p3& P, const fe& d2) {
   typedef EdRowsCfg<W, K> C;
@@ -328,99 +309,6 @@ CG_HD int sc_digit_at(const uint32_t* packed, int t) {
   return Bits == 16 ? sc_digit_h(packed, t) : (int)packed[t];
 }
 
-// R' = h (-A) + S' B: A over the per-key W/K rows, B over the WB table; left projective.
-// `Pick(out, row, digit)` loads a signed niels entry (identity for 0) from either table.
-// Signed = true: entries are picked by |digit| and the sign goes through ge_madd_signed (the
-// form k_ed_ladder_pf runs; the host tests run it with bounds checks).
-template <int W, int K, int WB, bool Signed = false, class RowA, class TabB, class PickA, class PickB>
-CG_HD void ed_double_scalar_wb(ge_p2& out, const uint32_t* eh, const uint32_t* esb, const RowA& TA, const TabB& TB,
-                               PickA pick_a, PickB pick_b) {
-  typedef EdRowsCfg<W, K> C;
-  typedef EdBCfg<W, K, WB> CB;
-  ge_p3 R;
-  ge_p3_0(R);
-  ge_p1p1 t;
-  ge_p2 q;
-  for (int i = K - 1; i >= 0; --i) {
-    if (i != K - 1) {  // R arrives as p2 (q) from the previous window's last addition
-      for (int d = 0; d < W - 1; ++d) {
-        ge_p2_dbl(t, q);
-        ge_p1p1_to_p2(q, t);
-      }
-      ge_p2_dbl(t, q);
-      ge_p1p1_to_p3(R, t);
-    }
-    const int u_lo = (i * CB::kDigits + K - 1) / K, u_hi = ((i + 1) * CB::kDigits + K - 1) / K;
-    const int n_a = (C::kDigits - i + K - 1) / K;  // rows with a digit in this window
-    const int n_ops = n_a + (u_hi - u_lo);
-    for (int k = 0; k < n_ops; ++k) {
-      ge_niels n;
-      const int dg = k < n_a ? sc_digit_b(eh, K * k + i) : sc_digit_h(esb, u_lo + k - n_a);
-      const int dp = Signed && dg < 0 ? -dg : dg;
-      if (k < n_a) {
-        pick_a(n, TA.t[k], dp);
-      } else {
-        pick_b(n, TB.t[u_lo + k - n_a], dp);
-      }
-      if (Signed) {
-        ge_madd_signed(t, R, n, dg < 0);
-      } else {
-        ge_madd(t, R, n);
-      }
-      if (k + 1 == n_ops) {
-        ge_p1p1_to_p2(q, t);  // next: doublings (or the end), which need no T
-      } else {
-        ge_p1p1_to_p3(R, t);
-      }
-    }
-  }
-  out = q;
-}
-
-// R' = h (-A) + S' B for a key that has only row 0 of its table (a key with few items in the
-// batch, keyws.h): Horner over h's signed radix-2^W digits, W doublings between digits (252 in
-// all), each B row added at the digit position whose remaining doublings its row scale
-// expects (digit position i_u = EdBCfg::window(u) < K is followed by W i_u doublings, as in
-// ed_double_scalar_wb). Same digits, same B table, same result.
-template <int W, int K, int WB, class TabB, class PickA, class PickB>
-CG_HD void ed_double_scalar_row0(ge_p2& out, const uint32_t* eh, const uint32_t* esb, const ge_niels* row0,
-                                 const TabB& TB, PickA pick_a, PickB pick_b) {
-  typedef EdRowsCfg<W, K> C;
-  typedef EdBCfg<W, K, WB> CB;
-  ge_p3 R;
-  ge_p3_0(R);
-  ge_p1p1 t;
-  ge_p2 q;
-  for (int td = C::kDigits - 1; td >= 0; --td) {
-    if (td != C::kDigits - 1) {
-      for (int d = 0; d < W - 1; ++d) {
-        ge_p2_dbl(t, q);
-        ge_p1p1_to_p2(q, t);
-      }
-      ge_p2_dbl(t, q);
-      ge_p1p1_to_p3(R, t);
-    }
-    const int u_lo = td < K ? (td * CB::kDigits + K - 1) / K : 0;
-    const int u_hi = td < K ? ((td + 1) * CB::kDigits + K - 1) / K : 0;
-    const int n_ops = 1 + (u_hi - u_lo);
-    for (int k = 0; k < n_ops; ++k) {
-      ge_niels n;
-      if (k == 0) {
-        pick_a(n, row0, sc_digit_b(eh, td));
-      } else {
-        pick_b(n, TB.t[u_lo + k - 1], sc_digit_h(esb, u_lo + k - 1));
-      }
-      ge_madd(t, R, n);
-      if (k + 1 == n_ops) {
-        ge_p1p1_to_p2(q, t);
-      } else {
-        ge_p1p1_to_p3(R, t);
-      }
-    }
-  }
-  out = q;
-}
-
 // Table rows: row u holds the affine multiples 1..kMult of 2^shift(u) B.
 template <int W, int K, int WB>
 CG_HD void ed_btab_wb_row(ge_niels* row, const ge_p3& B, int u, const fe& d2) {
@@ -456,9 +344,9 @@ struct EdWideCfg {
 static_assert(253 % ED_WIDE_W != 0 && 253 % ED_WIDE_BW != 0, "the top digit keeps headroom for the carry");
 
 // Both wide tables hold half-scaled niels entries ((y+x)/2, (y-x)/2, x y d), added with
-// ge_madd_half_signed (no doubling of Z and no carry pass per addition); digit 0 adds the
-// half-scaled identity (ge_niels_identity_half).
-// Entries in the radix-2^29 form (fe9.h: the wide ladders run in it), 112 B each.
+// ge9_madd_half / ge9_madd_half_flip (no doubling of Z and no carry pass per addition); digit 0 adds
+// the half-scaled identity (ge9_niels_identity_half).
+// Entries in the radix-2^29 form (fe9.h: the wide ladders run in it), GE9_NIELS_BYTES each.
 struct EdWideTab {
   ge9_niels t[EdWideCfg::kRows][EdWideCfg::kMult];  // t[j][k-1] = k 2^{8j} (-A), half-scaled
 };
@@ -485,7 +373,6 @@ CG_HD void ed_double_scalar_wide(ge_p2& out, const uint32_t* eh, const uint32_t*
   ge9_p3 R;
   bool n0;
   const ge9_niels q0 = entry(0, n0);
-#if ED_SIGN_FOLD
   // the running point is s_o R (fe9.h ge9_madd_half_flip): op o adds the stored entry of |digit|
   // and flips its output by s_o s_{o+1}; the last op by s_{N-1} alone
   bool n1;
@@ -499,15 +386,6 @@ CG_HD void ed_double_scalar_wide(ge_p2& out, const uint32_t* eh, const uint32_t*
     q = qn;
     n1 = nn;
   }
-#else
-  ge9_from_niels_half(R, q0, n0);  // identity + q0: one product, not seven
-  for (int o = 1; o < EdWideCfg::kOps; ++o) {
-    bool neg;
-    const ge9_niels n = entry(o, neg);
-    if (o + 1 < EdWideCfg::kOps) ge9_madd_half<true>(R, R, n, neg);
-    else ge9_madd_half<false>(R, R, n, neg);
-  }
-#endif
   ge9_to_p2(out, R);
 }
 
@@ -727,10 +605,7 @@ CG_HD void ed_wide_row_build(Out* out, const Park& pk, const ge_p3& P, int e0, i
   fe_mul(inv, inv, h);  // 1 / (2 Z_e0 .. Z_e1-1): the half-scaled entries' 1/2
   fe_add(d4, d2, d2);
   fe_carry(d4);
-#ifndef ED_ROWS_PREFETCH  // 1: the walk back loads each entry's parked values one entry ahead
-#define ED_ROWS_PREFETCH 1
-#endif
-#if ED_ROWS_PREFETCH
+  // the walk back loads each entry's parked values one entry ahead
   fe X, Y, Z, pr;
   pk.get(e1 - 1 - e0, X, Y, Z);
   if (e1 - 1 > e0) pk.get_run(e1 - 2 - e0, pr);
@@ -741,13 +616,6 @@ CG_HD void ed_wide_row_build(Out* out, const Park& pk, const ge_p3& P, int e0, i
       pk.get(k - 1 - e0, Xn, Yn, Zn);
       if (k - 1 > e0) pk.get_run(k - 2 - e0, prn);
     }
-#else  // parked lane-interleaved, the loads are coalesced: no prefetch registers (occupancy)
-#pragma unroll 1
-  for (int k = e1 - 1; k >= e0; --k) {
-    fe X, Y, Z, pr;
-    pk.get(k - e0, X, Y, Z);
-    if (k > e0) pk.get_run(k - 1 - e0, pr);
-#endif
     ge_p2 p;
     p.X = X;
     p.Y = Y;
@@ -761,12 +629,10 @@ CG_HD void ed_wide_row_build(Out* out, const Park& pk, const ge_p3& P, int e0, i
     ge_niels n;
     ed_niels_from(n, p, zi, d4);
     ed_niels_store(out + k, n);
-#if ED_ROWS_PREFETCH
     X = Xn;
     Y = Yn;
     Z = Zn;
     pr = prn;
-#endif
   }
 }
 
@@ -792,13 +658,6 @@ struct EdPark9Lanes {
     for (int d = 0; d < 9; ++d) f.v[d] = p[(size_t)d * lanes];
   }
 };
-// FE9_ROWS_ILP (round 6, A/B): the row walk's products without the ladders' opaque column chains
-// (fe9_mul Pin = false): one lane per row, 2 waves per SIMD, every entry dependent on the previous
-// one -- latency-bound, so the products' own instruction-level parallelism is what hides latency
-#ifndef FE9_ROWS_ILP
-#define FE9_ROWS_ILP 0
-#endif
-#define FE9_ROWS_PIN (!FE9_ROWS_ILP)
 template <class Park>
 CG_HD void ed_wide_row_build9(ge9_niels* out, const Park& pk, const ge_p3& P, int e0, int e1, const fe& d2) {
   fe9 cYpX, cYmX, cZ2, cT2d, d4;
@@ -833,19 +692,19 @@ CG_HD void ed_wide_row_build9(ge9_niels* out, const Park& pk, const ge_p3& P, in
       fe9 a, b, A, B, C, D, E, H, G, F;
       fe9_add(a, R.Y, R.X);
       fe9_sub(b, R.Y, R.X);
-      fe9_mul<false, FE9_ROWS_PIN>(A, a, cYpX);
-      fe9_mul<true, FE9_ROWS_PIN>(B, b, cYmX);
-      fe9_mul<false, FE9_ROWS_PIN>(C, R.T, cT2d);
-      fe9_mul<false, FE9_ROWS_PIN>(D, R.Z, cZ2);
+      fe9_mul<false>(A, a, cYpX);
+      fe9_mul<true>(B, b, cYmX);
+      fe9_mul<false>(C, R.T, cT2d);
+      fe9_mul<false>(D, R.Z, cZ2);
       fe9_sub(E, A, B);
       fe9_add(H, A, B);
       fe9_add(G, D, C);
       fe9_subk(F, D, C);
-      fe9_mul<true, FE9_ROWS_PIN>(R.X, E, F);
-      fe9_mul<false, FE9_ROWS_PIN>(R.Y, G, H);
-      fe9_mul<false, FE9_ROWS_PIN>(R.Z, G, F);
-      fe9_mul<true, FE9_ROWS_PIN>(R.T, E, H);
-      fe9_mul<false, FE9_ROWS_PIN>(run, run, R.Z);
+      fe9_mul<true>(R.X, E, F);
+      fe9_mul<false>(R.Y, G, H);
+      fe9_mul<false>(R.Z, G, F);
+      fe9_mul<true>(R.T, E, H);
+      fe9_mul<false>(run, run, R.Z);
     }
     const int i = k - e0;
     pk.st(i, 0, R.X);
@@ -872,21 +731,21 @@ CG_HD void ed_wide_row_build9(ge9_niels* out, const Park& pk, const ge_p3& P, in
       fe9 pr, Z;
       pk.ld(i - 1, 3, pr);
       pk.ld(i, 2, Z);
-      fe9_mul<false, FE9_ROWS_PIN>(zi, inv, pr);
-      fe9_mul<false, FE9_ROWS_PIN>(inv, inv, Z);
+      fe9_mul<false>(zi, inv, pr);
+      fe9_mul<false>(inv, inv, Z);
     } else {
       zi = inv;
     }
     fe9 x, y, s, xy;
-    fe9_mul<false, FE9_ROWS_PIN>(x, X, zi);
-    fe9_mul<false, FE9_ROWS_PIN>(y, Y, zi);
+    fe9_mul<false>(x, X, zi);
+    fe9_mul<false>(y, Y, zi);
     ge9_niels n;
     fe9_add(s, y, x);
     fe9_carry(n.ypx, s);
     fe9_subk(s, y, x);
     fe9_carry(n.ymx, s);
-    fe9_mul<false, FE9_ROWS_PIN>(xy, x, y);
-    fe9_mul<false, FE9_ROWS_PIN>(n.xy2d, xy, d4);
+    fe9_mul<false>(xy, x, y);
+    fe9_mul<false>(n.xy2d, xy, d4);
     for (uint32_t& w : n.pad) w = 0;
     out[k] = n;
   }
@@ -940,17 +799,17 @@ CG_HD void ed_row_build_parked(ge_niels* row, const ge_p3& P, const fe& d2, cons
   }
 }
 
-#ifndef ED_WIDE_ROW_LANES  // lanes per row (as EC_WIDE_ROW_LANES): 1 / 2 / 4 lanes, headline A/B in 3
-#define ED_WIDE_ROW_LANES 1  // rounds: 314.2 / 311.5 / 311.1 M sigs/s (profiles/r04/erl; one inversion per row,
-#endif                       // one round of 2 waves per SIMD for the 4 096 keys' 32 rows)
+// lanes per row (as EC_WIDE_ROW_LANES): one inversion per row, one round of 2 waves per SIMD for the
+// 4 096 keys' 32 rows (1 / 2 / 4 lanes measured 314.2 / 311.5 / 311.1 M sigs/s, profiles/r04/erl)
+#define ED_WIDE_ROW_LANES 1
 static_assert(EdWideCfg::kMult % ED_WIDE_ROW_LANES == 0, "row split");
 
 // ---------------------------------------------------------------- full / row-0 tables + wide B
 // R' = h (-A) + S' B for keys with full tables (W/K rows of -A, K windows, (K-1) W doublings) or
 // row 0 only (Horner, 252 doublings), with S' B from the constant radix-2^ED_WIDE_BW table at the
 // end: the B digits need no doublings, so they all go after the last window (12 additions instead
-// of the 26 of the round-1 radix-2^10 table spread over the windows). `Signed`: entries by |digit|,
-// the sign through ge_madd_signed / ge_madd_half_signed (the form k_ed_ladder_pf runs).
+// of the 26 of the round-1 radix-2^10 table spread over the windows). Entries by |digit|,
+// the sign through ge_madd_signed / ge9_madd_half (the form k_ed_ladder_pf runs).
 // S' B over the constant radix-2^ED_WIDE_BW table, in the radix-2^29 arithmetic of its entries
 // (fe9.h): R (extended, radix 2^25.5) in, q (projective, radix 2^25.5) out. Entries by |digit|,
 // the sign through ge9_madd_half.

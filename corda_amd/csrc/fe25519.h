@@ -134,17 +134,7 @@ CG_HD void fe_reduce_cols(fe& out, fe_acc_t* h) {
     h[(i) + 1] += c;                          \
     h[i] &= ((fe_acc_t)1 << (sh)) - 1;        \
   }
-#ifdef FE_SINGLE_CARRY_CHAIN  // one chain 0 -> 9 (11 carries): 2% fewer ladder instructions, a longer dependency chain
-  FE_CARRY(0, 26);
-  FE_CARRY(1, 25);
-  FE_CARRY(2, 26);
-  FE_CARRY(3, 25);
-  FE_CARRY(4, 26);
-  FE_CARRY(5, 25);
-  FE_CARRY(6, 26);
-  FE_CARRY(7, 25);
-  FE_CARRY(8, 26);
-#else  // two interleaved chains (ref10 order, 12 carries)
+  // two interleaved chains (ref10 order, 12 carries)
   FE_CARRY(0, 26);
   FE_CARRY(4, 26);
   FE_CARRY(1, 25);
@@ -155,7 +145,6 @@ CG_HD void fe_reduce_cols(fe& out, fe_acc_t* h) {
   FE_CARRY(7, 25);
   FE_CARRY(4, 26);
   FE_CARRY(8, 26);
-#endif
   {
     fe_acc_t c = h[9] >> 25;
     h[9] &= FE_M25;
@@ -381,11 +370,4 @@ CG_HD int fe_iszero(const fe& f) {
 #pragma unroll
   for (int i = 0; i < 8; ++i) o |= w[i];
   return o == 0;
-}
-
-// constant-index select helpers
-CG_HD void fe_cmov(fe& h, const fe& f, uint32_t b) {
-  const uint32_t m = 0u - b;
-#pragma unroll
-  for (int i = 0; i < 10; ++i) h.v[i] ^= (h.v[i] ^ f.v[i]) & m;
 }

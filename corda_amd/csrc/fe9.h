@@ -141,12 +141,9 @@ typedef __int128 fe9_acc;
 #endif
 
 // out = a b mod p, tight. Signed: limbs of a and b are int32 (class S operands), else uint32.
-// Pin (default FE9_PIN_ACC): the column sums as one opaque chain from the carry (the ladders: issue-
-// bound, 2-3 waves per SIMD hide the chain's latency). Pin = false: the compiler's independent column
-// chains, for latency-bound callers with few waves per SIMD (the wide-row builds of phase 1,
-// round 6: FE9_ROWS_ILP).
-// Copy = false: no opaque operand copies (round 6: operands used twice, whose copies are v_movs)
-template <bool Signed, bool Pin = true, bool Copy = true>
+// On the device the column sums are one opaque chain from the carry, and the operands are opaque
+// copies. Copy = false: no opaque operand copies (operands used twice, whose copies are v_movs).
+template <bool Signed, bool Copy = true>
 CG_HD void fe9_mul(fe9& out, const fe9& a, const fe9& b) {
   FE9_COUNT();
   const uint32_t k1216 = fe9_opaque(1216u), k9728 = fe9_opaque(9728u);
@@ -187,10 +184,7 @@ CG_HD void fe9_mul(fe9& out, const fe9& a, const fe9& b) {
   FE_ASSERT(acc >= 0 && T < (1ull << 35));
 #else
   typedef typename std::conditional<Signed, int64_t, uint64_t>::type acc_t;
-#ifndef FE9_PIN_COPIES
-#define FE9_PIN_COPIES 1
-#endif
-#if defined(__HIP_DEVICE_COMPILE__) && FE9_PIN_COPIES
+#if defined(__HIP_DEVICE_COMPILE__)
   // opaque 32-bit operands: in the ladder loop the compiler otherwise widened loop-carried
   // differences to 64 bits and emitted 64 x 64-bit multiplies (3 MACs + moves each)
   fe9 a_ = a, b_ = b;
@@ -216,27 +210,14 @@ CG_HD void fe9_mul(fe9& out, const fe9& a, const fe9& b) {
   acc_t acc = Signed ? (acc_t)(-(int64_t)19 * ((int64_t)1 << 40)) : 0;
 #pragma unroll
   for (int m = 0; m < 9; ++m) {
-#ifndef FE9_PIN_ACC  // round 4: 2326 -> 2217 VALU per two additions (v_lshl_add_u64 126 -> 22, plus
-#define FE9_PIN_ACC 1  // 333 s_nop the other waves fill), k_ed_ladder_wide 2.80 -> 2.68 ms (profiles/r04/pin)
-#endif
-#ifndef FE9_SCAN_ASM  // 1: pinned MACs (fe9_mac_*): 1004 -> 993 VALU per addition, but 176 s_nop (rejected)
-#define FE9_SCAN_ASM 0
-#endif
 #pragma unroll
     for (int i = 0; i <= m; ++i) {
-      if (FE9_SCAN_ASM && m > 0) {  // every MAC of the chain (an asm one among C adds is re-associated anyway);
-                                   // column 0 stays C: its constant addend then needs no VGPR copy
-        if (Signed) acc = (acc_t)fe9_mac_i(a.v[i], b.v[m - i], (int64_t)acc);
-        else acc = (acc_t)fe9_mac_u(a.v[i], b.v[m - i], (uint64_t)acc);
-      } else if (Signed) {
-        acc += (acc_t)(int64_t)(int32_t)a.v[i] * (int64_t)(int32_t)b.v[m - i];
-      } else {
-        acc += (acc_t)((uint64_t)a.v[i] * b.v[m - i]);
-      }
-#if defined(__HIP_DEVICE_COMPILE__) && FE9_PIN_ACC
+      if (Signed) acc += (acc_t)(int64_t)(int32_t)a.v[i] * (int64_t)(int32_t)b.v[m - i];
+      else acc += (acc_t)((uint64_t)a.v[i] * b.v[m - i]);
+#if defined(__HIP_DEVICE_COMPILE__)
       // the running column sum as an opaque value after every MAC: the carry-in then stays the
       // first MAC's addend instead of being re-associated into a separate 64-bit add
-      if (Pin) asm volatile("" : "+v"(acc));
+      asm volatile("" : "+v"(acc));
 #endif
     }
     if (m <= 7) acc = (acc_t)fe9_mac_u((uint32_t)hc[m], k1216, (uint64_t)acc);
@@ -257,7 +238,7 @@ CG_HD void fe9_mul(fe9& out, const fe9& a, const fe9& b) {
     }
   }
   const uint64_t T = (uint64_t)acc;
-#if defined(__HIP_DEVICE_COMPILE__) && FE9_PIN_COPIES
+#if defined(__HIP_DEVICE_COMPILE__)
 #undef a
 #undef b
 #endif
@@ -334,19 +315,16 @@ struct ge9_p3 {
   fe9 X, Y, Z, T;
 };
 // A half-scaled wide-table entry ((y+x)/2, (y-x)/2, x y d), tight: 108 B of limbs, gathered as
-// 7 x 16-B LDS DMA chunks. Padded to one 128-B line (round 5; GE9_NIELS_BYTES 112 = the round-4
-// packing): a random gather into the fixed-base table then fetches one line instead of 1.9 (every
-// HBM read request is a 128-B line on gfx950, profiles/r05/calib). The B table grows 37.6 -> 42.9 GB;
-// headline A/B 326.9 -> 332.5 M sigs/s over 4 pairs (Ed25519 ladder 13.06 -> 12.75 ms per step,
-// profiles/r05/n128).
-#ifndef GE9_NIELS_BYTES
+// 7 x 16-B LDS DMA chunks. Padded to one 128-B line: a random gather into the fixed-base table then
+// fetches one line instead of the 1.9 of a 112-B packing (every HBM read request is a 128-B line on
+// gfx950, profiles/r05/calib). The B table grows 37.6 -> 42.9 GB; headline 326.9 -> 332.5 M sigs/s
+// over 4 pairs (Ed25519 ladder 13.06 -> 12.75 ms per step, profiles/r05/n128).
 #define GE9_NIELS_BYTES 128
-#endif
 struct ge9_niels {
   fe9 ypx, ymx, xy2d;
   uint32_t pad[(GE9_NIELS_BYTES - 108) / 4];
 };
-static_assert(sizeof(ge9_niels) == GE9_NIELS_BYTES && (GE9_NIELS_BYTES == 112 || GE9_NIELS_BYTES == 128),
+static_assert(sizeof(ge9_niels) == GE9_NIELS_BYTES && GE9_NIELS_BYTES == 128,
               "ge9_niels layout");
 
 CG_HD void ge9_niels_from(ge9_niels& o, const ge_niels& n) {
@@ -363,13 +341,6 @@ CG_HD void ge9_niels_identity_half(ge9_niels& n) {
   fe9_half(n.ypx);
   fe9_half(n.ymx);
   fe9_0(n.xy2d);
-}
-
-CG_HD void ge9_p3_0(ge9_p3& h) {
-  fe9_0(h.X);
-  fe9_1(h.Y);
-  fe9_1(h.Z);
-  fe9_0(h.T);
 }
 
 CG_HD void ge9_from_p3(ge9_p3& r, const ge_p3& p) {
@@ -412,18 +383,12 @@ CG_HD void ge9_madd_half(ge9_p3& r, const ge9_p3& p, const ge9_niels& q, bool ne
   if (WithT) fe9_mul<true>(r.T, E, H);
 }
 
-// r = (-1)^flip (p + q) for a half-scaled entry q taken as stored (round 6, ED_SIGN_FOLD): a ladder
+// r = (-1)^flip (p + q) for a half-scaled entry q taken as stored: a ladder
 // keeps its running point as s_k R_k, s_k the sign of op k's digit, so every op adds the entry of
 // |digit| and the sign change s_k s_{k+1} rides on the output. -P = (-X, Y, Z, -T), and X3 = E F,
 // T3 = E H share E: negating E alone negates the point. That is 9 multiplies of E's limbs by +-1
 // (E is class S, symmetric, so -E is too) against ge9_madd_half's 36 selects of the entry halves
 // and of F / G.
-#ifndef ED_SIGN_FOLD
-#define ED_SIGN_FOLD 1
-#endif
-#ifndef ED_FLIP_COPY  // which of the four output products copy their operands (bit 0: X3 ... bit 3: T3)
-#define ED_FLIP_COPY 1  // X3 only: 2471 -> 2430 VALU per two loop additions (15: 2457, 0: 2674)
-#endif
 CG_HD uint32_t fe9_sign_mask(bool flip) {
   uint32_t s = flip ? ~0u : 1u;
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -448,10 +413,11 @@ CG_HD void ge9_madd_half_flip(ge9_p3& r, const ge9_p3& p, const ge9_niels& q, bo
   fe9_add(H, Bp, Ap);
   fe9_add(u, p.Z, C);
   fe9_subk(v, p.Z, C);
-  fe9_mul<true, true, (ED_FLIP_COPY & 1) != 0>(r.X, E, v);
-  fe9_mul<false, true, (ED_FLIP_COPY & 2) != 0>(r.Y, u, H);
-  fe9_mul<false, true, (ED_FLIP_COPY & 4) != 0>(r.Z, u, v);
-  if (WithT) fe9_mul<true, true, (ED_FLIP_COPY & 8) != 0>(r.T, E, H);
+  // only X3 copies its operands: the other products' operands are used twice
+  fe9_mul<true, true>(r.X, E, v);
+  fe9_mul<false, false>(r.Y, u, H);
+  fe9_mul<false, false>(r.Z, u, v);
+  if (WithT) fe9_mul<true, false>(r.T, E, H);
 }
 
 // r = (-1)^neg q as an extended point (the first entry of a ladder, added to the identity): x =

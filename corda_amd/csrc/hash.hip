@@ -200,25 +200,16 @@ __device__ __forceinline__ uint32_t tx_block_word(const uint32_t* W, int j, uint
 }
 
 // One lane per component (perm order: a wave's 64 components have the same block count), the
-// blob's bytes staged wave-cooperatively through LDS: for each 64-byte block, 17 consecutive lanes
-// load one component's 68 aligned bytes (coalesced runs instead of 64 scattered 16-byte loads per
-// instruction: round 2 moved ~4x the component bytes, profiles/r02/tx_v4), then every lane reads
-// its own 17 dwords back (stride 17: no bank conflicts).
+// blob's bytes staged wave-cooperatively through LDS (coalesced runs instead of 64 scattered 16-byte
+// loads per instruction), then every lane reads its own 17 dwords back (stride 17: no bank conflicts).
 #define TX_LDS_DW 17
-#ifndef TX_LEAVES_RING
-#define TX_LEAVES_RING 1
-#endif
 __global__ void __launch_bounds__(256) k_tx_leaves(const cg_tx* __restrict__ txs, const cg_component* __restrict__ comps,
                                                    const uint32_t* __restrict__ perm,
                                                    const uint32_t* __restrict__ ranges,
                                                    const uint32_t* __restrict__ map,
                                                    const uint8_t* __restrict__ arena, uint64_t arena_len,
                                                    uint8_t* __restrict__ status, uint8_t* __restrict__ ws) {
-#if TX_LEAVES_RING
   __shared__ uint32_t ring_lds[4][2 * 64 * TX_LDS_DW];
-#else
-  __shared__ uint32_t stage[4][64 * TX_LDS_DW];
-#endif
   __shared__ uint64_t sbase[4][64];
   const uint32_t lane = threadIdx.x & 63u, wid = threadIdx.x >> 6;
   const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -263,11 +254,7 @@ __global__ void __launch_bounds__(256) k_tx_leaves(const cg_tx* __restrict__ txs
     const uint32_t x = (uint32_t)__shfl_xor((int)mbl, o, 64);
     mbl = x > mbl ? x : mbl;
   }
-#if TX_LEAVES_RING
-  // Round 5: each 64-B sector of a component is loaded once. The 68-B window
-  // of round 3 straddled two sectors for every block, and the next block loaded the second again:
-  // 2.3x the component bytes in L1 -> L2 requests, and with every XCD's waves streaming the L2
-  // missed 79% of them (2.0x in memory-side reads, profiles/r05/tx/pmc). Now a ring of two sectors
+  // Each 64-B sector of a component is loaded once: a ring of two sectors
   // per component in LDS: block b reads sectors b and b + 1 (dwords o .. o + 16 from the first, o =
   // the component's dword offset in its sector); sector b + 2 is loaded into registers while block b
   // compresses and written over sector b's slot afterwards. Lane l loads quarter l & 3 of the
@@ -343,38 +330,6 @@ __global__ void __launch_bounds__(256) k_tx_leaves(const cg_tx* __restrict__ txs
     __builtin_amdgcn_wave_barrier();
     if (more) store_sector(blk & 1u, nx);  // sector blk + 2 over sector blk
   }
-#else
-  sbase[wid][lane] = live && inside ? (c.off & ~(uint64_t)3) : ~(uint64_t)0;
-  const uint32_t sh8 = (uint32_t)(c.off & 3) * 8u;
-  uint32_t h[8];
-  sha256_init(h);
-  uint32_t* st = stage[wid];
-  for (uint32_t blk = 0; blk < mbl; ++blk) {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the previous block's reads (and sbase) are done
-    __builtin_amdgcn_wave_barrier();
-#pragma unroll
-    for (int k = 0; k < TX_LDS_DW; ++k) {
-      const uint32_t task = lane + 64u * k, cc = task / TX_LDS_DW, d = task % TX_LDS_DW;
-      const uint64_t base = sbase[wid][cc];
-      const uint64_t addr = base + 64ull * blk + 4ull * d;
-      st[task] = base != ~(uint64_t)0 && addr + 4 <= lr ? *(const uint32_t*)(arena + addr) : 0u;
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_wave_barrier();
-    if (blk < nbl) {
-      uint32_t W[TX_LDS_DW], w[16];
-#pragma unroll
-      for (int d = 0; d < TX_LDS_DW; ++d) W[d] = st[lane * TX_LDS_DW + d];
-#pragma unroll
-      for (int j = 0; j < 16; ++j) w[j] = tx_block_word(W, j, sh8, blk, len, n, salt ? nullptr : nonce);
-      if (blk + 1 == nbl) {
-        w[14] = (uint32_t)((n * 8) >> 32);
-        w[15] = (uint32_t)(n * 8);
-      }
-      sha256_compress(h, w);
-    }
-  }
-#endif
   if (!live) return;
   if (!inside) {
 #pragma unroll

@@ -142,9 +142,7 @@ typedef EdRowTabW<ED_W, ED_K> EdTab;  // 22 x 32 affine niels = 84480 B
 // The quarter tables (keys with KEY_QUARTER_MIN_USES .. ED_DIRECT_MAX_USES - 1 items): the same
 // radix-2^6 digits in ED_QK windows per row, so 4 rows (row j = multiples of 2^{66 j} (-A)) and
 // 60 doublings per item, stored in the first 4 rows of the key's EdTab (a key has one mode).
-#ifndef ED_QK
 #define ED_QK 11
-#endif
 typedef EdRowsCfg<ED_W, ED_QK> EdQCfg;
 typedef EdRowTabW<ED_W, ED_QK> EdQTab;
 static_assert(EdQCfg::kRows <= EdCfg::kRows && EdQCfg::kMult == EdCfg::kMult, "quarter rows fit the full table");
@@ -156,28 +154,9 @@ typedef EdBTabW<ED_W, ED_K, ED_WB> EdBTab;  // 26 x 512 affine niels = 1.6 MB, c
 
 // Row-base chains are latency-bound single waves (a key's doublings are one dependent sequence);
 // beside the throughput-bound row builds they got a fraction of their SIMD's issue and ran ~4x
-// slower (profiles/r03/env_copyq). CG_CHAIN_PRIO (default 1): the chain waves raise their issue
-// priority, so a build wave on the same SIMD issues only in their stall cycles.
-#ifndef CG_CHAIN_PRIO
-#define CG_CHAIN_PRIO 1
-#endif
-__device__ __forceinline__ void chain_prio() {
-#if CG_CHAIN_PRIO
-  __builtin_amdgcn_s_setprio(3);
-#endif
-}
-
-// CG_FRONT_PRIO (A/B): the per-chunk front kernels (item build, plan, challenge hashes, ECDSA prep
-// and s^-1) raise their issue priority, so the first chunk's front is not slowed by the key-table
-// builds it shares the chip with (its ladders wait for both).
-#ifndef CG_FRONT_PRIO
-#define CG_FRONT_PRIO 0
-#endif
-__device__ __forceinline__ void front_prio() {
-#if CG_FRONT_PRIO
-  __builtin_amdgcn_s_setprio(CG_FRONT_PRIO);
-#endif
-}
+// slower (profiles/r03/env_copyq). The chain waves raise their issue priority, so a build wave on
+// the same SIMD issues only in their stall cycles.
+__device__ __forceinline__ void chain_prio() { __builtin_amdgcn_s_setprio(3); }
 
 // Per-key header: status (0 = decoded) and, for Ed25519, the canonical Abyte i2p hashes.
 struct EdKeyHdr {
@@ -214,10 +193,6 @@ union BaseSlot {
 // Items whose clear data is longer than this sort after the short ones of their class and table
 // mode (plan_sort.hip), so a wave hashes either short or long messages, never both.
 #define ITEM_LONG_MIN 1024u
-struct Plan {
-  const uint32_t* perm;    // plan position -> item index
-  const uint32_t* ranges;  // class c occupies positions [ranges[c], ranges[c + 1])
-};
 __device__ __forceinline__ int plan_class_of_curve(int curve) { return curve == 1 ? PLAN_R1 : PLAN_K1; }
 
 // Key workspace, each region n_keys long (a key is either Ed25519 or ECDSA, so the table and
@@ -323,18 +298,7 @@ struct KeyWs {
   uint32_t cap_ed, cap_ec;
   uint32_t min_ed, min_ec;
   KeyCache kc;  // the context's wide-table cache (kc.on() false: every wide key's tables are built)
-  // the counting plan (plan_sort.hip): per key its ticket in its (class, mode, short / long) group
-  // (2n), the per-chunk bucket counts and their exclusive scan by bucket rank (2n + 1 each, plus
-  // one scan partial per 16k-bucket tile), and 64 words of group counts [0, 32) / group bases [32, 64)
-  uint32_t* pl_tick;
-  uint32_t* pl_cnt;
-  uint32_t* pl_pos;
-  uint32_t* pl_tile;
-  uint32_t* pl_grp;
 };
-#define PL_TILE 16384u  // buckets per scan tile (1024 threads x 16)
-static inline size_t pl_buckets(uint32_t n_keys) { return 2 * (size_t)(n_keys ? n_keys : 1) + 1; }
-static inline size_t pl_tiles(uint32_t n_keys) { return (pl_buckets(n_keys) + PL_TILE - 1) / PL_TILE; }
 
 // How much table a key gets, from the number of items that use it in the batch (one-shot entry
 // points estimate it from a hashed 1-in-KEY_USES_SAMPLE sample of the items, plus an exact
@@ -343,12 +307,12 @@ static inline size_t pl_tiles(uint32_t n_keys) { return (pl_buckets(n_keys) + PL
 // never a verdict: both ladders compute the same point.
 //   0 uses                        decode only (Abyte, status), no rows
 //   1 .. KEY_QUARTER_MIN_USES - 1 row 0 only (the 32 affine multiples of -A): the item runs the
-//                                 252-doubling Horner ladder (ed_double_scalar_row0)
+//                                 252-doubling Horner ladder (ed_double_scalar_row0w)
 //   .. ED_DIRECT_MAX_USES - 1     quarter: 4 rows, 60 doublings per item (ed_double_scalar_fw over
 //                                 EdQTab; ECDSA: EC_QROWS rows, ecdsa_ladder_check_w). Round 4: the
 //                                 2^20-distinct-key leg (~12 uses a key) went 65 -> 90 M sigs/s
 //                                 with quarter rows instead of row 0 (profiles/r04/kd)
-//   more                          all 22 rows: 6 doublings per item (ed_double_scalar_wb)
+//   more                          all 22 rows: 6 doublings per item (ed_double_scalar_pf)
 // Break-even (measured on MI355X, 2^20 Ed25519 items): a key's full tables cost ~230 ns of
 // GPU time, the row-0 ladder ~7 ns more per item than the full-table one -> ~32 items.
 // A fourth mode, for keys with >= KEY_WIDE_MIN_USES_{ED,EC} items (and a free slot in the family's
@@ -465,15 +429,6 @@ static inline KeyWs key_ws(void* base, uint32_t n_keys, const WidePool* wp = nul
   p += al256(3 * n * sizeof(uint32_t));
   w.wide_count = (uint32_t*)p;
   p += 256;
-  w.pl_tick = (uint32_t*)p;
-  p += al256(2 * n * sizeof(uint32_t));
-  w.pl_cnt = (uint32_t*)p;
-  p += al256(pl_buckets(n_keys) * sizeof(uint32_t));
-  w.pl_pos = (uint32_t*)p;
-  p += al256(pl_buckets(n_keys) * sizeof(uint32_t));
-  w.pl_tile = (uint32_t*)p;
-  p += al256(pl_tiles(n_keys) * sizeof(uint32_t));
-  w.pl_grp = (uint32_t*)p;
   w.wed = wp ? (EdWideSlot*)wp->ed : nullptr;
   w.wec = wp ? (EcWideSlot*)wp->ec : nullptr;
   w.cap_ed = wp ? wp->cap_ed : 0;
@@ -489,8 +444,7 @@ static inline size_t key_ws_bytes(uint32_t n_keys) {
          al256(tab_park_lanes(n_keys, EdCfg::kRows) * ED_ROW_PARK_BYTES) +
          2 * al256(tab_park_lanes(n_keys, EC_ROWS) * EC_ROW_PARK_BYTES) + al256(n * sizeof(uint32_t)) +
          al256(3 * n * sizeof(uint32_t)) + 256 + 2 * al256(3 * n * sizeof(uint32_t)) + al256(n) +
-         al256(n * sizeof(uint32_t)) + al256(3 * n * sizeof(uint32_t)) + 256 + al256(2 * n * sizeof(uint32_t)) +
-         2 * al256(pl_buckets(n_keys) * sizeof(uint32_t)) + al256(pl_tiles(n_keys) * sizeof(uint32_t)) + 256;
+         al256(n * sizeof(uint32_t)) + al256(3 * n * sizeof(uint32_t)) + 256;
 }
 
 // Per-item workspace slot (indexed by plan position, so the schemes never share one):

@@ -126,10 +126,7 @@ CG_HD void f29_to_words(uint32_t w[8], const f29& a) {
 // A modulus limb as a multiply operand. A power-of-two limb (secp256r1 p: 2^18) would otherwise be
 // folded into a 64-bit shift and two masks (3 VALU, ~4 ns of issue) instead of one v_mad_u64_u32
 // (~2.4 ns): hide it in an SGPR the compiler cannot see through (SALU, off the VALU path).
-#ifndef CG_M29_OPAQUE_POW2  // 0: let the compiler fold power-of-two limbs (A/B builds)
-#define CG_M29_OPAQUE_POW2 1
-#endif
-constexpr bool m29_pow2(uint32_t v) { return CG_M29_OPAQUE_POW2 && v != 0 && (v & (v - 1)) == 0; }
+constexpr bool m29_pow2(uint32_t v) { return v != 0 && (v & (v - 1)) == 0; }
 CG_HD uint32_t m29_opaque(uint32_t v) {
 #if defined(__HIP_DEVICE_COMPILE__)
   asm volatile("" : "+s"(v));
@@ -141,10 +138,7 @@ CG_HD uint32_t m29_opaque(uint32_t v) {
 // PLAIN form (R = 1 in everything below: m29_r2 gives 1, so the "Montgomery" conversions are
 // identities) and a product is folded instead of Montgomery-reduced. The fold uses
 // 2^261 = 32 * 2^256 = 2^37 + 31264 (mod p): 81 + 11 MACs per product instead of 162.
-#ifndef CG_M29_K1_PLAIN  // 0: secp256k1 p in Montgomery form like the other moduli (A/B builds)
-#define CG_M29_K1_PLAIN 1
-#endif
-constexpr bool m29_plain(int C, int N) { return CG_M29_K1_PLAIN && C == 0 && N == 0; }
+constexpr bool m29_plain(int C, int N) { return C == 0 && N == 0; }
 
 // r = a b mod p (p = 2^256 - 2^32 - 977) for limbs < 2^30 (a b < 2^524); r reduced (< 2p). The low nine product columns stay raw 64-bit sums (no carries); the high eight
 // are product-scanned into 29-bit limbs H, folded into the low columns (H_m 31264 into column m,
@@ -215,10 +209,7 @@ CG_HD void m29_mul_k1p(f29& r, const f29& a, const f29& b) {
 // 2^96 - 1. With -p^-1 = 1 (mod 2^29) the Montgomery digit q is the column's low 29 bits, so the -q
 // term only clears bits the column shift drops: q p costs four MACs (2^9, 2^18, limbs 7 and 8)
 // instead of seven.
-#ifndef CG_M29_R1_TELESCOPE  // 0: seven MACs per digit (A/B builds)
-#define CG_M29_R1_TELESCOPE 1
-#endif
-constexpr bool m29_r1p_tel(int C, int N) { return CG_M29_R1_TELESCOPE && C == 1 && N == 0; }
+constexpr bool m29_r1p_tel(int C, int N) { return C == 1 && N == 0; }
 static_assert(m29_limb(1, 0, 1, 0) == M29_MASK && m29_limb(1, 0, 1, 1) == M29_MASK && m29_limb(1, 0, 1, 2) == M29_MASK &&
                   m29_limb(1, 0, 1, 3) == 0x1ffu && m29_limb(1, 0, 1, 4) == 0 && m29_limb(1, 0, 1, 5) == 0 &&
                   m29_limb(1, 0, 1, 6) == (1u << 18) && m29_ninv(1, 0) == 1u,
@@ -523,16 +514,13 @@ static_assert(m29_make_inv_sched(1, 1).n < 96 && m29_make_inv_sched(0, 1).n < 96
                   m29_make_inv_sched(0, 0).n < 96,
               "inversion windows fit the schedule");
 
-#ifndef CG_M29_INV_WINDOW  // 0: square-and-multiply (A/B)
-#define CG_M29_INV_WINDOW 1
-#endif
 // Windowed for the group order only (k_ec_inv's s^-1, ~1 wave per SIMD: latency-bound, registers
 // to spare); the field inversions of the table builds keep square-and-multiply, whose register
 // footprint keeps those kernels at 3 waves per SIMD (the 8-entry table took k_ec_wide_rows from 155
 // to 216 VGPRs).
 template <int C, int N>
 CG_HD void m29_inv(f29& r, const f29& a, const f29& one_m) {
-  if constexpr (CG_M29_INV_WINDOW && N == 1) {
+  if constexpr (N == 1) {
   (void)one_m;
   const M29InvSched& S = CG_M29_INV_SCHED[C][N];
   // eight named values, not an array: an array of them stayed in scratch for secp256r1

@@ -75,20 +75,11 @@ CG_HD uint32_t cg_maj32(uint32_t a, uint32_t b, uint32_t c) {
   return (a & b) | (c & (a | b));
 #endif
 }
-CG_HD uint64_t cg_xor3_64(uint64_t a, uint64_t b, uint64_t c) {
-  return ((uint64_t)cg_xor3_32((uint32_t)(a >> 32), (uint32_t)(b >> 32), (uint32_t)(c >> 32)) << 32) |
-         cg_xor3_32((uint32_t)a, (uint32_t)b, (uint32_t)c);
-}
-#ifndef CG_SHA512_BITOP3
-// 2: Maj as bitop3 (priced 3% better, round 2); 4: Ch as bitop3 (round 5: k_ed_hash 5.5 -> 5.35 ms
-// per headline step, profiles/r05/hash); the 64-bit xor3 form (1) costs more moves than it saves
-#define CG_SHA512_BITOP3 6
-#endif
-// (e & f) ^ (~e & g): one bitfield select per 32-bit half. With CG_SHA512_BITOP3 & 4 an opaque
-// bitop3 (truth table 0xCA: e ? f : g) per half: the compiler otherwise splits the disjoint OR into
-// two terms it adds into T1 separately (v_and + v_bfi + two 64-bit adds per round)
+// (e & f) ^ (~e & g): on the device an opaque bitop3 (truth table 0xCA: e ? f : g) per 32-bit half:
+// the compiler otherwise splits the disjoint OR into two terms it adds into T1 separately (v_and +
+// v_bfi + two 64-bit adds per round)
 CG_HD uint64_t cg_ch64(uint64_t e, uint64_t f, uint64_t g) {
-#if (CG_SHA512_BITOP3 & 4) && defined(__HIP_DEVICE_COMPILE__)
+#if defined(__HIP_DEVICE_COMPILE__)
   // (the builtin returns a signed int: each half goes through uint32_t before widening)
   const uint32_t hi = (uint32_t)__builtin_amdgcn_bitop3_b32((uint32_t)(e >> 32), (uint32_t)(f >> 32),
                                                             (uint32_t)(g >> 32), 0xCA);
@@ -99,21 +90,11 @@ CG_HD uint64_t cg_ch64(uint64_t e, uint64_t f, uint64_t g) {
 #endif
 }
 CG_HD uint64_t cg_maj64(uint64_t a, uint64_t b, uint64_t c) {
-#if CG_SHA512_BITOP3 & 2
   return ((uint64_t)cg_maj32((uint32_t)(a >> 32), (uint32_t)(b >> 32), (uint32_t)(c >> 32)) << 32) |
          cg_maj32((uint32_t)a, (uint32_t)b, (uint32_t)c);
-#else
-  const uint64_t m = a ^ b;
-  return (m & c) | (~m & b);
-#endif
 }
-CG_HD uint64_t cg_x3_64(uint64_t a, uint64_t b, uint64_t c) {
-#if CG_SHA512_BITOP3 & 1
-  return cg_xor3_64(a, b, c);
-#else
-  return a ^ b ^ c;
-#endif
-}
+// the 64-bit three-input XOR stays plain: halves through bitop3 cost more moves than they save
+CG_HD uint64_t cg_x3_64(uint64_t a, uint64_t b, uint64_t c) { return a ^ b ^ c; }
 
 // Round constants in constant memory: the rounds run in a rolled loop of 16 unrolled rounds
 // (sha512_compress), so the constant of round r + j is a scalar load at a uniform index.

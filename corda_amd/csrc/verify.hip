@@ -14,7 +14,6 @@ namespace cg {
 
 __global__ void k_misc_status(const cg_item* __restrict__ items, uint64_t n_items, const cg_key* __restrict__ keys,
                               uint32_t n_keys, uint8_t* __restrict__ status) {
-  front_prio();
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n_items) return;
   const uint32_t ki = items[i].key_idx;

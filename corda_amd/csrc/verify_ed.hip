@@ -8,8 +8,8 @@
 //   k_ed_ladder_pf       one lane per item of a full-table key: key status, then 2 windows x
 //                        (~21.5 rows of -A + 13 rows of the radix-2^10 B table) mixed additions,
 //                        6 doublings; each op's table entry gathered into LDS one op ahead
-//   k_ed_ladder<false>   a key with few items in the batch: row 0 of -A and 252 doublings
-//                        (keyws.h ED_DIRECT_MAX_USES)
+//   k_ed_ladder<Mode>    a key with few items in the batch: row 0 of -A and 252 doublings, or the
+//                        quarter table's 4 rows and 60 doublings (keyws.h ED_DIRECT_MAX_USES)
 //   k_ed_finish          16 items per lane: batch inversion, encode, byte compare
 // Replaces, per item, i2p EdDSAEngine.engineVerify behind Crypto.isValid
 // (core/src/main/kotlin/net/corda/core/crypto/Crypto.kt:553-559, scheme :120-133).
@@ -196,18 +196,13 @@ __device__ __forceinline__ WideLane wide_lane(uint32_t rows, uint32_t groups) {
 #ifndef ED_WIDE_ROWS_WAVES  // waves per SIMD the register allocation must allow
 #define ED_WIDE_ROWS_WAVES 2  // 3 spills 125 VGPRs
 #endif
-#ifndef ED_WIDE_ROWS_PRIO
-#define ED_WIDE_ROWS_PRIO 2
-#endif
 // ED_WIDE_ROW_LANES lanes per (wide key, row): the row's 128 multiples walked in radix 2^29, one
 // inversion, one launch (ed25519_rows.h ed_wide_row_build9)
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ED_WIDE_ROWS_WAVES))) k_ed_wide_rows(uint32_t n_keys, const EdKeyHdr* __restrict__ hdr,
                                                      const uint32_t* __restrict__ wide,
                                                      const uint32_t* __restrict__ wide_count,
                                                      const uint32_t* __restrict__ wide_idx, EdWideSlot* __restrict__ wed) {
-#if ED_WIDE_ROWS_PRIO  // (A/B) issue priority over the ECDSA row builds sharing the SIMDs
-  __builtin_amdgcn_s_setprio(ED_WIDE_ROWS_PRIO);
-#endif
+  __builtin_amdgcn_s_setprio(2);  // issue priority over the ECDSA row builds sharing the SIMDs
   const WideLane L = wide_lane(EdWideCfg::kRows, ED_WIDE_ROW_LANES);
   if (L.l >= wide_count[PLAN_ED]) return;
   const uint32_t i = wide[(size_t)PLAN_ED * n_keys + L.l];
@@ -323,12 +318,6 @@ static_assert(sizeof(EdDigitsWide) == ITEM_SLOT, "digits must fill one item slot
 #ifndef ED_HASH_WAVES_PER_SIMD
 #define ED_HASH_WAVES_PER_SIMD 4
 #endif
-#ifndef ED_HASH_STATUS_EARLY
-#define ED_HASH_STATUS_EARLY 0
-#endif
-#ifndef ED_HASH_MID_SCHEDULE
-#define ED_HASH_MID_SCHEDULE 1
-#endif
 template <bool Fused>
 __device__ __forceinline__ void ed_hash_one(uint64_t p, const cg_item* __restrict__ items,
                                             const uint32_t* __restrict__ perm, const EdKeyHdr* __restrict__ hdr,
@@ -365,7 +354,7 @@ __device__ __forceinline__ void ed_hash_one(uint64_t p, const cg_item* __restric
       // scheme in a notary batch) reads the image with scalar addresses and branches and runs block 1
       // from the template's precomputed schedule; a mixed wave takes the per-lane form.
       const uint32_t t0 = __builtin_amdgcn_readfirstlane(it.reserved1);
-      if (__builtin_amdgcn_ballot_w64(it.reserved1 != t0) == 0 && ED_HASH_MID_SCHEDULE) {
+      if (__builtin_amdgcn_ballot_w64(it.reserved1 != t0) == 0) {
         const TmplMid* m0 = (const TmplMid*)(msgs + SPLICE_HDR_BYTES) + t0;
         const uint64_t* wk1 =
             m0->ed_mid ? ((const TmplW512*)(msgs + ((const SpliceHdr*)msgs)->w512_off) + t0)->wk : nullptr;
@@ -416,10 +405,10 @@ __device__ __forceinline__ void ed_hash_one(uint64_t p, const cg_item* __restric
     for (int w = 0; w < 8; ++w) ec.r[(size_t)w * ec.n + p] = sw[w];
   }
   ec.pend[p] = st == ED_PENDING;
-  // ED_HASH_STATUS_EARLY=0 (round 6): a pending item's status byte is left as k_misc_status set it
-  // (CG_NOT_RUN) until k_ed_finish writes the verdict: nothing reads ED_PENDING, and a 1-byte store at
-  // a random position (items are in plan order here) cost the kernel a whole written-back line per item
-  if (!ED_HASH_STATUS_EARLY ? st != (uint8_t)ED_PENDING : true) status[i] = st;
+  // a pending item's status byte is left as k_misc_status set it (CG_NOT_RUN) until k_ed_finish writes
+  // the verdict: nothing reads ED_PENDING, and a 1-byte store at a random position (items are in plan
+  // order here) cost the kernel a whole written-back line per item
+  if (st != (uint8_t)ED_PENDING) status[i] = st;
 }
 
 template <bool Fused>  // Fused: every item's message is a SignableData splice (the tx-signature paths)
@@ -428,7 +417,6 @@ __global__ void __launch_bounds__(256, ED_HASH_WAVES_PER_SIMD) k_ed_hash(
     const EdKeyHdr* __restrict__ hdr, const uint8_t* __restrict__ arena, uint64_t arena_len,
     const uint8_t* __restrict__ msgs, uint64_t msgs_len, uint32_t mode, uint8_t* __restrict__ status,
     EdDigits* __restrict__ dig, EdCols ec) {
-  front_prio();
   const uint32_t beg = ranges[PLAN_ED], wbeg = ranges[PLAN_WIDE + PLAN_ED];
   for (Walk w = walk_units(ranges[PLAN_ED + 1] - beg); w.u < w.end; w.u += w.step)
     ed_hash_one<Fused>(beg + w.u, items, perm, hdr, arena, arena_len, msgs, msgs_len, mode, status, dig,
@@ -462,12 +450,7 @@ struct EdOps {
   static constexpr int kOps = kNa1 + kNa0 + EdWideCfg::kBDigits;
   static constexpr uint32_t kWaveBytes = 64 * sizeof(ge_niels);
 };
-#ifndef ED_LADDER_PF  // -DED_LADDER_PF=0: the unpipelined full-table ladder (A/B; any ED_K)
-#define ED_LADDER_PF 1
-#endif
-#if ED_LADDER_PF
 static_assert(ED_K == 2, "the flat op sequence is written for 2 windows");
-#endif
 static_assert(sizeof(ge_niels) == 120, "LDS chunking assumes 120-B niels entries");
 
 // op o -> (digit word index in EdDigits, shift, B?, row)
@@ -527,7 +510,6 @@ __device__ __forceinline__ const ge_niels* ed_op_src(const EdTab& TA, int row, i
 
 // The 55 A additions in radix 2^25.5 (full-table entries), then the 12 B additions in radix 2^29
 // (fe9.h, the wide B table's entry form), one entry gathered into LDS one op ahead throughout.
-#if ED_LADDER_PF
 __device__ __forceinline__ void ed_double_scalar_pf(ge_p2& out, const uint32_t* __restrict__ dw, const EdTab& TA,
                                                     const EdBWideTab& TB, uint8_t* wave_lds, uint32_t lane) {
   constexpr int N = EdOps::kOps, NA = EdOps::kNa1 + EdOps::kNa0;
@@ -593,16 +575,11 @@ __device__ __forceinline__ void ed_double_scalar_pf(ge_p2& out, const uint32_t* 
   ge9_to_p2(out, R9);
 }
 
-#endif
-// A/B on one box (gpurun_out/ab_sw1, profiles/r01/ed25519_v9): the pipelined ladder at 2
-// waves/SIMD (216 VGPRs, no scratch) against k_ed_ladder<true> at 3 waves/SIMD (168 VGPRs,
-// digits and spills in scratch): item kernels 4.24 vs 4.28 ms per 2^20 items. The gain is
-// small because the ladder is VALU-issue-bound, not latency-bound.
-// -DED_LADDER_PF=0 builds the unpipelined ladder for A/B runs (tools/ab.sh).
+// The pipelined ladder runs at 2 waves/SIMD (216 VGPRs, no scratch). The ladder is VALU-issue-bound,
+// not latency-bound.
 #ifndef ED_LADDER_PF_WAVES
 #define ED_LADDER_PF_WAVES 2
 #endif
-#if ED_LADDER_PF
 __global__ void __launch_bounds__(256, ED_LADDER_PF_WAVES) k_ed_ladder_pf(
     const cg_item* __restrict__ items, const uint32_t* __restrict__ perm, const uint32_t* __restrict__ ranges,
     const EdKeyHdr* __restrict__ hdr, const TabSlot* __restrict__ tabs, const EdBWideTab* __restrict__ btab,
@@ -627,7 +604,7 @@ __global__ void __launch_bounds__(256, ED_LADDER_PF_WAVES) k_ed_ladder_pf(
     ((ge_p2*)slots)[p] = q;
   }
 }
-#endif
+
 // ---------------------------------------------------------------- wide-table ladder
 // ed_double_scalar_wide as a flat sequence of 54 signed mixed additions (32 rows of the key's
 // wide table, then the 22 radix-2^12 B rows), no doublings; each op's entry gathered into LDS
@@ -687,33 +664,25 @@ __device__ __forceinline__ void ed_double_scalar_wide_pf(ge_p2& out, const uint3
       w_next = dw[widx];
     }
   };
-  // after next(o, ...), d_cur is op o + 1's digit: ED_SIGN_FOLD flips op o's output by the sign
+  // after next(o, ...), d_cur is op o + 1's digit: op o's output is flipped by the sign
   // change s_o s_{o+1} (fe9.h ge9_madd_half_flip), the last op's by s_{N-1}
   {  // op 0: identity + q0 (fe9.h ge9_from_niels_half: one product instead of an addition's seven)
     ge9_niels n;
     bool neg;
     next(0, n, neg);
-    ge9_from_niels_half(R, n, ED_SIGN_FOLD ? neg != (d_cur < 0) : neg);
+    ge9_from_niels_half(R, n, neg != (d_cur < 0));
   }
   for (int o = 1; o + 1 < N; ++o) {
     ge9_niels n;
     bool neg;
     next(o, n, neg);
-#if ED_SIGN_FOLD
     ge9_madd_half_flip<true>(R, R, n, neg != (d_cur < 0));
-#else
-    ge9_madd_half<true>(R, R, n, neg);
-#endif
   }
   {  // the last addition: projective output
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     ge9_niels n;
     ed_lds_niels9(n, wave_lds, lane);
-#if ED_SIGN_FOLD
     ge9_madd_half_flip<false>(R, R, n, d_cur < 0);
-#else
-    ge9_madd_half<false>(R, R, n, d_cur < 0);
-#endif
   }
   ge9_to_p2(out, R);
 }
@@ -755,19 +724,16 @@ __global__ void __launch_bounds__(256, ED_LADDER_WIDE_WAVES) k_ed_ladder_wide(
 // projective in the item slot.
 // One launch over the Ed25519 range per table mode (the plan keeps the modes in separate waves);
 // separate kernels keep each ladder's registers free of the others'. Mode: PLAN_MODE_ROW0 /
-// PLAN_MODE_QUART / PLAN_MODE_FULL (keyws.h).
+// PLAN_MODE_QUART (keyws.h); the full-table keys' items run k_ed_ladder_pf.
 template <int Mode>
 __global__ void __launch_bounds__(256, ED_LADDER_WAVES_PER_SIMD) k_ed_ladder(
     const cg_item* __restrict__ items, const uint32_t* __restrict__ perm, const uint32_t* __restrict__ ranges,
     const EdKeyHdr* __restrict__ hdr, const TabSlot* __restrict__ tabs, const EdBWideTab* __restrict__ btab,
     uint8_t* __restrict__ status, void* __restrict__ slots, EdCols ec) {
-  // the plan's mode split: row-0 keys' items, quarter-table keys', full-table keys' (plan_sort.hip)
-  const uint32_t beg = Mode == PLAN_MODE_FULL    ? ranges[PLAN_FULL + PLAN_ED]
-                     : Mode == PLAN_MODE_QUART ? ranges[PLAN_QUART + PLAN_ED]
-                                               : ranges[PLAN_ED];
-  const uint32_t end = Mode == PLAN_MODE_FULL    ? ranges[PLAN_WIDE + PLAN_ED]
-                     : Mode == PLAN_MODE_QUART ? ranges[PLAN_FULL + PLAN_ED]
-                                               : ranges[PLAN_QUART + PLAN_ED];
+  // the plan's mode split: row-0 keys' items, then quarter-table keys' (plan_sort.hip)
+  static_assert(Mode == PLAN_MODE_ROW0 || Mode == PLAN_MODE_QUART, "row-0 and quarter tables");
+  const uint32_t beg = Mode == PLAN_MODE_QUART ? ranges[PLAN_QUART + PLAN_ED] : ranges[PLAN_ED];
+  const uint32_t end = Mode == PLAN_MODE_QUART ? ranges[PLAN_FULL + PLAN_ED] : ranges[PLAN_QUART + PLAN_ED];
   for (Walk w = walk_units(end - beg); w.u < w.end; w.u += w.step) {
     const uint64_t p = beg + w.u;
     const uint32_t key = ec.key[p];
@@ -779,9 +745,7 @@ __global__ void __launch_bounds__(256, ED_LADDER_WAVES_PER_SIMD) k_ed_ladder(
     if (!ec.pend[p]) continue;
     const EdDigits d = ((const EdDigits*)slots)[p];
     ge_p2 q;
-    if (Mode == PLAN_MODE_FULL) {
-      ed_double_scalar_fw<ED_W, ED_K>(q, d.eh, d.es, tabs[key].ed, *btab, PickGlobal(), PickGlobal());
-    } else if (Mode == PLAN_MODE_QUART) {  // the first rows of the table, 2^{66 j} (-A) (keyws.h)
+    if (Mode == PLAN_MODE_QUART) {  // the first rows of the table, 2^{66 j} (-A) (keyws.h)
       ed_double_scalar_fw<ED_W, ED_QK>(q, d.eh, d.es, *(const EdQTab*)&tabs[key].ed, *btab, PickGlobal(),
                                        PickGlobal());
     } else {  // a key with few items: row 0 only (keyws.h)
@@ -914,17 +878,11 @@ void ed_launch_front(const cg_item* d_items, uint64_t n_items, const uint8_t* d_
 void ed_launch_ladder(bool full, const cg_item* d_items, uint64_t n_items, uint8_t* d_status, const KeyWs& w,
                       const ItemWs& iw, const void* d_btab, hipStream_t stream) {
   const uint32_t B = 256;
-  const unsigned grid = walk_grid(n_items, B, WALK_CAP(full && ED_LADDER_PF ? ED_LADDER_PF_WAVES : ED_LADDER_WAVES_PER_SIMD));
+  const unsigned grid = walk_grid(n_items, B, WALK_CAP(full ? ED_LADDER_PF_WAVES : ED_LADDER_WAVES_PER_SIMD));
   // full: the full-table ladder; else the row-0 then the quarter-table one (the side streams)
-#if ED_LADDER_PF
-  if (full)
+  if (full) {
     hipLaunchKernelGGL(k_ed_ladder_pf, dim3(grid), dim3(B), 0, stream, d_items, iw.perm, iw.ranges, w.hdr,
                        w.tab, bwide(d_btab), d_status, iw.slots, iw.ed);
-  else
-#endif
-  if (full) {
-    hipLaunchKernelGGL(k_ed_ladder<PLAN_MODE_FULL>, dim3(grid), dim3(B), 0, stream, d_items, iw.perm, iw.ranges,
-                       w.hdr, w.tab, bwide(d_btab), d_status, iw.slots, iw.ed);
   } else {
     hipLaunchKernelGGL(k_ed_ladder<PLAN_MODE_ROW0>, dim3(grid), dim3(B), 0, stream, d_items, iw.perm, iw.ranges,
                        w.hdr, w.tab, bwide(d_btab), d_status, iw.slots, iw.ed);

@@ -67,5 +67,5 @@ def test_makefile_lists_every_header_the_library_includes():
     assert flags(tmk) == flags(mk)
     assert re.search(r"^\$\(OUT\):.*rsa_wave_gpu\.hip.*corda_amd/csrc/rsa_wave\.h", tmk, re.M)
     # the radix builds: each variant object of each radix-dependent source
-    assert set(_make_var(mk, "VARIANT_SRCS")) == {"verify", "verify_ed", "verify_ec", "plan_sort"}
+    assert set(_make_var(mk, "VARIANT_SRCS")) == {"verify", "verify_ed", "verify_ec", "plan_sort", "sign_ed"}
     assert set(_make_var(mk, "VARIANTS")) == {"24", "22"}

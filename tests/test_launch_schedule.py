@@ -75,7 +75,6 @@ def stages():
 #   bases.<f> tab.<f> park.<f>   row bases, row tables and the builds' park, of family f's keys
 #   wslot.<f>           the wide-pool slots of family f's keys (the ECDSA pool is split by key)
 #   kc.index kc.own.<f> kc.ctr   the wide-table cache: index, owners / live / free list, counters
-#   plan_ws             the plan's bucket counters in the key workspace (pl_*)
 #   h<h>.perm .sort .slots.<f>.<m> .edcols.<m>   item workspace h: perm and ranges, the sort
 #                       buffers, the per-item slots and the Ed25519 columns (both by plan position,
 #                       so a family's and a mode's items never share one)
@@ -97,7 +96,7 @@ def _fam_rows(name, f):
                       f"hdr.status.{f} bases.{f} list.row0.{f} list.full.{f} list.quart.{f} park.{f}",
                       f"tab.{f} park.{f}", ""),
         "row0_ladder": (f"k_{k}_ladder<ROW0> k_{k}_ladder<QUART>", f"tab.{f}", "", ""),
-        "full_ladder": (f"k_{k}_ladder<FULL>" + ("" if ec else " k_ed_ladder_pf"), f"tab.{f}", "", ""),
+        "full_ladder": (f"k_ec_ladder<FULL>" if ec else "k_ed_ladder_pf", f"tab.{f}", "", ""),
         "wide_ladder": (f"k_{k}_ladder_wide", f"wide_idx wslot.{f}", "", ""),
     }
     kern, r, w, a = rows[name]
@@ -122,8 +121,8 @@ ACCESS = {
                  "wide_idx kc.own.{f} list.wide.{f} list.full.{f} list.row0.{f}", "skip_word kc.ctr"),
     "ed_abyte": ("k_ed_key_abyte", "keys arena.keys", "hdr.abyte", ""),
     "misc_status": ("k_misc_status", "items.c{c} keys", "st.c{c}.{f}.{m} st.c{c}.other", ""),
-    "plan": ("launch_plan (k_plan_*, the radix sort)", "items.c{c} keys uses wide_idx plan_ws h{h}.sort",
-             "plan_ws h{h}.sort h{h}.perm", ""),
+    "plan": ("launch_plan (k_plan_*, the radix sort)", "items.c{c} keys uses wide_idx h{h}.sort",
+             "h{h}.sort h{h}.perm", ""),
     "ed_front": ("k_ed_hash", "items.c{c} h{h}.perm hdr.abyte arena.c{c} msgs.c{c} st.c{c}.ed.{m}",
                  "st.c{c}.ed.{m} h{h}.slots.ed.{m} h{h}.edcols.{m}", ""),
     "ed_finish": ("k_ed_finish", "h{h}.perm h{h}.slots.ed.{m} h{h}.edcols.{m} st.c{c}.ed.{m}", "st.c{c}.ed.{m}", ""),
