@@ -199,6 +199,21 @@ def lib():
                     L.cg_pool_sign_tx_ids.argtypes = [vp, vp, u64, vp, u64, vp, u32, vp, u64, vp, vp,
                                                       ctypes.POINTER(cg_pool_stats)]
                     L.cg_pool_sign_tx_ids.restype = i32
+            if hasattr(L, "cg_derive_keys"):  # older builds (A/B variants) lack key derivation
+                L.cg_derive_keys.argtypes = [vp, vp, u32, vp, u64, vp, u64, vp, vp, vp, vp]
+                L.cg_derive_keys.restype = i32
+                L.cg_derive_keys_device.argtypes = [vp, vp, u32, vp, u64, vp, u64, vp, vp, vp, vp, vp]
+                L.cg_derive_keys_device.restype = i32
+                L.cg_public_keys.argtypes = [vp, u32, vp, u64, vp, vp]
+                L.cg_public_keys.restype = i32
+                L.cg_public_keys_device.argtypes = [vp, u32, vp, u64, vp, vp, vp]
+                L.cg_public_keys_device.restype = i32
+                if pool:
+                    L.cg_pool_derive_keys.argtypes = [vp, vp, u32, vp, u64, vp, u64, vp, vp, vp, vp,
+                                                      ctypes.POINTER(cg_pool_stats)]
+                    L.cg_pool_derive_keys.restype = i32
+                    L.cg_pool_public_keys.argtypes = [vp, u32, vp, u64, vp, vp, ctypes.POINTER(cg_pool_stats)]
+                    L.cg_pool_public_keys.restype = i32
             if hasattr(L, "cg_rsa_key_bits"):  # older builds (A/B variants) lack the RSA path
                 L.cg_rsa_key_bits.argtypes = [ctypes.c_char_p, u32]
                 L.cg_rsa_key_bits.restype = u32

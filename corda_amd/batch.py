@@ -28,6 +28,12 @@ assert TXSIG12_DTYPE.itemsize == 12
 SIGN_REQ_DTYPE = np.dtype([("tx_idx", "<u4"), ("signer", "<u2"), ("tmpl", "<u2")])
 SIGN_ITEM_DTYPE = np.dtype([("msg_off", "<u8"), ("msg_len", "<u4"), ("signer", "<u4")])
 assert SIGN_REQ_DTYPE.itemsize == 8 and SIGN_ITEM_DTYPE.itemsize == 16
+# key derivation (cg_derive_parent / cg_derive_req)
+DERIVE_PARENT_DTYPE = np.dtype([("key_off", "<u8"), ("key_len", "<u2"), ("scheme", "u1"), ("pad", "u1", (5,))])
+DERIVE_REQ_DTYPE = np.dtype([("seed_off", "<u8"), ("seed_len", "<u4"), ("parent", "<u4")])
+assert DERIVE_PARENT_DTYPE.itemsize == 16 and DERIVE_REQ_DTYPE.itemsize == 16
+DERIVE_HOST, DERIVE_BAD_PARENT, KEY_REJECTED = 6, 7, 8  # CG_DERIVE_HOST, CG_DERIVE_BAD_PARENT, CG_KEY_REJECTED
+DERIVE_MAX_RETRIES = 4
 # tear-offs (cg_pmt_node / cg_filtered_leaf / cg_filtered_tx)
 PMT_NODE_DTYPE = np.dtype([("hash_off", "<u8"), ("kind", "<u4"), ("reserved", "<u4")])
 FLEAF_DTYPE = np.dtype([("off", "<u8"), ("nonce_off", "<u8"), ("len", "<u4"), ("flags", "<u4")])
@@ -471,3 +477,66 @@ class RequirementBuilder:
             for j, c in enumerate(k.children):
                 fill(first + j, c.node, c.weight)
         return np.array(self._reqs, dtype=np.uint32), nodes
+
+
+class DeriveRequests:
+    """cg_derive_keys input: ``parents`` (DERIVE_PARENT_DTYPE: keyData in the arena, the scheme),
+    ``reqs`` (DERIVE_REQ_DTYPE: the seed in the arena, the parent's index), ``arena`` (uint8). The
+    arena holds private key material: ``wipe()`` zeroes it."""
+
+    def __init__(self, parents, reqs, arena):
+        self.parents, self.reqs, self.arena = parents, reqs, arena
+
+    @property
+    def n(self):
+        return len(self.reqs)
+
+    def wipe(self):
+        self.arena[:] = 0
+
+
+class DeriveRequestBuilder:
+    """Packs Crypto.deriveKeyPair(privateKey, seed) requests: one parent per private key, its keyData
+    formed here as deriveHMAC forms it (corda_amd/derive.py key_data), then one 16-byte request per
+    seed."""
+
+    def __init__(self):
+        self._arena = bytearray()
+        self._parents, self._reqs = [], []
+
+    def _put(self, data):
+        off = len(self._arena)
+        self._arena += data
+        return off
+
+    def parent_key_data(self, scheme, key):
+        """A parent by the HMAC key bytes themselves."""
+        key = bytes(key)
+        if len(key) > 0xFFFF:
+            raise ValueError("keyData longer than the 16-bit cg_derive_parent.key_len")
+        self._parents.append((self._put(key), len(key), scheme))
+        return len(self._parents) - 1
+
+    def parent(self, scheme, encoded):
+        """A parent by its private key: the 32-byte Ed25519 seed or the 32-byte big-endian ECDSA d."""
+        from .derive import key_data
+        return self.parent_key_data(scheme, key_data(scheme, encoded))
+
+    def add_request(self, parent, seed):
+        seed = bytes(seed)
+        check_msg_len(seed)
+        self._reqs.append((self._put(seed), len(seed), parent))
+        return len(self._reqs) - 1
+
+    def build(self):
+        parents = np.zeros(len(self._parents), dtype=DERIVE_PARENT_DTYPE)
+        for i, (off, ln, scheme) in enumerate(self._parents):
+            parents[i]["key_off"], parents[i]["key_len"], parents[i]["scheme"] = off, ln, scheme
+        reqs = np.zeros(len(self._reqs), dtype=DERIVE_REQ_DTYPE)
+        if self._reqs:
+            arr = np.array(self._reqs, dtype=np.uint64)
+            reqs["seed_off"], reqs["seed_len"], reqs["parent"] = arr[:, 0], arr[:, 1], arr[:, 2]
+        arena = np.frombuffer(self._arena, dtype=np.uint8).copy() if self._arena else np.zeros(0, np.uint8)
+        for k in range(len(self._arena)):
+            self._arena[k] = 0
+        return DeriveRequests(parents, reqs, arena)

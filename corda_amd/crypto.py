@@ -45,6 +45,18 @@ Signing (Crypto.kt:395-402, :415-422), EDDSA_ED25519_SHA512 only, on the GPU:
   there is no host ECDSA / RSA signer in this mirror (BC draws k and the PSS salt at random, so there is
   nothing bit-exact to reproduce; a JVM caller keeps its own Crypto.doSign for them).
 
+Key derivation (Crypto.kt:646-771), all three curves, on the GPU:
+  * ``Crypto.derive_key_pair(private_key, seed, scheme=None)`` -- deriveKeyPair: a scheme that is not
+    supported -> IllegalArgumentException; RSA / SPHINCS -> UnsupportedOperationException; returns the
+    KeyPair the JVM returns, byte for byte (ECDSA public keys as raw X || Y).
+  * ``Crypto.derive_key_pairs(private_key, seeds)`` -- the batch form: one key pair per seed in one call
+    (a confidential identity per transaction). An item the device hands back with DERIVE_HOST (more than
+    4 rehashes) is finished by corda_amd/derive.py.
+  * ``Crypto.derive_key_pair_from_entropy(entropy)`` -- deriveKeyPairFromEntropy (Ed25519 only).
+  * ``Crypto.generate_key_pair(scheme)`` -- generateKeyPair for the three curves: the host draws the
+    randomness (``secrets``), the device applies the accept rule and computes the public key; a refused
+    ECDSA candidate is redrawn.
+
 Public keys are ``PublicKey(scheme, encoded, fmt)`` (fmt: raw / SPKI / SEC1), the byte forms a JVM
 caller hands over JNI; two PublicKeys are equal when their X.509 encodings are (as JVM keys are),
 and ``CompositeKey`` (corda_amd/composite.py) is a PublicKey too.
@@ -115,7 +127,8 @@ class PublicKey:
 @dataclass(frozen=True, eq=False)
 class PrivateKey:
     """A private key as the node's key store holds it. EDDSA_ED25519_SHA512: ``encoded`` is the 32-byte
-    seed of EdDSAPrivateKeySpec(seed)."""
+    seed of EdDSAPrivateKeySpec(seed). ECDSA_SECP256R1_SHA256 / ECDSA_SECP256K1_SHA256: ``encoded`` is the
+    32-byte big-endian d of the BC EC private key."""
     scheme: int
     encoded: bytes
 
@@ -458,6 +471,88 @@ class _Crypto:
         for s in st:
             self._sign_status(int(s))
         return [TransactionSignature(sigs[j].tobytes(), key_pair.public, pv, sid) for j in range(len(tx_ids))]
+
+    # ------------------------------------------------------------------ key derivation
+    @staticmethod
+    def _derive_scheme(scheme):
+        """deriveKeyPair's checks in its order (Crypto.kt:647-653)."""
+        if scheme not in SCHEME_CODE_NAMES or scheme == COMPOSITE_KEY:
+            raise IllegalArgumentException(f"Unsupported key/algorithm for schemeCodeName: {scheme}")
+        if scheme not in GPU_SCHEMES:
+            raise UnsupportedOperationException(
+                "Although supported for signing, deterministic key derivation is not currently implemented for "
+                f"{SCHEME_CODE_NAMES[scheme]}")
+
+    @staticmethod
+    def _key_pair(scheme, secret, pub):
+        return KeyPair(PublicKey(scheme, pub[:32] if scheme == EDDSA_ED25519_SHA512 else pub, B.KEY_RAW),
+                       PrivateKey(scheme, secret))
+
+    def derive_key_pairs(self, private_key, seeds, scheme=None):
+        """Crypto.deriveKeyPair(privateKey, seed) for every seed in one call (cg_derive_keys)."""
+        from . import derive as D
+        scheme = private_key.scheme if scheme is None else scheme
+        self._derive_scheme(scheme)
+        if len(private_key.encoded) != 32:
+            raise InvalidKeyException("a private key is 32 bytes: an Ed25519 seed, or an ECDSA d big-endian")
+        seeds = [bytes(s) for s in seeds]
+        if not seeds:
+            return []
+        b = B.DeriveRequestBuilder()
+        parent = b.parent(scheme, private_key.encoded)
+        for s in seeds:
+            b.add_request(parent, s)
+        dr = b.build()
+        try:
+            secrets, pubs, st, _ = self.engine().derive_keys(dr)
+        finally:
+            dr.wipe()
+        out = []
+        for j, s in enumerate(seeds):
+            if st[j] == 0:
+                out.append(self._key_pair(scheme, secrets[j].tobytes(), pubs[j].tobytes()))
+            elif st[j] == B.DERIVE_HOST:
+                d, q, _ = D.derive_ecdsa(scheme, D.key_data(scheme, private_key.encoded), s)
+                out.append(self._key_pair(scheme, d, q))
+            else:
+                raise RuntimeError(f"key not derived (status {int(st[j])})")
+        return out
+
+    def derive_key_pair(self, private_key, seed, scheme=None):
+        """Crypto.deriveKeyPair(signatureScheme, privateKey, seed) (Crypto.kt:646-654)."""
+        return self.derive_key_pairs(private_key, [seed], scheme)[0]
+
+    def _public(self, scheme, secret):
+        pubs, st = self.engine().public_keys(scheme, [secret])
+        return int(st[0]), pubs[0].tobytes()
+
+    def derive_key_pair_from_entropy(self, entropy, scheme=EDDSA_ED25519_SHA512):
+        """Crypto.deriveKeyPairFromEntropy (Crypto.kt:738-757): the seed is entropy.toByteArray() padded
+        with zeros (or cut) to 32 bytes."""
+        if scheme != EDDSA_ED25519_SHA512:
+            raise IllegalArgumentException("Unsupported signature scheme for fixed entropy-based key pair generation: "
+                                           f"{SCHEME_CODE_NAMES.get(scheme, scheme)}")
+        n = int(entropy)
+        tb = n.to_bytes((n.bit_length() + 8) // 8 if n >= 0 else ((-n - 1).bit_length() + 8) // 8, "big", signed=True)
+        seed = (tb + bytes(32))[:32]
+        st, pub = self._public(scheme, seed)
+        if st != 0:
+            raise RuntimeError(f"public key not computed (status {st})")
+        return self._key_pair(scheme, seed, pub)
+
+    def generate_key_pair(self, scheme=EDDSA_ED25519_SHA512):
+        """Crypto.generateKeyPair for the three curves: 32 (Ed25519) or 256 bits (BC ECKeyPairGenerator's
+        BigInteger(nBitLength, random)) drawn on the host; an ECDSA candidate the accept rule refuses is
+        redrawn, as BC's loop does."""
+        import secrets as _secrets
+        self._derive_scheme(scheme)
+        while True:
+            secret = _secrets.token_bytes(32)
+            st, pub = self._public(scheme, secret)
+            if st == 0:
+                return self._key_pair(scheme, secret, pub)
+            if st != B.KEY_REJECTED:
+                raise RuntimeError(f"public key not computed (status {st})")
 
     def do_verify_tx(self, tx_id, ts):
         """Crypto.doVerify(txId, transactionSignature) (Crypto.kt:499-502)."""

@@ -184,6 +184,11 @@ struct cg_ctx : cg::CallState<HipStreams> {
   // allocates neither. signws: a chunk's r column and digit slots, zeroed behind every sign call.
   DevBuf signers, signws;
   uint32_t n_signers = 0;
+  // Key derivation (derive_keys.hip): the parents' HMAC midstates and a chunk's slots (d, the digits),
+  // zeroed behind every derive call. derive_force: CG_TEST_DERIVE_FORCE_RETRIES (tests only), the ECDSA
+  // accept rule refuses the first that many attempts of every item.
+  DevBuf derivews;
+  uint32_t derive_force = 0;
   // host-buffer verify: one event per pipeline chunk (seg); timing events for cg_stats (tev)
   // a second stream on a hardware queue of its own, idle in every schedule: the CG_HOST_TRACE marker
   // "tables built" waits there (launch_chunked)
@@ -798,6 +803,7 @@ int cg_open(cg_ctx** out, const cg_config* cfg) {
   c->kc_on = !(cfg && (cfg->flags & CG_FLAG_NO_KEY_CACHE)) && env_flag("CG_KEY_CACHE", true);
   c->wide_slots_max = (uint32_t)std::min<uint64_t>(env_u64("CG_TEST_WIDE_SLOTS", cg::kKeyWideMax), cg::kKeyWideMax);
   c->kc_bits = (uint32_t)std::min<uint64_t>(env_u64("CG_TEST_KEY_CACHE_BITS", 32), 32);
+  c->derive_force = (uint32_t)std::min<uint64_t>(env_u64("CG_TEST_DERIVE_FORCE_RETRIES", 0), CG_DERIVE_MAX_RETRIES + 1);
   hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
   if (e != hipSuccess) {
     delete c;
@@ -874,6 +880,7 @@ void cg_close(cg_ctx* c) {
   if (c->stream) hipStreamSynchronize(c->stream);
   signers_drop(c);
   c->signws.release();
+  c->derivews.release();
   c->keyprep.release();
   c->itemws.release();
   c->wide.release();
@@ -2261,6 +2268,157 @@ int cg_sign_batch(cg_ctx* c, const cg_sign_item* items, uint64_t n, const uint8_
   return sign_host("cg_sign_batch", c, {items, n, false, nullptr, 0, nullptr, 0, arena, arena_len, sigs_out, status_out});
 }
 
+// ---------------------------------------------------------------- key derivation (derive_keys.hip)
+static_assert(sizeof(cg_derive_parent) == 16 && sizeof(cg_derive_req) == 16, "derive request layouts");
+
+// One derive call (reqs != null) or public-key call (reqs == null: `secrets` is the input, of `scheme`):
+// the caller's tables, all in host memory or all in HBM.
+struct DeriveReq {
+  const cg_derive_parent* parents;
+  uint32_t n_parents;
+  const cg_derive_req* reqs;
+  uint64_t n;
+  const uint8_t* arena;
+  uint64_t arena_len;
+  uint8_t scheme;
+  uint8_t* secrets;
+  uint8_t* pubs;
+  uint8_t* status;
+  uint8_t* retries;  // optional
+  bool derives() const { return reqs != nullptr; }
+};
+
+static int derive_args(const char* fn, cg_ctx* c, const DeriveReq& q, bool derives, bool host) {
+  if (!c) return fail(CG_ERR_ARG, "%s: ctx is NULL", fn);
+  if (q.n && (!q.secrets || !q.pubs || !q.status)) return fail(CG_ERR_ARG, "%s: NULL secret / public key / status buffer", fn);
+  if (derives) {
+    if (q.n && !q.reqs) return fail(CG_ERR_ARG, "%s: requests is NULL", fn);
+    if (q.n_parents && !q.parents) return fail(CG_ERR_ARG, "%s: parents is NULL", fn);
+    if (host && q.arena_len && !q.arena) return fail(CG_ERR_ARG, "%s: arena is NULL", fn);
+  } else if (q.scheme != CG_EDDSA_ED25519_SHA512 && q.scheme != CG_ECDSA_SECP256K1_SHA256 &&
+             q.scheme != CG_ECDSA_SECP256R1_SHA256) {
+    return fail(CG_ERR_ARG, "%s: this scheme has no key derivation (Crypto.deriveKeyPair: UnsupportedOperationException)", fn);
+  }
+  return CG_OK;
+}
+
+// Every launch of the call over the device tables `d` on `s`: the parents' midstates, then each chunk of
+// at most the context's chunk items over the one workspace, which is zeroed behind the last kernel
+// whatever happened before (it holds the midstates and the last chunk's d and digits).
+static hipError_t launch_derive_call(cg_ctx* c, const DeriveReq& d, hipStream_t s) {
+  const uint64_t per = chunk_of(c, d.n);
+  cg::DeriveArgs a = {d.parents, d.n_parents, d.reqs,    per,      d.arena,  d.arena_len,   d.scheme,
+                      c->derive_force, d.secrets, d.pubs, d.status, d.retries, c->derivews.p, c->btab};
+  hipError_t e = d.derives() ? c->eng->launch_derive_parents(a, s) : hipSuccess;
+  const std::vector<uint64_t> bounds = cg::equal_bounds(d.n, per);
+  for (size_t k = 0; e == hipSuccess && k + 1 < bounds.size(); ++k) {
+    const uint64_t first = bounds[k];
+    a.n = bounds[k + 1] - first;
+    a.d_reqs = d.reqs ? d.reqs + first : nullptr;
+    a.d_secrets = d.secrets + 32 * first;
+    a.d_pubs = d.pubs + 64 * first;
+    a.d_status = d.status + first;
+    a.d_retries = d.retries ? d.retries + first : nullptr;
+    e = c->eng->launch_derive(a, s);
+  }
+  const hipError_t z = hipMemsetAsync(c->derivews.p, 0, c->eng->derive_ws_bytes(d.n_parents, per), s);
+  return e != hipSuccess ? e : z;
+}
+
+static hipError_t ensure_derive_ws(cg_ctx* c, const DeriveReq& q) {
+  return ensure_all({{&c->derivews, c->eng->derive_ws_bytes(q.n_parents, chunk_of(c, q.n))}});
+}
+
+static int derive_device(const char* fn, cg_ctx* c, const DeriveReq& d, bool derives, void* hip_stream) {
+  if (const int a = derive_args(fn, c, d, derives, false)) return a;
+  if (d.n == 0) return CG_OK;
+  std::lock_guard<std::mutex> g(c->mu);
+  if (const int rc = enter(c, fn)) return rc;
+  HIP_TRY(ensure_derive_ws(c, d), "hipMalloc(derive workspace)");
+  Call call(c, Call::kDevice);
+  HIP_TRY(call.open(hip_stream), "hipStreamWaitEvent");
+  HIP_TRY(launch_derive_call(c, d, call.stream()), "launch_derive");
+  HIP_TRY(call.close(), "hipEventRecord");
+  return CG_OK;
+}
+
+// A host-buffer call with the ctx lock held. Staged on the device: the parents (keys), the requests
+// (items), the arena with the parents' key bytes, and [secrets 32 n][pubs 64 n][retries n] (aux0). The
+// staged arena and secrets are zeroed on the stream behind the copies back: no key byte stays in HBM.
+static int derive_host_locked(const char* fn, cg_ctx* c, const DeriveReq& h) {
+  if (const int rc = enter(c, fn)) return rc;
+  HIP_TRY(ensure_derive_ws(c, h), "hipMalloc(derive workspace)");
+  hipStream_t s = c->stream;
+  Call call(c, Call::kHost);
+  HIP_TRY(call.open(), "hipStreamWaitEvent");
+  DeriveReq d = h;
+  HIP_TRY(c->aux0.ensure(97 * h.n), "hipMalloc(derived keys)");
+  HIP_TRY(c->status.ensure(h.n), "hipMalloc(status)");
+  d.secrets = (uint8_t*)c->aux0.p;
+  d.pubs = d.secrets + 32 * h.n;
+  d.retries = h.retries ? d.pubs + 64 * h.n : nullptr;
+  d.status = (uint8_t*)c->status.p;
+  if (h.derives()) {
+    HIP_TRY(stage(c->keys, h.parents, sizeof(cg_derive_parent) * (size_t)h.n_parents, s), "H2D parents");
+    HIP_TRY(stage(c->items, h.reqs, sizeof(cg_derive_req) * h.n, s), "H2D derive requests");
+    HIP_TRY(stage(c->arena, h.arena, h.arena_len, s, arena_room(h.arena_len)), "H2D arena");
+    d.parents = (const cg_derive_parent*)c->keys.p;
+    d.reqs = (const cg_derive_req*)c->items.p;
+    d.arena = (const uint8_t*)c->arena.p;
+  } else {
+    HIP_TRY(hipMemcpyAsync(d.secrets, h.secrets, 32 * h.n, hipMemcpyHostToDevice, s), "H2D private keys");
+  }
+  hipError_t e = launch_derive_call(c, d, s);
+  if (e == hipSuccess && h.derives()) e = hipMemcpyAsync(h.secrets, d.secrets, 32 * h.n, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(h.pubs, d.pubs, 64 * h.n, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess && h.retries) e = hipMemcpyAsync(h.retries, d.retries, h.n, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(h.status, d.status, h.n, hipMemcpyDeviceToHost, s);
+  // the staged secrets, whatever happened before
+  const hipError_t z0 = hipMemsetAsync(d.secrets, 0, 32 * h.n, s);
+  const hipError_t z1 = h.derives() && h.arena_len ? hipMemsetAsync(c->arena.p, 0, h.arena_len, s) : hipSuccess;
+  if (e == hipSuccess) e = z0 != hipSuccess ? z0 : z1;
+  HIP_TRY(e, "launch_derive / copies");
+  HIP_TRY(call.close(), "hipEventRecord");
+  HIP_TRY(hipStreamSynchronize(s), "hipStreamSynchronize");
+  return CG_OK;
+}
+
+static int derive_host(const char* fn, cg_ctx* c, const DeriveReq& h, bool derives) {
+  if (const int a = derive_args(fn, c, h, derives, true)) return a;
+  if (h.n == 0) return CG_OK;
+  std::lock_guard<std::mutex> g(c->mu);
+  return derive_host_locked(fn, c, h);
+}
+
+int cg_derive_keys(cg_ctx* c, const cg_derive_parent* parents, uint32_t n_parents, const cg_derive_req* reqs, uint64_t n,
+                   const uint8_t* arena, uint64_t arena_len, uint8_t* secrets_out, uint8_t* pubs_out,
+                   uint8_t* status_out, uint8_t* retries_out) {
+  return derive_host("cg_derive_keys", c,
+                     {parents, n_parents, reqs, n, arena, arena_len, 0, secrets_out, pubs_out, status_out, retries_out}, true);
+}
+
+int cg_derive_keys_device(cg_ctx* c, const cg_derive_parent* d_parents, uint32_t n_parents, const cg_derive_req* d_reqs,
+                          uint64_t n, const uint8_t* d_arena, uint64_t arena_len, uint8_t* d_secrets, uint8_t* d_pubs,
+                          uint8_t* d_status, uint8_t* d_retries, void* hip_stream) {
+  return derive_device("cg_derive_keys_device", c,
+                       {d_parents, n_parents, d_reqs, n, d_arena, arena_len, 0, d_secrets, d_pubs, d_status, d_retries},
+                       true, hip_stream);
+}
+
+int cg_public_keys(cg_ctx* c, uint32_t scheme, const uint8_t* secrets, uint64_t n, uint8_t* pubs_out,
+                   uint8_t* status_out) {
+  return derive_host("cg_public_keys", c,
+                     {nullptr, 0, nullptr, n, nullptr, 0, (uint8_t)(scheme < 256 ? scheme : 0), (uint8_t*)secrets, pubs_out,
+                      status_out, nullptr}, false);
+}
+
+int cg_public_keys_device(cg_ctx* c, uint32_t scheme, const uint8_t* d_secrets, uint64_t n, uint8_t* d_pubs,
+                          uint8_t* d_status, void* hip_stream) {
+  return derive_device("cg_public_keys_device", c,
+                       {nullptr, 0, nullptr, n, nullptr, 0, (uint8_t)(scheme < 256 ? scheme : 0), (uint8_t*)d_secrets,
+                        d_pubs, d_status, nullptr}, false, hip_stream);
+}
+
 // ---------------------------------------------------------------- several devices (pool.h)
 struct cg_pool {
   std::vector<cg_ctx*> ctx;
@@ -2478,6 +2636,46 @@ int cg_pool_sign_tx_ids(cg_pool* p, const uint8_t* ids, uint64_t n_ids, const cg
   });
   if (stats) stats->not_run = rc == CG_OK ? 0 : n;
   return rc;
+}
+
+// cg_derive_keys / cg_public_keys whole on one live slot, and on a device fault the next one
+// (cg_pool_sign_tx_ids' pattern).
+static int pool_derive(const char* fn, cg_pool* p, const DeriveReq& h, bool derives, cg_pool_stats* stats) {
+  if (!p) return fail(CG_ERR_ARG, "%s: pool is NULL", fn);
+  if (p->ctx.empty()) return fail(CG_ERR_ARG, "%s: empty pool", fn);
+  if (const int a = derive_args(fn, p->ctx[0], h, derives, true)) return a;
+  if (h.n == 0) return CG_OK;
+  std::lock_guard<std::mutex> g(p->mu);
+  auto blank = [&]() {
+    memset(h.status, CG_NOT_RUN, h.n);
+    if (derives) memset(h.secrets, 0, 32 * h.n);
+    memset(h.pubs, 0, 64 * h.n);
+    if (h.retries) memset(h.retries, 0, h.n);
+  };
+  blank();
+  uint8_t unit = CG_NOT_RUN;
+  const int rc = pool_call_locked(p, 1, &unit, stats, fn, [&](cg_ctx* c, uint64_t, uint64_t) {
+    const int r = derive_host_locked(fn, c, h);
+    if (r != CG_OK) blank();
+    return r;
+  });
+  if (stats) stats->not_run = rc == CG_OK ? 0 : h.n;
+  return rc;
+}
+
+int cg_pool_derive_keys(cg_pool* p, const cg_derive_parent* parents, uint32_t n_parents, const cg_derive_req* reqs,
+                        uint64_t n, const uint8_t* arena, uint64_t arena_len, uint8_t* secrets_out, uint8_t* pubs_out,
+                        uint8_t* status_out, uint8_t* retries_out, cg_pool_stats* stats) {
+  return pool_derive("cg_pool_derive_keys", p,
+                     {parents, n_parents, reqs, n, arena, arena_len, 0, secrets_out, pubs_out, status_out, retries_out}, true,
+                     stats);
+}
+
+int cg_pool_public_keys(cg_pool* p, uint32_t scheme, const uint8_t* secrets, uint64_t n, uint8_t* pubs_out,
+                        uint8_t* status_out, cg_pool_stats* stats) {
+  return pool_derive("cg_pool_public_keys", p,
+                     {nullptr, 0, nullptr, n, nullptr, 0, (uint8_t)(scheme < 256 ? scheme : 0), (uint8_t*)secrets, pubs_out,
+                      status_out, nullptr}, false, stats);
 }
 
 int cg_pool_verify_tx_signatures_packed(cg_pool* p, const cg_key* keys, uint32_t n_keys, const uint8_t* ids,

@@ -191,6 +191,27 @@ struct SignArgs {
   const void* d_btab;
 };
 
+// One chunk of a key-derivation call (derive_keys.hip). With d_reqs: cg_derive_keys, d_secrets is
+// written. Without: cg_public_keys, d_secrets holds the private keys of `scheme` and is only read.
+// d_ws holds derive_ws_bytes(n_parents, n) bytes and starts with the call's parent midstates
+// (launch_derive_parents, once per call, before the chunks).
+struct DeriveArgs {
+  const cg_derive_parent* d_parents;
+  uint32_t n_parents;
+  const cg_derive_req* d_reqs;
+  uint64_t n;
+  const uint8_t* d_arena;
+  uint64_t arena_len;
+  uint8_t scheme;
+  uint32_t force_retries;  // CG_TEST_DERIVE_FORCE_RETRIES
+  uint8_t* d_secrets;
+  uint8_t* d_pubs;
+  uint8_t* d_status;
+  uint8_t* d_retries;  // optional
+  void* d_ws;
+  const void* d_btab;
+};
+
 // One build of the radix-dependent kernels: the entry points cordagpu.cpp calls through a context's
 // variant (cg_config.table_bytes_max picks it at cg_open). Each build defines cg::variant() (renamed
 // cg24::variant() / cg22::variant() in the others).
@@ -220,12 +241,17 @@ struct EngineVariant {
   hipError_t (*launch_signer_expand)(const uint8_t* d_seeds, uint32_t n, void* d_signers, uint8_t* d_pubkeys,
                                      const void* d_btab, hipStream_t stream);
   hipError_t (*launch_sign)(const SignArgs& a, hipStream_t stream);
+  // key derivation (derive_keys.hip)
+  size_t (*derive_ws_bytes)(uint32_t n_parents, uint64_t n);
+  hipError_t (*launch_derive_parents)(const DeriveArgs& a, hipStream_t stream);
+  hipError_t (*launch_derive)(const DeriveArgs& a, hipStream_t stream);
 };
 
 }  // namespace cgt
 
 namespace cg {
 
+using cgt::DeriveArgs;
 using cgt::EngineVariant;
 using cgt::Fork;
 using cgt::ItemArgs;
@@ -293,6 +319,15 @@ size_t sign_ws_bytes(uint64_t n);
 hipError_t launch_signer_expand(const uint8_t* d_seeds, uint32_t n, void* d_signers, uint8_t* d_pubkeys,
                                 const void* d_btab, hipStream_t stream);
 hipError_t launch_sign(const SignArgs& a, hipStream_t stream);
+
+// Key derivation (derive_keys.hip; Crypto.deriveKeyPair). launch_derive_parents fills the head of the
+// workspace (derive_ws_bytes(n_parents, n) bytes: the parents' HMAC midstates, then one chunk's slots)
+// once per call, launch_derive runs one chunk over it. The workspace holds secrets (midstates, d, the
+// digits) until the caller zeroes it. derive_upload_constants: this translation unit's curve constants.
+hipError_t derive_upload_constants();
+size_t derive_ws_bytes(uint32_t n_parents, uint64_t n);
+hipError_t launch_derive_parents(const DeriveArgs& a, hipStream_t stream);
+hipError_t launch_derive(const DeriveArgs& a, hipStream_t stream);
 
 // RSA_SHA256 (verify_rsa.hip; radix-independent, used only by contexts opened with CG_FLAG_RSA).
 // Key records for a key table (launch_rsa_keyprep fills them: accepted keys get their Montgomery

@@ -374,6 +374,53 @@ CG_HD void sha512_prefix_ld(uint32_t out[16], const uint32_t prefix[PW], const L
   }
 }
 
+// SHA-512 resumed in `s` after one 128-byte block that is already absorbed (HMAC's K xor ipad block,
+// derive.h): the msg_len message bytes follow, the length field counts 128 + msg_len. The message is
+// read as sha512_prefix_ld reads it (aligned 16-byte chunks, one funnel shift per word); `s` is left as
+// the state, not as digest bytes: the caller's outer hash takes it as words.
+template <class Ld>
+CG_HD void sha512_resume128_ld(uint64_t s[8], const Ld& ld, uint64_t msg_off, uint64_t msg_len) {
+  const uint64_t n = 128 + msg_len;
+  const uint64_t nblocks = (msg_len + 17 + 127) >> 7;
+  const uint64_t base = msg_off & ~(uint64_t)3;
+  const uint32_t sh8 = (uint32_t)(msg_off & 3) * 8u;
+  for (uint64_t blk = 0; blk < nblocks; ++blk) {
+    const uint64_t k0 = blk * 32;  // the block's first message word
+    uint32_t W[36];
+#pragma unroll
+    for (int t = 0; t < 9; ++t) ld.dwords4(&W[4 * t], base + (k0 + 4 * t) * 4);
+    uint32_t be[32];
+#pragma unroll
+    for (int j = 0; j < 32; ++j) {
+#if defined(__HIP_DEVICE_COMPILE__)
+      const uint32_t raw = __builtin_amdgcn_alignbit(W[j + 1], W[j], sh8);
+#else
+      const uint32_t raw = (uint32_t)((((uint64_t)W[j + 1] << 32) | W[j]) >> sh8);
+#endif
+      const int64_t rem = (int64_t)msg_len - 4 * (int64_t)(k0 + j);  // message bytes in this word
+      uint32_t w;
+      if (rem >= 4) {
+        w = raw;
+      } else if (rem > 0) {
+        w = (raw & (0xffffffffu >> (32u - 8u * (uint32_t)rem))) | (0x80u << (8u * (uint32_t)rem));
+      } else {
+        w = rem == 0 ? 0x80u : 0u;
+      }
+      be[j] = CG_BSWAP32(w);
+    }
+    if (blk + 1 == nblocks) {
+      be[28] = 0;
+      be[29] = 0;
+      be[30] = (uint32_t)((n * 8) >> 32);
+      be[31] = (uint32_t)(n * 8);
+    }
+    uint64_t w[16];
+#pragma unroll
+    for (int j = 0; j < 16; ++j) w[j] = ((uint64_t)be[2 * j] << 32) | be[2 * j + 1];
+    sha512_compress(s, w);
+  }
+}
+
 template <class Ld>
 CG_HD void sha512_prefix64_ld(uint32_t out[16], const uint32_t prefix[16], const Ld& ld, uint64_t msg_off,
                               uint64_t msg_len) {

@@ -161,48 +161,6 @@ __global__ void __launch_bounds__(256, ED_SIGN_HASH_WAVES) k_ed_sign_nonce(
   }
 }
 
-// ed_fixed_base9 with each row's entry gathered into LDS one op ahead (the idiom of
-// ed_double_scalar_pf's B tail): op u's addition runs while op u + 1's entry is in flight and op
-// u + 2's digit word is loaded.
-__device__ __forceinline__ void ed_fixed_base_pf(ge_p2& out, const uint32_t* __restrict__ dw, const EdBWideTab& TB,
-                                                 uint8_t* wave_lds, uint32_t lane) {
-  constexpr int N = EdWideCfg::kBDigits;
-  const uint32_t wl = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(cg_lds_ptr)wave_lds);
-  int d_cur = (int)dw[0];
-  ed_glds_niels9(ed_b_src(TB, 0, d_cur), wl);
-  uint32_t w_next = dw[1];
-  ge9_p3 R;
-  // op u's entry from LDS into n, then op u + 1's gather and op u + 2's digit word issued
-  auto next = [&](int u, ge9_niels& n, bool& neg) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // op u's entry and op u + 1's digit word
-    ed_lds_niels9(n, wave_lds, lane);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // slot read before the next DMA lands
-    neg = d_cur < 0;
-    d_cur = (int)w_next;
-    ed_glds_niels9(ed_b_src(TB, u + 1, d_cur), wl);
-    if (u + 2 < N) w_next = dw[u + 2];
-  };
-  {  // op 0: identity + q0 (fe9.h ge9_from_niels_half: one product instead of an addition's seven)
-    ge9_niels n;
-    bool neg;
-    next(0, n, neg);
-    ge9_from_niels_half(R, n, neg);
-  }
-  for (int u = 1; u + 1 < N; ++u) {
-    ge9_niels n;
-    bool neg;
-    next(u, n, neg);
-    ge9_madd_half<true>(R, R, n, neg);
-  }
-  {  // the last addition: projective output
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    ge9_niels n;
-    ed_lds_niels9(n, wave_lds, lane);
-    ge9_madd_half<false>(R, R, n, d_cur < 0);
-  }
-  ge9_to_p2(out, R);
-}
-
 #ifndef ED_SIGN_RB_WAVES
 #define ED_SIGN_RB_WAVES 2  // k_ed_ladder_wide's bound: the fe9 additions need ~106 VGPRs
 #endif
@@ -224,45 +182,9 @@ __global__ void __launch_bounds__(256, ED_SIGN_RB_WAVES) k_ed_sign_rb(uint64_t n
   }
 }
 
-// Encode for ED_FINISH_K items per lane, one inversion per lane (k_ed_finish's batching: a wave takes
-// 64 x K consecutive items, lane l the items l, l + 64, ... of them).
-__device__ __forceinline__ void ed_sign_encode_one(uint64_t unit, uint64_t end, uint32_t* __restrict__ sigs,
-                                                   const SignWs& ws) {
-  const ge_p2* rin = (const ge_p2*)ws.slots;
-  const uint64_t base = (unit >> 6) * (64 * ED_FINISH_K) + (unit & 63);
-  fe acc[ED_FINISH_K];
-  fe run;
-  fe_1(run);
-  uint32_t pend = 0;
-  for (uint32_t k = 0; k < ED_FINISH_K; ++k) {
-    const uint64_t p = base + 64 * k;
-    const bool pd = p < end && ws.pend[p];
-    pend |= (uint32_t)pd << k;
-    if (pd) fe_mul(run, run, rin[p].Z);
-    fe_copy(acc[k], run);
-  }
-  if (!pend) return;
-  fe inv;
-  fe_invert(inv, run);
-  for (int k = ED_FINISH_K - 1; k >= 0; --k) {
-    if (!((pend >> k) & 1u)) continue;
-    const uint64_t p = base + 64 * (uint32_t)k;
-    const ge_p2 P = rin[p];
-    fe zi, t;
-    if (k > 0) fe_mul(zi, inv, acc[k - 1]);
-    else fe_copy(zi, inv);
-    fe_mul(t, inv, P.Z);
-    fe_copy(inv, t);
-    uint32_t enc[8];
-    ed_encode(enc, P, zi);
-#pragma unroll
-    for (int w = 0; w < 8; ++w) sigs[16 * p + w] = enc[w];
-  }
-}
-
 __global__ void __launch_bounds__(256) k_ed_sign_encode(uint64_t n, uint32_t* __restrict__ sigs, SignWs ws) {
   const uint64_t units = (n + 64 * ED_FINISH_K - 1) / (64 * ED_FINISH_K) * 64;
-  for (Walk w = walk_units(units); w.u < w.end; w.u += w.step) ed_sign_encode_one(w.u, n, sigs, ws);
+  for (Walk w = walk_units(units); w.u < w.end; w.u += w.step) ed_encode_run<ED_FINISH_K>(w.u, n, sigs, (const ge_p2*)ws.slots, ws.pend, 1);
 }
 
 template <bool Fused>

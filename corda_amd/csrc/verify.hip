@@ -306,7 +306,9 @@ __global__ void __launch_bounds__(256) k_mode_guard(const uint32_t* __restrict__
 hipError_t upload_constants() {
   hipError_t e = ed_upload_constants();
   if (e != hipSuccess) return e;
-  return ec_upload_constants();
+  e = ec_upload_constants();
+  if (e != hipSuccess) return e;
+  return derive_upload_constants();
 }
 
 size_t keyprep_bytes(uint32_t n_keys) { return key_ws_bytes(n_keys); }
@@ -626,7 +628,8 @@ const EngineVariant& variant() {
                                   make_wide_pool, wide_slots, key_cache_bytes, btab_bytes, btab_scratch_bytes, init_btab, item_ws_bytes,
                                   launch_keyprep, launch_key_tables, launch_items, launch_items_plan,
                                   launch_items_front, launch_items_back,
-                                  signer_bytes, sign_ws_bytes, launch_signer_expand, launch_sign};
+                                  signer_bytes, sign_ws_bytes, launch_signer_expand, launch_sign,
+                                  derive_ws_bytes, launch_derive_parents, launch_derive};
   return v;
 }
 

@@ -13,6 +13,7 @@ from . import _lib
 from .batch import COMPONENT_DTYPE, FLEAF_DTYPE, FTX_DTYPE, KEY_DTYPE, PMT_NODE_DTYPE, MODE_DOVERIFY, SPAN_DTYPE, TMPL_DTYPE, TX_DTYPE, TXSIG_DTYPE
 from .batch import REQ_NODE_DTYPE, TX_CHECK_DTYPE, TX_VERDICT_DTYPE, TXSIG12_DTYPE
 from .batch import SIGN_ITEM_DTYPE, SIGN_REQ_DTYPE
+from .batch import DERIVE_PARENT_DTYPE, DERIVE_REQ_DTYPE
 
 
 def _p(a):
@@ -298,6 +299,33 @@ class Engine:
         _lib.check(rc, "cg_sign_batch")
         return sigs.reshape(-1, 64), st
 
+    # ------------------------------------------------------------------ key derivation
+    def derive_keys(self, dr):
+        """Batch Crypto.deriveKeyPair(privateKey, seed) (cg_derive_keys, Crypto.kt:646-771): ``dr`` is a
+        batch.DeriveRequests. Returns (secrets uint8 [n, 32], public keys uint8 [n, 64], status uint8 [n],
+        rehashes uint8 [n]). Ed25519: the child seed, Abyte then 32 zero bytes; ECDSA: d and X || Y,
+        big-endian. An item whose status is not 0 has zero bytes; DERIVE_HOST items are the caller's to
+        finish (Crypto.derive_key_pairs does, with corda_amd/derive.py)."""
+        return _derive_keys(_lib.lib().cg_derive_keys, "cg_derive_keys", self._h, dr)
+
+    def derive_keys_device(self, d_parents, n_parents, d_reqs, n, d_arena, arena_len, d_secrets, d_pubs, d_status,
+                           d_retries=None, stream=0):
+        """Asynchronous device form: every table in HBM."""
+        rc = _lib.lib().cg_derive_keys_device(self._h, d_parents, n_parents, d_reqs, n, d_arena, arena_len, d_secrets,
+                                              d_pubs, d_status, d_retries or None, stream or None)
+        _lib.check(rc, "cg_derive_keys_device")
+
+    def public_keys(self, scheme, secrets):
+        """cg_public_keys: the public key of each 32-byte private key of one scheme (Ed25519: the seed;
+        ECDSA: a candidate d, big-endian). Returns (public keys uint8 [n, 64], status uint8 [n]); a
+        refused ECDSA candidate has status KEY_REJECTED and zero bytes. The staging copy of the secrets is
+        zeroed before this returns."""
+        return _public_keys(_lib.lib().cg_public_keys, "cg_public_keys", self._h, scheme, secrets)
+
+    def public_keys_device(self, scheme, d_secrets, n, d_pubs, d_status, stream=0):
+        rc = _lib.lib().cg_public_keys_device(self._h, scheme, d_secrets, n, d_pubs, d_status, stream or None)
+        _lib.check(rc, "cg_public_keys_device")
+
     # ------------------------------------------------------------------ per-transaction verdicts
     def tx_verdicts(self, sig_table, status, keys, checks, reqs, nodes, key_class=None):
         """cg_tx_verdicts: verifySignaturesExcept's two steps reduced on the device from one status byte
@@ -362,6 +390,38 @@ def _load_signers(fn, what, h, seeds):
         ctypes.memset(buf.ctypes.data, 0, buf.size)  # the staging copy (the caller's bytes are its own)
     _lib.check(rc, what)
     return [pub[32 * i:32 * i + 32].tobytes() for i in range(len(seeds))]
+
+
+def _public_keys(fn, what, h, scheme, secrets, stats=None):
+    views = [np.frombuffer(s, dtype=np.uint8) for s in secrets]
+    if any(v.size != 32 for v in views):
+        raise ValueError("a private key is 32 bytes (an Ed25519 seed, or an ECDSA d big-endian)")
+    n = len(views)
+    buf = np.zeros(32 * n, dtype=np.uint8)
+    for i, v in enumerate(views):
+        buf[32 * i:32 * i + 32] = v
+    pubs = np.zeros(64 * n, dtype=np.uint8)
+    st = np.full(n, 255, dtype=np.uint8)
+    args = [h, scheme, _p(buf), n, _p(pubs), _p(st)]
+    try:
+        rc = fn(*args, ctypes.byref(stats)) if stats is not None else fn(*args)
+    finally:
+        ctypes.memset(buf.ctypes.data, 0, buf.size)
+    _lib.check(rc, what)
+    return pubs.reshape(-1, 64), st
+
+
+def _derive_keys(fn, what, h, dr, stats=None, allow_partial=False):
+    assert dr.parents.dtype == DERIVE_PARENT_DTYPE and dr.reqs.dtype == DERIVE_REQ_DTYPE
+    n = dr.n
+    secrets, pubs = np.zeros(32 * n, dtype=np.uint8), np.zeros(64 * n, dtype=np.uint8)
+    st, tries = np.full(n, 255, dtype=np.uint8), np.zeros(n, dtype=np.uint8)
+    args = [h, _p(dr.parents), len(dr.parents), _p(dr.reqs), n, _p(dr.arena), dr.arena.size, _p(secrets), _p(pubs),
+            _p(st), _p(tries)]
+    rc = fn(*args, ctypes.byref(stats)) if stats is not None else fn(*args)
+    if rc != 0 and not allow_partial:
+        _lib.check(rc, what)
+    return secrets.reshape(-1, 32), pubs.reshape(-1, 64), st, tries
 
 
 def _check_tables(checks, reqs, nodes, key_class, n_keys):
@@ -511,6 +571,21 @@ class EnginePool:
         if rc != 0 and not allow_partial:
             _lib.check(rc, "cg_pool_sign_tx_ids")
         return sigs.reshape(-1, 64), st
+
+    def derive_keys(self, dr, allow_partial=False):
+        """cg_pool_derive_keys: the whole call on one healthy slot, the next one on a device fault.
+        Returns what Engine.derive_keys returns."""
+        stats = _lib.cg_pool_stats()
+        out = _derive_keys(_lib.lib().cg_pool_derive_keys, "cg_pool_derive_keys", self._h, dr, stats, allow_partial)
+        self.last_stats = {k: getattr(stats, k) for k, _ in _lib.cg_pool_stats._fields_ if k != "reserved"}
+        return out
+
+    def public_keys(self, scheme, secrets):
+        """cg_pool_public_keys: Engine.public_keys on one healthy slot, the next one on a device fault."""
+        stats = _lib.cg_pool_stats()
+        out = _public_keys(_lib.lib().cg_pool_public_keys, "cg_pool_public_keys", self._h, scheme, secrets, stats)
+        self.last_stats = {k: getattr(stats, k) for k, _ in _lib.cg_pool_stats._fields_ if k != "reserved"}
+        return out
 
     def verify_requeue(self, batch, mode=MODE_DOVERIFY, between=None):
         """The JVM binding's re-queue (CryptoBatch.kt verifyBatch): on CG_ERR_DEVICE only the items left

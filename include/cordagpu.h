@@ -679,6 +679,69 @@ typedef struct cg_sign_item {
 int cg_sign_batch(cg_ctx* ctx, const cg_sign_item* items, uint64_t n, const uint8_t* arena, uint64_t arena_len,
                   uint8_t* sigs_out, uint8_t* status_out);
 
+/* ---- Key derivation: the batch form of Crypto.deriveKeyPair (core/.../crypto/Crypto.kt:646-771), the
+ * call the reference points at for a unique key per transaction (Crypto.kt:631-637). Deterministic for
+ * all three curves, so the output is byte for byte what the JVM returns:
+ *   mac = HMAC-SHA512(key = keyData, msg = seed)                                   (deriveHMAC)
+ *   keyData: a BC EC private key's d.toByteArray() (minimal two's complement, big-endian, 1..33 bytes),
+ *            an EdDSA key's geta() (the 32 clamped bytes h[0..32) of SHA-512(seed)). The caller (the
+ *            packers of the Python and Kotlin mirrors) forms keyData; the library does not reinterpret it.
+ *   EDDSA_ED25519_SHA512: child seed = mac[0..32), EdDSAPrivateKeySpec(seed), public Abyte = encode(a B).
+ *   ECDSA_SECP256R1/K1_SHA256: d = BigInteger(1, mac[0..32)); d is refused when d < 2, or
+ *            bitCount(3d xor d) < 64 (WNafUtil.getNafWeight against n.bitLength() >>> 2), or d >= n, or
+ *            d G is infinity (never, for 2 <= d < n). A refused d repeats the derivation with
+ *            seed := SHA-256(seed). The device makes at most CG_DERIVE_MAX_RETRIES rehashes (each
+ *            happens with probability about 2^-32 on secp256r1, far less on secp256k1); an item that
+ *            still has no d gets CG_DERIVE_HOST and is finished by the caller's host restatement.
+ * A seed of length 0 is legal. Statuses: 0 derived; CG_DERIVE_HOST; CG_DERIVE_BAD_PARENT the parent's
+ * key_len is 0 (SecretKeySpec throws) or above 128 (would need a pre-hash of the key; never occurs);
+ * CG_UNSUPPORTED the parent's scheme is none of the three (deriveKeyPair throws for RSA and SPHINCS);
+ * CG_NOT_RUN the parent index, the parent's key bytes or the seed lie out of range. An item with a
+ * status other than 0 gets zero secret and public bytes.
+ * The parent key bytes on the device, the HMAC midstates, the macs, d and the table digits are secret:
+ * the call's workspace is zeroed on the stream behind its last kernel (also after a failed launch) and
+ * the library keeps no host copy. Not cleared: scratch memory and LDS. The table gathers are indexed by
+ * digits of the child scalar: not constant-time, as for the signer above. The host always draws
+ * randomness (generateKeyPair), never the device. */
+#define CG_DERIVE_MAX_RETRIES 4
+enum {
+  CG_DERIVE_HOST = 6,       /* more than CG_DERIVE_MAX_RETRIES rehashes: finish this item on the host */
+  CG_DERIVE_BAD_PARENT = 7, /* parent key_len == 0 or > 128 */
+  CG_KEY_REJECTED = 8       /* cg_public_keys: the ECDSA candidate d fails the accept rule; redraw it */
+};
+typedef struct cg_derive_parent {
+  uint64_t key_off;  /* keyData at arena[key_off .. key_off+key_len) */
+  uint16_t key_len;  /* 1 .. 128 */
+  uint8_t scheme;    /* CG_ECDSA_SECP256K1_SHA256, CG_ECDSA_SECP256R1_SHA256 or CG_EDDSA_ED25519_SHA512 */
+  uint8_t pad[5];    /* must be 0 */
+} cg_derive_parent;  /* 16 bytes */
+typedef struct cg_derive_req {
+  uint64_t seed_off;  /* seed at arena[seed_off .. seed_off+seed_len) */
+  uint32_t seed_len;
+  uint32_t parent;    /* index into the parent table */
+} cg_derive_req;      /* 16 bytes */
+/* Per request: secrets_out 32 bytes (Ed25519: the child seed; ECDSA: d big-endian), pubs_out 64 bytes
+ * (Ed25519: Abyte, then 32 zero bytes; ECDSA: X || Y big-endian), status_out 1 byte, and when
+ * retries_out_opt is not NULL the number of rehashes made (0 for Ed25519). */
+int cg_derive_keys(cg_ctx* ctx, const cg_derive_parent* parents, uint32_t n_parents, const cg_derive_req* reqs,
+                   uint64_t n, const uint8_t* arena, uint64_t arena_len, uint8_t* secrets_out, uint8_t* pubs_out,
+                   uint8_t* status_out, uint8_t* retries_out_opt);
+/* Device buffers in HBM (d_arena, d_secrets and d_pubs 4-byte aligned: the kernels move them as 32-bit
+ * words; d_arena readable up to arena_len rounded up to 4); asynchronous on hip_stream. */
+int cg_derive_keys_device(cg_ctx* ctx, const cg_derive_parent* d_parents, uint32_t n_parents,
+                          const cg_derive_req* d_reqs, uint64_t n, const uint8_t* d_arena, uint64_t arena_len,
+                          uint8_t* d_secrets, uint8_t* d_pubs, uint8_t* d_status, uint8_t* d_retries_opt,
+                          void* hip_stream);
+/* The second half alone: private key -> public key for n secrets of one scheme (32 * n bytes).
+ * Ed25519: seed -> Abyte (deriveKeyPairFromEntropy; generateKeyPair with host-drawn SecureRandom bytes).
+ * ECDSA: a candidate d (big-endian) goes through the accept rule, then Q = d G; a refused candidate
+ * gets CG_KEY_REJECTED and zero bytes, and the host redraws it. pubs_out: 64 * n bytes as above. */
+int cg_public_keys(cg_ctx* ctx, uint32_t scheme, const uint8_t* secrets, uint64_t n, uint8_t* pubs_out,
+                   uint8_t* status_out);
+/* d_secrets and d_pubs 4-byte aligned, as above. */
+int cg_public_keys_device(cg_ctx* ctx, uint32_t scheme, const uint8_t* d_secrets, uint64_t n, uint8_t* d_pubs,
+                          uint8_t* d_status, void* hip_stream);
+
 /* ---- Several devices in one process (the JVM process drives every GPU of the node).
  * A pool holds one cg_ctx per slot (a slot is a device ordinal; a device may appear twice).
  * cg_pool_verify_batch cuts the items into contiguous, equal shards, one per healthy slot, runs
@@ -752,6 +815,16 @@ int cg_pool_signers_clear(cg_pool* pool);
 int cg_pool_sign_tx_ids(cg_pool* pool, const uint8_t* ids, uint64_t n_ids, const cg_sign_req* reqs, uint64_t n,
                         const cg_signable_tmpl* tmpls, uint32_t n_tmpls, const uint8_t* arena, uint64_t arena_len,
                         uint8_t* sigs_out, uint8_t* status_out, cg_pool_stats* stats_opt);
+/* cg_derive_keys on a pool: not sharded, the whole call runs on the first healthy slot and, if that
+ * slot's device fails, on the next one (as cg_pool_sign_tx_ids). When no slot could run it the status
+ * bytes are CG_NOT_RUN, the outputs zero, and the call returns CG_ERR_DEVICE. */
+int cg_pool_derive_keys(cg_pool* pool, const cg_derive_parent* parents, uint32_t n_parents,
+                        const cg_derive_req* reqs, uint64_t n, const uint8_t* arena, uint64_t arena_len,
+                        uint8_t* secrets_out, uint8_t* pubs_out, uint8_t* status_out, uint8_t* retries_out_opt,
+                        cg_pool_stats* stats_opt);
+/* cg_public_keys on a pool, the same way. */
+int cg_pool_public_keys(cg_pool* pool, uint32_t scheme, const uint8_t* secrets, uint64_t n, uint8_t* pubs_out,
+                        uint8_t* status_out, cg_pool_stats* stats_opt);
 /* Failure drill: make every later call on `slot` fail as a device fault would (fail = 1), or
  * clear it and mark the slot healthy again (fail = 0). For tests and operational drills. */
 int cg_pool_inject_fault(cg_pool* pool, uint32_t slot, int fail);

@@ -185,6 +185,37 @@ JNIEXPORT jint JNICALL Java_net_corda_core_crypto_CryptoBatch_nativeSignTxIds(
                         (uint8_t*)ADDR(status_out));
 }
 
+/* Crypto.deriveKeyPair(privateKey, seed) over many seeds (Crypto.kt:646-771): cg_derive_keys (pool != 0:
+ * cg_pool_derive_keys, the whole call on one healthy device, the next one on a device fault). parents:
+ * cg_derive_parent records over keyData the binding wrote into the arena; secrets_out 32 bytes, pubs_out
+ * 64 bytes, status_out and retries_out one byte per request. The binding zeroes the arena and the
+ * secrets buffer afterwards. */
+JNIEXPORT jint JNICALL Java_net_corda_core_crypto_CryptoBatch_nativeDeriveKeys(
+    JNIEnv* env, jobject self, jlong ctx, jlong pool, jobject parents, jint n_parents, jobject reqs, jlong n,
+    jobject arena, jlong arena_len, jobject secrets_out, jobject pubs_out, jobject status_out, jobject retries_out) {
+  if (pool)
+    return cg_pool_derive_keys((cg_pool*)(intptr_t)pool, (const cg_derive_parent*)ADDR(parents), (uint32_t)n_parents,
+                               (const cg_derive_req*)ADDR(reqs), (uint64_t)n, (const uint8_t*)ADDR(arena),
+                               (uint64_t)arena_len, (uint8_t*)ADDR(secrets_out), (uint8_t*)ADDR(pubs_out),
+                               (uint8_t*)ADDR(status_out), (uint8_t*)ADDR(retries_out), 0);
+  return cg_derive_keys((cg_ctx*)(intptr_t)ctx, (const cg_derive_parent*)ADDR(parents), (uint32_t)n_parents,
+                        (const cg_derive_req*)ADDR(reqs), (uint64_t)n, (const uint8_t*)ADDR(arena), (uint64_t)arena_len,
+                        (uint8_t*)ADDR(secrets_out), (uint8_t*)ADDR(pubs_out), (uint8_t*)ADDR(status_out),
+                        (uint8_t*)ADDR(retries_out));
+}
+
+/* Private key -> public key for n 32-byte private keys of one scheme: cg_public_keys / cg_pool_public_keys. */
+JNIEXPORT jint JNICALL Java_net_corda_core_crypto_CryptoBatch_nativePublicKeys(JNIEnv* env, jobject self, jlong ctx,
+                                                                             jlong pool, jint scheme, jobject secrets,
+                                                                             jlong n, jobject pubs_out,
+                                                                             jobject status_out) {
+  if (pool)
+    return cg_pool_public_keys((cg_pool*)(intptr_t)pool, (uint32_t)scheme, (const uint8_t*)ADDR(secrets), (uint64_t)n,
+                               (uint8_t*)ADDR(pubs_out), (uint8_t*)ADDR(status_out), 0);
+  return cg_public_keys((cg_ctx*)(intptr_t)ctx, (uint32_t)scheme, (const uint8_t*)ADDR(secrets), (uint64_t)n,
+                        (uint8_t*)ADDR(pubs_out), (uint8_t*)ADDR(status_out));
+}
+
 /* A direct buffer the node keeps across calls: pinned once (cg_host_register), so its bytes reach
  * every device by DMA without the runtime's CPU staging copy. */
 JNIEXPORT jint JNICALL Java_net_corda_core_crypto_CryptoBatch_nativeHostRegister(JNIEnv* env, jobject self,

@@ -13,10 +13,21 @@ import net.corda.core.serialization.serialize
 import net.corda.core.transactions.SignedTransaction
 import net.i2p.crypto.eddsa.EdDSAPrivateKey
 import net.i2p.crypto.eddsa.EdDSAPublicKey
+import net.i2p.crypto.eddsa.spec.EdDSANamedCurveSpec
+import net.i2p.crypto.eddsa.spec.EdDSAPrivateKeySpec
+import net.i2p.crypto.eddsa.spec.EdDSAPublicKeySpec
+import org.bouncycastle.jcajce.provider.asymmetric.ec.BCECPrivateKey
+import org.bouncycastle.jcajce.provider.asymmetric.ec.BCECPublicKey
+import org.bouncycastle.jce.provider.BouncyCastleProvider
+import org.bouncycastle.jce.spec.ECParameterSpec
+import org.bouncycastle.jce.spec.ECPrivateKeySpec
+import org.bouncycastle.jce.spec.ECPublicKeySpec
+import java.math.BigInteger
 import java.nio.ByteBuffer
 import java.nio.ByteOrder
 import java.security.InvalidKeyException
 import java.security.KeyPair
+import java.security.PrivateKey
 import java.security.PublicKey
 import java.security.SignatureException
 import java.util.concurrent.TimeUnit
@@ -114,6 +125,15 @@ object CryptoBatch {
     private external fun nativeSignTxIds(ctx: Long, pool: Long, ids: ByteBuffer, nIds: Long, reqs: ByteBuffer, n: Long,
                                          tmpls: ByteBuffer, nTmpls: Int, arena: ByteBuffer, arenaLen: Long,
                                          sigsOut: ByteBuffer, statusOut: ByteBuffer): Int
+    /** cg_(pool_)derive_keys: Crypto.deriveKeyPair(privateKey, seed) per 16-byte request (cg_derive_req: seed
+     *  offset and length, parent) over 16-byte parents (cg_derive_parent: keyData offset and length, scheme);
+     *  32 secret bytes, 64 public bytes, a status byte and a rehash count per request. */
+    private external fun nativeDeriveKeys(ctx: Long, pool: Long, parents: ByteBuffer, nParents: Int, reqs: ByteBuffer, n: Long,
+                                          arena: ByteBuffer, arenaLen: Long, secretsOut: ByteBuffer, pubsOut: ByteBuffer,
+                                          statusOut: ByteBuffer, retriesOut: ByteBuffer): Int
+    /** cg_(pool_)public_keys: the public key of each 32-byte private key of one scheme. */
+    private external fun nativePublicKeys(ctx: Long, pool: Long, scheme: Int, secrets: ByteBuffer, n: Long,
+                                          pubsOut: ByteBuffer, statusOut: ByteBuffer): Int
     private external fun nativeHostRegister(buf: ByteBuffer, len: Long): Int
     private external fun nativeHostUnregister(buf: ByteBuffer): Int
 
@@ -129,6 +149,10 @@ object CryptoBatch {
     const val CG_UNSUPPORTED = 4
     const val CG_EMPTY = 5
     const val CG_NOT_RUN = 255
+    // key derivation (cg_derive_keys / cg_public_keys)
+    const val CG_DERIVE_HOST = 6
+    const val CG_DERIVE_BAD_PARENT = 7
+    const val CG_KEY_REJECTED = 8
     // include/cordagpu.h return codes
     // per-transaction verdicts (include/cordagpu.h cg_tx_verdict.flags, req_status codes, struct sizes)
     const val CG_TXV_SPAN_BAD = 1
@@ -538,6 +562,97 @@ object CryptoBatch {
             if (rc == CG_OK && status.get(j).toInt() == 0)
                 TransactionSignature(ByteArray(64).also { sigs.position(64 * j); sigs.get(it) }, keyPair.public, signatureMetadata)
             else onJvm(id)
+        }
+    }
+
+    private fun wipe(b: ByteBuffer) { for (i in 0 until b.capacity()) b.put(i, 0) }
+
+    /** deriveHMAC's keyData (Crypto.kt:759-771) and the scheme id of a private key the device derives
+     *  from, or null: d.toByteArray() of a BC EC key on secp256r1 / secp256k1, geta() of an EdDSA key. */
+    private fun deriveKeyData(privateKey: PrivateKey): Pair<Int, ByteArray>? = when (Crypto.findSignatureScheme(privateKey)) {
+        Crypto.EDDSA_ED25519_SHA512 -> Crypto.EDDSA_ED25519_SHA512.schemeNumberID to (privateKey as EdDSAPrivateKey).geta()
+        Crypto.ECDSA_SECP256R1_SHA256 -> Crypto.ECDSA_SECP256R1_SHA256.schemeNumberID to (privateKey as BCECPrivateKey).d.toByteArray()
+        Crypto.ECDSA_SECP256K1_SHA256 -> Crypto.ECDSA_SECP256K1_SHA256.schemeNumberID to (privateKey as BCECPrivateKey).d.toByteArray()
+        else -> null
+    }
+
+    /** The key pair of the child bytes the device wrote: EdDSAPrivateKeySpec(seed) with the device's Abyte,
+     *  or ECPrivateKeySpec(d) with the device's Q = (X, Y), as deriveKeyPairEdDSA / deriveKeyPairECDSA
+     *  build them (Crypto.kt:713-737, 676-711). */
+    private fun childKeyPair(parent: PrivateKey, schemeId: Int, secret: ByteArray, pub: ByteArray): KeyPair {
+        if (schemeId == Crypto.EDDSA_ED25519_SHA512.schemeNumberID) {
+            val params = Crypto.EDDSA_ED25519_SHA512.algSpec as EdDSANamedCurveSpec
+            val priv = EdDSAPrivateKeySpec(secret, params)
+            val abyte = pub.copyOf(32)
+            check(abyte.contentEquals(priv.a.toByteArray())) { "the device's Abyte is not the child seed's" }
+            return KeyPair(EdDSAPublicKey(EdDSAPublicKeySpec(abyte, params)), EdDSAPrivateKey(priv))
+        }
+        val scheme = if (schemeId == Crypto.ECDSA_SECP256R1_SHA256.schemeNumberID) Crypto.ECDSA_SECP256R1_SHA256
+                     else Crypto.ECDSA_SECP256K1_SHA256
+        val spec = scheme.algSpec as ECParameterSpec
+        val q = spec.curve.createPoint(BigInteger(1, pub.copyOfRange(0, 32)), BigInteger(1, pub.copyOfRange(32, 64)))
+        return KeyPair(BCECPublicKey(parent.algorithm, ECPublicKeySpec(q, spec), BouncyCastleProvider.CONFIGURATION),
+                       BCECPrivateKey(parent.algorithm, ECPrivateKeySpec(BigInteger(1, secret), spec), BouncyCastleProvider.CONFIGURATION))
+    }
+
+    /** Crypto.deriveKeyPair(privateKey, seed) (Crypto.kt:646-771) for many seeds in one call: a key pair
+     *  per transaction and party (Crypto.kt:631-637), byte for byte what the JVM derives. A scheme the
+     *  device does not derive for (RSA, SPHINCS: the reference throws), fewer seeds than minBatch, a
+     *  device fault or any non-zero status (CG_DERIVE_HOST: more than four rehashes) falls back to
+     *  Crypto.deriveKeyPair on the JVM for those seeds, which also raises the reference's own exceptions.
+     *  The direct buffers that held key bytes (the arena with keyData, the child secrets) are zeroed
+     *  before they are released, and so is the keyData array. */
+    fun deriveAll(privateKey: PrivateKey, seeds: List<ByteArray>): List<KeyPair> {
+        fun onJvm(seed: ByteArray) = Crypto.deriveKeyPair(privateKey, seed)
+        if (seeds.isEmpty()) return emptyList()
+        val kd = if (seeds.size < config.minBatch) null else deriveKeyData(privateKey)
+        if (kd == null || kd.second.isEmpty() || kd.second.size > 128) return seeds.map(::onJvm)
+        val (schemeId, keyData) = kd
+        val n = seeds.size
+        val arena = direct(keyData.size + seeds.sumOf { it.size } + 16)
+        val parents = direct(16)
+        val reqs = direct(16 * n)
+        val secrets = direct(32 * n)
+        val pubs = direct(64 * n)
+        val status = direct(n)
+        val retries = direct(n)
+        try {
+            parents.putLong(0L).putShort(keyData.size.toShort()).put(schemeId.toByte())
+            arena.put(keyData)
+            seeds.forEach { reqs.putLong(arena.position().toLong()).putInt(it.size).putInt(0); arena.put(it) }
+            val rc = withHandles { c, p ->
+                nativeDeriveKeys(c, p, parents, 1, reqs, n.toLong(), arena, arena.position().toLong(), secrets, pubs, status, retries)
+            }
+            return seeds.mapIndexed { j, seed ->
+                if (rc == CG_OK && status.get(j).toInt() == 0)
+                    childKeyPair(privateKey, schemeId, ByteArray(32).also { secrets.position(32 * j); secrets.get(it) },
+                                 ByteArray(64).also { pubs.position(64 * j); pubs.get(it) })
+                else onJvm(seed)
+            }
+        } finally {
+            wipe(arena); wipe(secrets); keyData.fill(0)
+        }
+    }
+
+    /** The public halves of 32-byte private keys of one scheme (cg_public_keys): Abyte for Ed25519 seeds
+     *  (deriveKeyPairFromEntropy, generateKeyPair with bytes the caller drew from SecureRandom), X || Y for
+     *  ECDSA candidates d, whose status is CG_KEY_REJECTED when BC's accept rule refuses them (the caller
+     *  redraws). Returns (public keys 64 bytes each, status bytes); null on a device fault. The secrets
+     *  buffer is zeroed before it is released. */
+    fun publicKeys(schemeId: Int, privateKeys: List<ByteArray>): Pair<ByteArray, ByteArray>? {
+        require(privateKeys.all { it.size == 32 }) { "a private key is 32 bytes" }
+        val n = privateKeys.size
+        if (n == 0) return ByteArray(0) to ByteArray(0)
+        val secrets = direct(32 * n)
+        val pubs = direct(64 * n)
+        val status = direct(n)
+        try {
+            privateKeys.forEach { secrets.put(it) }
+            val rc = withHandles { c, p -> nativePublicKeys(c, p, schemeId, secrets, n.toLong(), pubs, status) }
+            if (rc != CG_OK) return null
+            return ByteArray(64 * n).also { pubs.position(0); pubs.get(it) } to ByteArray(n).also { status.position(0); status.get(it) }
+        } finally {
+            wipe(secrets)
         }
     }
 
