@@ -31,7 +31,8 @@ i2p GroupElement) -> IllegalArgumentException("not a valid point"); an X.509 key
 Crypto.decodePublicKey (Crypto.kt:349-356, the ECDSA Kryo path Kryo.kt:388-398) ->
 InvalidKeySpecException("This public key cannot be decoded, ...").
 
-Signing (Crypto.kt:395-402, :415-422), EDDSA_ED25519_SHA512 only, on the GPU:
+Signing (Crypto.kt:395-402, :415-422) on the GPU: EDDSA_ED25519_SHA512, and with ``random=`` the two ECDSA
+schemes (below):
   * ``Crypto.do_sign(private_key, clear_data)`` -- doSign(privateKey, clearData): an unsupported scheme
     -> IllegalArgumentException; empty clear data -> Exception("Signing of an empty array is not
     permitted!"); returns the 64 signature bytes i2p's EdDSAEngine.engineSign writes (RFC 8032).
@@ -41,9 +42,14 @@ Signing (Crypto.kt:395-402, :415-422), EDDSA_ED25519_SHA512 only, on the GPU:
     key is not the private key's (the Abyte ``Engine.load_signers`` returns).
   * ``Crypto.sign_all(key_pair, tx_ids, metadata)`` -- the batch form: NotaryService.sign(txId)
     (NotaryService.kt:77-80) for many ids in one call.
-  A private key of another scheme raises UnsupportedOperationException, as SPHINCS verification does:
-  there is no host ECDSA / RSA signer in this mirror (BC draws k and the PSS salt at random, so there is
-  nothing bit-exact to reproduce; a JVM caller keeps its own Crypto.doSign for them).
+  An RSA or SPHINCS private key raises UnsupportedOperationException, as SPHINCS verification does, and so
+  does an ECDSA key when no ``random=`` is given: the mirror has no host signer (a JVM caller keeps its own
+  Crypto.doSign for those).
+  * ``do_sign`` / ``do_sign_tx`` / ``sign_all`` with ``random=`` (a callable ``random(nbytes) -> bytes``, e.g.
+    ``secrets.token_bytes``) sign with ECDSA_SECP256K1_SHA256 / ECDSA_SECP256R1_SHA256 keys: the host
+    draws BC's BigInteger(256, random) candidates for k, the device signs (cg_ec_sign_batch /
+    cg_ec_sign_tx_ids) and applies BC's refusals, and only the refused items are redrawn, one draw per
+    attempt as in ECDSASigner.generateSignature. Returns BC's DER bytes.
 
 Key derivation (Crypto.kt:646-771), all three curves, on the GPU:
   * ``Crypto.derive_key_pair(private_key, seed, scheme=None)`` -- deriveKeyPair: a scheme that is not
@@ -75,6 +81,9 @@ RSA_SHA256 = 1
 ECDSA_SECP256K1_SHA256 = B.ECDSA_SECP256K1_SHA256
 ECDSA_SECP256R1_SHA256 = B.ECDSA_SECP256R1_SHA256
 EDDSA_ED25519_SHA512 = B.EDDSA_ED25519_SHA512
+_ECDSA_SCHEMES = (ECDSA_SECP256K1_SHA256, ECDSA_SECP256R1_SHA256)
+_EC_ORDER = {ECDSA_SECP256K1_SHA256: 0xFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFEBAAEDCE6AF48A03BBFD25E8CD0364141,
+             ECDSA_SECP256R1_SHA256: 0xFFFFFFFF00000000FFFFFFFFFFFFFFFFBCE6FAADA7179E84F3B9CAC2FC632551}  # group orders n
 SPHINCS256_SHA256 = 5
 COMPOSITE_KEY = 6
 
@@ -190,6 +199,9 @@ class _Crypto:
         self._signers = []       # the private keys loaded into the engine, by signer index
         self._signer_pub = []    # their Abytes
         self._signer_engine = None
+        self._ec_signers = []    # the ECDSA private keys loaded into the engine's ECDSA signer set
+        self._ec_signer_pub = []  # their X || Y
+        self._ec_signer_engine = None
 
     def engine(self):
         with self._lock:
@@ -388,12 +400,16 @@ class _Crypto:
         return self._one(public_key, signature_data, clear_data, B.MODE_ISVALID)
 
     # ------------------------------------------------------------------ signing
-    def _sign_scheme(self, private_key, clear_len):
+    def _sign_scheme(self, private_key, clear_len, random=None):
         """doSign's checks in its order (Crypto.kt:396-398), then the mirror's own limit."""
         if private_key.scheme not in SCHEME_CODE_NAMES or private_key.scheme == COMPOSITE_KEY:
             raise IllegalArgumentException(f"Unsupported key/algorithm for schemeCodeName: {private_key.scheme}")
         if clear_len == 0:
             raise Exception("Signing of an empty array is not permitted!")
+        if private_key.scheme in _ECDSA_SCHEMES and random is not None:
+            if len(private_key.encoded) != 32:
+                raise InvalidKeyException("an ECDSA private key is 32 bytes of d, big-endian")
+            return
         if private_key.scheme != EDDSA_ED25519_SHA512:
             raise UnsupportedOperationException(
                 f"no signer for scheme {SCHEME_CODE_NAMES[private_key.scheme]} in this mirror; the JVM caller keeps "
@@ -414,12 +430,60 @@ class _Crypto:
             i = self._signers.index(private_key)
             return i, self._signer_pub[i]
 
+    def _ec_signer(self, private_key):
+        """(signer index, X || Y) of a key in the engine's ECDSA signer set, loading it when it is new."""
+        eng = self.engine()
+        with self._lock:
+            if self._ec_signer_engine is not eng:
+                self._ec_signers, self._ec_signer_pub, self._ec_signer_engine = [], [], eng
+            if private_key not in self._ec_signers:
+                # the range check on the host, before anything is loaded: the device set and this list
+                # never disagree (Crypto never makes a key outside [1, n - 1])
+                if not 0 < int.from_bytes(private_key.encoded, "big") < _EC_ORDER[private_key.scheme]:
+                    raise InvalidKeyException("the ECDSA private key is not in [1, n - 1]")
+                keys = self._ec_signers + [private_key]
+                pubs, st = eng.load_ec_signers([(k.scheme, k.encoded) for k in keys])
+                if any(int(x) != 0 for x in st):
+                    raise InvalidKeyException("the device refused an ECDSA private key")
+                self._ec_signer_pub, self._ec_signers = pubs, keys
+            i = self._ec_signers.index(private_key)
+            return i, self._ec_signer_pub[i]
+
     def forget_signers(self):
-        """Zeroes and frees the engine's signer set (cg_signers_clear)."""
+        """Zeroes and frees the engine's signer sets (cg_signers_clear, cg_ec_signers_clear)."""
         with self._lock:
             if self._signer_engine is not None:
                 self._signer_engine.clear_signers()
             self._signers, self._signer_pub, self._signer_engine = [], [], None
+            if self._ec_signer_engine is not None:
+                self._ec_signer_engine.clear_ec_signers()
+            self._ec_signers, self._ec_signer_pub, self._ec_signer_engine = [], [], None
+
+    def _ec_sign_loop(self, n, random, call):
+        """ECDSASigner.generateSignature's loop over a batch: every pending item gets one 32-byte draw
+        (BigInteger(256, random)), ``call(pending, nonces)`` signs them, and only the items that came back
+        NONCE_REJECTED are redrawn. The nonce array is zeroed by the engine call that read it."""
+        out, pending = [None] * n, list(range(n))
+        while pending:
+            nonces = np.zeros(32 * len(pending), dtype=np.uint8)
+            for j in range(len(pending)):
+                k = random(32)
+                if len(k) != 32:
+                    raise ValueError("random(32) must return 32 bytes")
+                nonces[32 * j:32 * j + 32] = np.frombuffer(k, dtype=np.uint8)
+            try:
+                sigs, ln, st = call(pending, nonces)
+            finally:
+                nonces[:] = 0
+            again = []
+            for j, i in enumerate(pending):
+                if int(st[j]) == B.NONCE_REJECTED:
+                    again.append(i)
+                    continue
+                self._sign_status(int(st[j]))
+                out[i] = sigs[j, :int(ln[j])].tobytes()
+            pending = again
+        return out
 
     @staticmethod
     def _sign_status(status):
@@ -428,41 +492,60 @@ class _Crypto:
         if status != 0:
             raise RuntimeError(f"item not signed (status {status})")
 
-    def do_sign(self, private_key, clear_data):
-        """Crypto.doSign(privateKey, clearData) (Crypto.kt:395-402)."""
+    def do_sign(self, private_key, clear_data, random=None):
+        """Crypto.doSign(privateKey, clearData) (Crypto.kt:395-402). ``random``: see the module text; without
+        it an ECDSA key raises UnsupportedOperationException."""
         clear_data = bytes(clear_data)
-        self._sign_scheme(private_key, len(clear_data))
+        self._sign_scheme(private_key, len(clear_data), random)
+        if private_key.scheme in _ECDSA_SCHEMES:
+            i, _ = self._ec_signer(private_key)
+            return self._ec_sign_loop(1, random, lambda pend, k: self.engine().sign_ec([(i, clear_data)], k))[0]
         i, _ = self._signer(private_key)
         sigs, st = self.engine().sign([(i, clear_data)])
         self._sign_status(int(st[0]))
         return sigs[0].tobytes()
 
-    def _aligned_signer(self, key_pair):
+    def _aligned_signer(self, key_pair, random=None):
         """The key-pair check of Crypto.kt:416-419, then the signer index."""
         sig_key = self.find_signature_scheme(key_pair.private)
         sig_meta = self.find_signature_scheme(key_pair.public)
         if sig_key != sig_meta:
             raise IllegalArgumentException(f"Metadata schemeCodeName: {SCHEME_CODE_NAMES[sig_meta]} is not aligned with "
                                            f"the key type: {SCHEME_CODE_NAMES[sig_key]}.")
-        self._sign_scheme(key_pair.private, 1)
+        self._sign_scheme(key_pair.private, 1, random)
+        if key_pair.private.scheme in _ECDSA_SCHEMES:
+            i, xy = self._ec_signer(key_pair.private)
+            if K.canonical_spki(key_pair.private.scheme, B.KEY_RAW, xy) != key_pair.public.spki():
+                raise IllegalArgumentException("The public key of this pair is not the private key's.")
+            return i
         i, abyte = self._signer(key_pair.private)
         if K.canonical_spki(EDDSA_ED25519_SHA512, B.KEY_RAW, abyte) != key_pair.public.spki():
             raise IllegalArgumentException("The public key of this pair is not the private key's.")
         return i
 
-    def do_sign_tx(self, key_pair, signable_data):
+    def do_sign_tx(self, key_pair, signable_data, random=None):
         """Crypto.doSign(keyPair, signableData) (Crypto.kt:415-422) -> TransactionSignature."""
         return self.sign_all(key_pair, [signable_data.tx_id],
-                             (signable_data.platform_version, signable_data.scheme_number_id))[0]
+                             (signable_data.platform_version, signable_data.scheme_number_id), random=random)[0]
 
-    def sign_all(self, key_pair, tx_ids, metadata=(1, 4)):
+    def sign_all(self, key_pair, tx_ids, metadata=(1, 4), random=None):
         """NotaryService.sign(txId) (NotaryService.kt:77-80) for every id in one call:
-        Crypto.doSign(keyPair, SignableData(txId, SignatureMetadata(*metadata))) each."""
+        Crypto.doSign(keyPair, SignableData(txId, SignatureMetadata(*metadata))) each. ``random``: see the
+        module text; without it an ECDSA key pair raises UnsupportedOperationException."""
         from . import signable
-        signer = self._aligned_signer(key_pair)
+        signer = self._aligned_signer(key_pair, random)
         if not tx_ids:
             return []
         pv, sid = metadata
+        if key_pair.private.scheme in _ECDSA_SCHEMES:
+            def call(pending, nonces):
+                b = B.SignRequestBuilder()
+                t = b.template(*signable.template(pv, sid))
+                for i in pending:
+                    b.add_request(signer, b.tx_id(tx_ids[i]), t)
+                return self.engine().sign_ec_tx_ids(b.build(), nonces)
+            return [TransactionSignature(sig, key_pair.public, pv, sid)
+                    for sig in self._ec_sign_loop(len(tx_ids), random, call)]
         b = B.SignRequestBuilder()
         t = b.template(*signable.template(pv, sid))
         for tx_id in tx_ids:

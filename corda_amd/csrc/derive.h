@@ -181,6 +181,18 @@ CG_HD bool ec_fixed_base(Jac& R, const u256w& d, const TabG& TG, const EcConsts&
   return !inf;
 }
 
+// The k G of an item slot in place: the slot's scalar (u256w) becomes the Jacobian result. False at
+// infinity (the slot keeps the scalar). Shared by k_derive_ec_mul (derive_keys.hip) and k_ec_sign_mul
+// (sign_ec.hip).
+template <int C, class TabG>
+CG_HD bool ec_slot_fixed_base(void* slot, const TabG& TG, const EcConsts& K) {
+  const u256w d = *(const u256w*)slot;
+  Jac R;
+  if (!ec_fixed_base<C>(R, d, TG, K)) return false;
+  *(Jac*)slot = R;
+  return true;
+}
+
 // X || Y big-endian (16 little-endian words of the 64 bytes) of the Jacobian P given zi = 1 / P.Z
 template <int C>
 CG_HD void ec_affine_be(uint32_t out[16], const Jac& P, const f29& zi) {

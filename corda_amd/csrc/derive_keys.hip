@@ -223,12 +223,8 @@ __global__ void __launch_bounds__(256) k_derive_ec_mul(uint64_t n, const EcGWide
   for (Walk w = walk_units(n); w.u < w.end; w.u += w.step) {
     const uint64_t p = w.u;
     if (ws.pend[p] != DK_EC + C) continue;
-    uint8_t* slot = (uint8_t*)ws.slots + (size_t)p * ITEM_SLOT;
-    const u256w d = *(const u256w*)slot;
-    Jac R;
-    if (ec_fixed_base<C>(R, d, *gtab, c_dk_ec[C])) {
-      *(Jac*)slot = R;
-    } else {  // Crypto.kt:729-731 (pointQ.isInfinity): not reachable for 2 <= d < n; left to the host
+    if (!ec_slot_fixed_base<C>((uint8_t*)ws.slots + (size_t)p * ITEM_SLOT, *gtab, c_dk_ec[C])) {
+      // Crypto.kt:729-731 (pointQ.isInfinity): not reachable for 2 <= d < n; left to the host
       ws.pend[p] = DK_NONE;  // (secrets: null in the public-key form, where they are the caller's input)
       status[p] = secrets ? CG_DERIVE_HOST : CG_KEY_REJECTED;
       dk_zero_out(secrets, pubs, p, secrets != nullptr);

@@ -191,6 +191,29 @@ struct SignArgs {
   const void* d_btab;
 };
 
+// One chunk of an ECDSA sign call (sign_ec.hip): SignArgs' request forms over the context's ECDSA signer
+// store, the chunk's nonces (32 bytes per request) and its 72-byte signature slots, length and status
+// bytes. d_ws holds sign_ec_ws_bytes(n) bytes.
+struct SignEcArgs {
+  const void* d_reqs;
+  uint64_t n;
+  bool fused;
+  const void* d_signers;
+  uint32_t n_signers;
+  const uint8_t* d_arena;
+  uint64_t arena_len;
+  const uint8_t* d_msgs;
+  const cg_signable_tmpl* d_tmpls;
+  uint32_t n_tmpls;
+  uint64_t n_ids;
+  const uint8_t* d_nonces;
+  uint8_t* d_sigs;
+  uint8_t* d_sig_len;
+  uint8_t* d_status;
+  void* d_ws;
+  const void* d_btab;
+};
+
 // One chunk of a key-derivation call (derive_keys.hip). With d_reqs: cg_derive_keys, d_secrets is
 // written. Without: cg_public_keys, d_secrets holds the private keys of `scheme` and is only read.
 // d_ws holds derive_ws_bytes(n_parents, n) bytes and starts with the call's parent midstates
@@ -245,6 +268,12 @@ struct EngineVariant {
   size_t (*derive_ws_bytes)(uint32_t n_parents, uint64_t n);
   hipError_t (*launch_derive_parents)(const DeriveArgs& a, hipStream_t stream);
   hipError_t (*launch_derive)(const DeriveArgs& a, hipStream_t stream);
+  // the ECDSA signer (sign_ec.hip)
+  size_t (*ec_signer_bytes)();
+  size_t (*sign_ec_ws_bytes)(uint64_t n);
+  hipError_t (*launch_ec_signer_expand)(const uint8_t* d_schemes, const uint8_t* d_secrets, uint32_t n, void* d_signers,
+                                        uint8_t* d_pubs, uint8_t* d_status, const void* d_btab, hipStream_t stream);
+  hipError_t (*launch_sign_ec)(const SignEcArgs& a, hipStream_t stream);
 };
 
 }  // namespace cgt
@@ -257,6 +286,7 @@ using cgt::Fork;
 using cgt::ItemArgs;
 using cgt::PendingTabs;
 using cgt::SignArgs;
+using cgt::SignEcArgs;
 using cgt::SigTable;
 using cgt::StageTimer;
 using cgt::VerifyReq;
@@ -328,6 +358,19 @@ hipError_t derive_upload_constants();
 size_t derive_ws_bytes(uint32_t n_parents, uint64_t n);
 hipError_t launch_derive_parents(const DeriveArgs& a, hipStream_t stream);
 hipError_t launch_derive(const DeriveArgs& a, hipStream_t stream);
+
+// The ECDSA signer (sign_ec.hip; BC's ECDSASigner.generateSignature behind Crypto.doSign, k given by the
+// caller). The signer store holds ec_signer_bytes() per signer (launch_ec_signer_expand fills it from the
+// scheme bytes and the 32-byte big-endian d, and writes X || Y and a load status per signer);
+// launch_sign_ec signs one chunk over a workspace of sign_ec_ws_bytes(n) bytes, which holds secrets (every
+// k and its k G) until the caller zeroes it. sign_ec_upload_constants: this translation unit's curve
+// constants.
+hipError_t sign_ec_upload_constants();
+size_t ec_signer_bytes();
+size_t sign_ec_ws_bytes(uint64_t n);
+hipError_t launch_ec_signer_expand(const uint8_t* d_schemes, const uint8_t* d_secrets, uint32_t n, void* d_signers,
+                                   uint8_t* d_pubs, uint8_t* d_status, const void* d_btab, hipStream_t stream);
+hipError_t launch_sign_ec(const SignEcArgs& a, hipStream_t stream);
 
 // RSA_SHA256 (verify_rsa.hip; radix-independent, used only by contexts opened with CG_FLAG_RSA).
 // Key records for a key table (launch_rsa_keyprep fills them: accepted keys get their Montgomery

@@ -534,6 +534,44 @@ static inline const EcGWideTab* gwide(const void* d_btab, int curve) {
   return (const EcGWideTab*)((const uint8_t*)bwide(d_btab) + sizeof(EdBWideTab)) + curve;
 }
 
+// What one item of a sign call signs (sign_ed.hip, sign_ec.hip), from either request form: the signer, and the message as a splice (template,
+// tx index) or as arena bytes (offset). `st`: 0 when it can be signed.
+struct SignMsg {
+  uint32_t signer, tmpl, len;
+  uint64_t at;  // Fused: the tx index, else the arena offset
+  uint8_t st;
+};
+template <bool Fused>
+__device__ __forceinline__ SignMsg sign_msg(const void* __restrict__ reqs, uint64_t i, uint32_t n_signers,
+                                            const cg_signable_tmpl* __restrict__ tmpls, uint32_t n_tmpls,
+                                            uint64_t n_ids, uint64_t arena_len) {
+  SignMsg m;
+  m.tmpl = 0;
+  if (Fused) {
+    const cg_sign_req q = ((const cg_sign_req*)reqs)[i];
+    m.signer = q.signer;
+    m.tmpl = q.tmpl;
+    m.at = q.tx_idx;
+    m.len = 0;
+    bool ok = q.signer < n_signers && q.tx_idx < n_ids && q.tmpl < n_tmpls;
+    if (ok) {
+      const cg_signable_tmpl t = tmpls[q.tmpl];
+      ok = in_arena(t.prefix_off, t.prefix_len, arena_len) && in_arena(t.suffix_off, t.suffix_len, arena_len);
+      m.len = t.prefix_len + 32u + t.suffix_len;  // never empty: the id is part of it
+    }
+    m.st = ok ? 0 : CG_NOT_RUN;
+  } else {
+    const cg_sign_item q = ((const cg_sign_item*)reqs)[i];
+    m.signer = q.signer;
+    m.at = q.msg_off;
+    m.len = q.msg_len;
+    m.st = q.msg_len == 0 ? CG_EMPTY
+           : (q.signer >= n_signers || !in_arena(q.msg_off, q.msg_len, arena_len)) ? CG_NOT_RUN
+                                                                                     : 0;
+  }
+  return m;
+}
+
 // Intermediate per-item status codes (never returned to the caller)
 #define ED_PENDING 254u
 #define EC_PENDING_BASE 250u  // + curve: parsed + hashed, awaiting the ladder

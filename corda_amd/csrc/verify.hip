@@ -308,7 +308,9 @@ hipError_t upload_constants() {
   if (e != hipSuccess) return e;
   e = ec_upload_constants();
   if (e != hipSuccess) return e;
-  return derive_upload_constants();
+  e = derive_upload_constants();
+  if (e != hipSuccess) return e;
+  return sign_ec_upload_constants();
 }
 
 size_t keyprep_bytes(uint32_t n_keys) { return key_ws_bytes(n_keys); }
@@ -629,7 +631,8 @@ const EngineVariant& variant() {
                                   launch_keyprep, launch_key_tables, launch_items, launch_items_plan,
                                   launch_items_front, launch_items_back,
                                   signer_bytes, sign_ws_bytes, launch_signer_expand, launch_sign,
-                                  derive_ws_bytes, launch_derive_parents, launch_derive};
+                                  derive_ws_bytes, launch_derive_parents, launch_derive,
+                                  ec_signer_bytes, sign_ec_ws_bytes, launch_ec_signer_expand, launch_sign_ec};
   return v;
 }
 

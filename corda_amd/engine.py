@@ -299,6 +299,52 @@ class Engine:
         _lib.check(rc, "cg_sign_batch")
         return sigs.reshape(-1, 64), st
 
+    # ------------------------------------------------------------------ ECDSA signing
+    def load_ec_signers(self, keys):
+        """cg_ec_signers_load: replaces the context's ECDSA signer set (separate from the Ed25519 one) with
+        ``keys``, (scheme 2 / 3, 32-byte big-endian d) pairs. Returns (X || Y per key, load status uint8
+        [n]); a refused key (KEY_INVALID: d = 0 or d >= n; UNSUPPORTED: another scheme) has zero bytes. The
+        staging copy of the d bytes is zeroed before this returns."""
+        return _load_ec_signers(_lib.lib().cg_ec_signers_load, "cg_ec_signers_load", self._h, keys)
+
+    def clear_ec_signers(self):
+        _lib.check(_lib.lib().cg_ec_signers_clear(self._h), "cg_ec_signers_clear")
+
+    def sign_ec_tx_ids(self, sr, nonces):
+        """Batch Crypto.doSign(keyPair, SignableData(txId, metadata)) for ECDSA keys (cg_ec_sign_tx_ids):
+        ``sr`` is a batch.SignRequests over the ECDSA signer set, ``nonces`` the requests' 32-byte
+        big-endian k candidates (what BC's RandomDSAKCalculator.nextK would have drawn). Returns
+        (signature slots uint8 [n, 72], lengths uint8 [n], status uint8 [n]); an item with status
+        NONCE_REJECTED is the caller's to redraw and resubmit. The nonce array handed to the C ABI is
+        zeroed before this returns: a C-contiguous uint8 array is that array (the caller sees it zeroed);
+        a list of bytes objects is copied into one, and the caller's immutable copies stay in memory."""
+        assert sr.reqs.dtype == SIGN_REQ_DTYPE and sr.tmpls.dtype == TMPL_DTYPE
+        fn = _lib.lib().cg_ec_sign_tx_ids
+        return _sign_ec(lambda k, sigs, ln, st: fn(self._h, _p(sr.ids), sr.n_ids, _p(sr.reqs), sr.n, _p(sr.tmpls),
+                                                   len(sr.tmpls), _p(sr.arena), sr.arena.size, k, sigs, ln, st),
+                        "cg_ec_sign_tx_ids", sr.n, nonces)
+
+    def sign_ec_tx_ids_device(self, d_ids, n_ids, d_reqs, n, tmpls, d_arena, arena_len, d_nonces, d_sigs, d_sig_len,
+                              d_status, stream=0):
+        """Asynchronous device form; `tmpls` is a host TMPL_DTYPE array (template bytes in the arena). The
+        caller owns, and zeroes, d_nonces."""
+        assert tmpls.dtype == TMPL_DTYPE
+        rc = _lib.lib().cg_ec_sign_tx_ids_device(self._h, d_ids, n_ids, d_reqs, n, _p(tmpls), len(tmpls), d_arena,
+                                                 arena_len, d_nonces, d_sigs, d_sig_len, d_status, stream or None)
+        _lib.check(rc, "cg_ec_sign_tx_ids_device")
+
+    def sign_ec(self, signer_msgs, nonces):
+        """Batch Crypto.doSign(privateKey, clearData) for ECDSA keys (cg_ec_sign_batch) over (signer index,
+        message bytes) pairs. Returns what sign_ec_tx_ids returns."""
+        n = len(signer_msgs)
+        spans, arena = self._spans([m for _, m in signer_msgs])
+        items = np.zeros(n, dtype=SIGN_ITEM_DTYPE)
+        items["msg_off"], items["msg_len"] = spans["off"], spans["len"]
+        items["signer"] = [s for s, _ in signer_msgs]
+        fn = _lib.lib().cg_ec_sign_batch
+        return _sign_ec(lambda k, sigs, ln, st: fn(self._h, _p(items), n, _p(arena), arena.size - 8, k, sigs, ln, st),
+                        "cg_ec_sign_batch", n, nonces)
+
     # ------------------------------------------------------------------ key derivation
     def derive_keys(self, dr):
         """Batch Crypto.deriveKeyPair(privateKey, seed) (cg_derive_keys, Crypto.kt:646-771): ``dr`` is a
@@ -390,6 +436,59 @@ def _load_signers(fn, what, h, seeds):
         ctypes.memset(buf.ctypes.data, 0, buf.size)  # the staging copy (the caller's bytes are its own)
     _lib.check(rc, what)
     return [pub[32 * i:32 * i + 32].tobytes() for i in range(len(seeds))]
+
+
+def _load_ec_signers(fn, what, h, keys):
+    keys = list(keys)
+    views = [np.frombuffer(d, dtype=np.uint8) for _, d in keys]
+    if not views or any(v.size != 32 for v in views):
+        raise ValueError("an ECDSA private key is 32 bytes of d, big-endian; at least one is needed")
+    n = len(keys)
+    schemes = np.array([s if 0 <= s < 256 else 255 for s, _ in keys], dtype=np.uint8)
+    buf = np.zeros(32 * n, dtype=np.uint8)
+    for i, v in enumerate(views):
+        buf[32 * i:32 * i + 32] = v
+    pubs = np.zeros(64 * n, dtype=np.uint8)
+    st = np.full(n, 255, dtype=np.uint8)
+    try:
+        rc = fn(h, _p(schemes), _p(buf), n, _p(pubs), _p(st))
+    finally:
+        ctypes.memset(buf.ctypes.data, 0, buf.size)  # the staging copy (the caller's bytes are its own)
+    _lib.check(rc, what)
+    return [pubs[64 * i:64 * i + 64].tobytes() for i in range(n)], st
+
+
+def nonce_array(nonces, n):
+    """The 32 n bytes of a sign call's k candidates, from n bytes-like objects or from a uint8 array. A
+    C-contiguous uint8 array is used in place: it is the array the C ABI reads, and the caller sees it zeroed."""
+    if isinstance(nonces, np.ndarray):
+        buf = nonces.reshape(-1) if nonces.dtype == np.uint8 and nonces.flags.c_contiguous else \
+            np.ascontiguousarray(nonces, dtype=np.uint8).reshape(-1)
+    else:
+        buf = np.zeros(32 * n, dtype=np.uint8)
+        for i, k in enumerate(nonces):
+            v = np.frombuffer(k, dtype=np.uint8)
+            if v.size != 32:
+                raise ValueError("a nonce candidate is 32 bytes, big-endian")
+            buf[32 * i:32 * i + 32] = v
+    if buf.size != 32 * n:
+        raise ValueError("one 32-byte nonce candidate per request")
+    return buf
+
+
+def _sign_ec(call, what, n, nonces, allow_partial=False):
+    buf = nonce_array(nonces, n)
+    sigs = np.zeros(72 * n, dtype=np.uint8)
+    ln = np.zeros(n, dtype=np.uint8)
+    st = np.full(n, 255, dtype=np.uint8)
+    try:
+        rc = call(_p(buf), _p(sigs), _p(ln), _p(st))
+    finally:
+        if buf.size:
+            ctypes.memset(buf.ctypes.data, 0, buf.size)  # the array the C ABI read
+    if rc != 0 and not allow_partial:
+        _lib.check(rc, what)
+    return sigs.reshape(-1, 72), ln, st
 
 
 def _public_keys(fn, what, h, scheme, secrets, stats=None):
@@ -571,6 +670,26 @@ class EnginePool:
         if rc != 0 and not allow_partial:
             _lib.check(rc, "cg_pool_sign_tx_ids")
         return sigs.reshape(-1, 64), st
+
+    def load_ec_signers(self, keys):
+        """cg_pool_ec_signers_load: the ECDSA signer set on every slot; returns what Engine.load_ec_signers does."""
+        return _load_ec_signers(_lib.lib().cg_pool_ec_signers_load, "cg_pool_ec_signers_load", self._h, keys)
+
+    def clear_ec_signers(self):
+        _lib.check(_lib.lib().cg_pool_ec_signers_clear(self._h), "cg_pool_ec_signers_clear")
+
+    def sign_ec_tx_ids(self, sr, nonces, allow_partial=False):
+        """cg_pool_ec_sign_tx_ids: the whole call on one healthy slot, the next one on a device fault.
+        Returns what Engine.sign_ec_tx_ids returns."""
+        assert sr.reqs.dtype == SIGN_REQ_DTYPE and sr.tmpls.dtype == TMPL_DTYPE
+        stats = _lib.cg_pool_stats()
+        fn = _lib.lib().cg_pool_ec_sign_tx_ids
+        out = _sign_ec(lambda k, sigs, ln, st: fn(self._h, _p(sr.ids), sr.n_ids, _p(sr.reqs), sr.n, _p(sr.tmpls),
+                                                  len(sr.tmpls), _p(sr.arena), sr.arena.size, k, sigs, ln, st,
+                                                  ctypes.byref(stats)),
+                       "cg_pool_ec_sign_tx_ids", sr.n, nonces, allow_partial)
+        self.last_stats = {k: getattr(stats, k) for k, _ in _lib.cg_pool_stats._fields_ if k != "reserved"}
+        return out
 
     def derive_keys(self, dr, allow_partial=False):
         """cg_pool_derive_keys: the whole call on one healthy slot, the next one on a device fault.

@@ -635,7 +635,8 @@ int cg_verify_filtered_device(cg_ctx* ctx, const cg_filtered_tx* d_ftxs, uint64_
  *     -> i2p 0.2.0 EdDSAEngine.engineSign: RFC 8032's deterministic signature
  *          r = SHA-512(h[32..64) || M) mod L, R = r B, S = (r + SHA-512(R || A || M) a) mod L
  *   (the BFT notary signs the same way, BFTSMaRt.kt:249-255). The output is byte for byte what the JVM
- *   writes. ECDSA and RSA signing stay on the host: BC draws k and the PSS salt from SecureRandom.
+ *   writes. ECDSA signing has a block of its own below (the host draws k); RSA-PSS signing stays on the
+ *   host: BC draws the salt from SecureRandom.
  * A context holds a signer set: private keys the node keeps in its own process
  * (PersistentKeyManagementService.kt:84-95), loaded once and named by index in every request. The seeds,
  * the expanded keys and every nonce r are secret: the signer store is a device allocation of its own,
@@ -678,6 +679,59 @@ typedef struct cg_sign_item {
 /* Crypto.doSign(privateKey, clearData) (Crypto.kt:395-402; NotaryService.kt:73-75) over arena bytes. */
 int cg_sign_batch(cg_ctx* ctx, const cg_sign_item* items, uint64_t n, const uint8_t* arena, uint64_t arena_len,
                   uint8_t* sigs_out, uint8_t* status_out);
+
+/* ---- ECDSA signing: the batch form of Crypto.doSign for ECDSA_SECP256K1_SHA256 (2) and
+ * ECDSA_SECP256R1_SHA256 (3), with the nonce drawn by the caller:
+ *   Crypto.doSign(privateKey, clearData)            core/.../crypto/Crypto.kt:395-402
+ *   Crypto.doSign(keyPair, signableData)            Crypto.kt:415-422; NotaryService.kt:73-80
+ *     -> BC 1.57 DSABase.engineSign -> ECDSASigner.generateSignature -> StdDSAEncoder.encode
+ *          e = BigInteger(1, SHA-256(M)); k = BigInteger(256, random), redrawn while k = 0 or k >= n;
+ *          r = x(k G) mod n, redrawn while 0; s = k^-1 (e + d r) mod n, the attempt repeated while 0;
+ *          DERSequence(ASN1Integer(r), ASN1Integer(s)), 8 .. 72 bytes
+ *   Every attempt of BC's loop consumes one 32-byte draw. A request carries one candidate k (32 bytes,
+ *   big-endian: what RandomDSAKCalculator.nextK would have drawn); the device applies BC's refusals and
+ *   answers CG_NONCE_REJECTED, and the caller redraws and resubmits that item alone: BC's loop for that
+ *   item, and given the draws the output is byte for byte what the JVM writes. The device never draws
+ *   randomness.
+ * The ECDSA signer set is separate from the Ed25519 one: loading or clearing either leaves the other
+ * untouched. Secret: d, every k and k^-1 and the table digits of k (given one k, d = (s k - e) / r). The
+ * signer store is a device allocation of its own; the staged d bytes are zeroed on the stream right
+ * behind the expansion, the store before every free (cg_ec_signers_clear, a reload, cg_close), and no
+ * host copy is kept. A sign call zeroes its workspace on the stream behind the last chunk's last kernel,
+ * also after a failed launch; the host forms zero their staged copy of the nonces too. Not cleared:
+ * scratch memory and LDS. The fixed-base table is read at addresses that depend on digits of k, so the
+ * access pattern is not constant-time, as for the Ed25519 signer above.
+ * Statuses: 0 signed; CG_EMPTY msg_len == 0, checked before anything else (Crypto.kt:398); CG_NOT_RUN a
+ * signer, id or template index out of range, bytes outside the arena, or a signer refused at load;
+ * CG_NONCE_REJECTED the candidate is 0 or >= n, or gave r = 0 or s = 0. An item that is not signed gets 72
+ * zero bytes and length 0. With no ECDSA signers loaded a sign call is CG_ERR_ARG and writes nothing;
+ * n == 0 is a no-op. */
+#define CG_NONCE_REJECTED 9 /* redraw this item's k and resubmit it */
+#define CG_EC_SIG_MAX 72    /* bytes per signature slot */
+/* Replaces the context's ECDSA signer set with n keys: schemes[i] (2 or 3) and 32 bytes of d, big-endian,
+ * at secrets[32 i]; mixed curves are allowed, n <= CG_SIGNERS_MAX. pubs_out (64 * n bytes) receives X || Y
+ * of d G, which the caller compares with keyPair.public (Crypto.kt:416-419). status_out (n bytes): 0
+ * loaded; CG_KEY_INVALID d = 0 or d >= n; CG_UNSUPPORTED another scheme. A refused signer gets zero public
+ * bytes and its requests later get CG_NOT_RUN (Crypto never makes such a key). */
+int cg_ec_signers_load(cg_ctx* ctx, const uint8_t* schemes, const uint8_t* secrets, uint32_t n, uint8_t* pubs_out,
+                       uint8_t* status_out); /* no host copy is kept */
+/* Zeroes and frees the ECDSA signer set (a no-op when none is loaded). */
+int cg_ec_signers_clear(cg_ctx* ctx);
+/* Crypto.doSign(keyPair, SignableData(ids[tx_idx], tmpl)) for every request, as cg_sign_tx_ids; nonces:
+ * 32 * n bytes, request i's candidate k. sigs_out: 72 * n bytes (the DER bytes, then zeros), sig_len_out
+ * and status_out: n bytes each. */
+int cg_ec_sign_tx_ids(cg_ctx* ctx, const uint8_t* ids, uint64_t n_ids, const cg_sign_req* reqs, uint64_t n,
+                      const cg_signable_tmpl* tmpls, uint32_t n_tmpls, const uint8_t* arena, uint64_t arena_len,
+                      const uint8_t* nonces, uint8_t* sigs_out, uint8_t* sig_len_out, uint8_t* status_out);
+/* Device buffers in HBM except `tmpls` (a small host array); asynchronous on hip_stream. d_ids, d_reqs,
+ * d_arena, d_nonces and d_sigs must be 4-byte aligned. The caller owns (and zeroes) d_nonces. */
+int cg_ec_sign_tx_ids_device(cg_ctx* ctx, const uint8_t* d_ids, uint64_t n_ids, const cg_sign_req* d_reqs, uint64_t n,
+                             const cg_signable_tmpl* tmpls, uint32_t n_tmpls, const uint8_t* d_arena,
+                             uint64_t arena_len, const uint8_t* d_nonces, uint8_t* d_sigs, uint8_t* d_sig_len,
+                             uint8_t* d_status, void* hip_stream);
+/* Crypto.doSign(privateKey, clearData) (Crypto.kt:395-402) over arena bytes. */
+int cg_ec_sign_batch(cg_ctx* ctx, const cg_sign_item* items, uint64_t n, const uint8_t* arena, uint64_t arena_len,
+                     const uint8_t* nonces, uint8_t* sigs_out, uint8_t* sig_len_out, uint8_t* status_out);
 
 /* ---- Key derivation: the batch form of Crypto.deriveKeyPair (core/.../crypto/Crypto.kt:646-771), the
  * call the reference points at for a unique key per transaction (Crypto.kt:631-637). Deterministic for
@@ -815,6 +869,16 @@ int cg_pool_signers_clear(cg_pool* pool);
 int cg_pool_sign_tx_ids(cg_pool* pool, const uint8_t* ids, uint64_t n_ids, const cg_sign_req* reqs, uint64_t n,
                         const cg_signable_tmpl* tmpls, uint32_t n_tmpls, const uint8_t* arena, uint64_t arena_len,
                         uint8_t* sigs_out, uint8_t* status_out, cg_pool_stats* stats_opt);
+/* The ECDSA signer set on every slot and cg_ec_sign_tx_ids on a pool, by the rules of the three calls
+ * above (pubs_out and status_out of the load from the first slot that loaded). When no slot could run the
+ * sign call the status bytes are CG_NOT_RUN, the signatures and lengths zero, and it returns CG_ERR_DEVICE. */
+int cg_pool_ec_signers_load(cg_pool* pool, const uint8_t* schemes, const uint8_t* secrets, uint32_t n,
+                            uint8_t* pubs_out, uint8_t* status_out);
+int cg_pool_ec_signers_clear(cg_pool* pool);
+int cg_pool_ec_sign_tx_ids(cg_pool* pool, const uint8_t* ids, uint64_t n_ids, const cg_sign_req* reqs, uint64_t n,
+                           const cg_signable_tmpl* tmpls, uint32_t n_tmpls, const uint8_t* arena, uint64_t arena_len,
+                           const uint8_t* nonces, uint8_t* sigs_out, uint8_t* sig_len_out, uint8_t* status_out,
+                           cg_pool_stats* stats_opt);
 /* cg_derive_keys on a pool: not sharded, the whole call runs on the first healthy slot and, if that
  * slot's device fails, on the next one (as cg_pool_sign_tx_ids). When no slot could run it the status
  * bytes are CG_NOT_RUN, the outputs zero, and the call returns CG_ERR_DEVICE. */

@@ -185,6 +185,40 @@ JNIEXPORT jint JNICALL Java_net_corda_core_crypto_CryptoBatch_nativeSignTxIds(
                         (uint8_t*)ADDR(status_out));
 }
 
+/* The ECDSA signer set (cg_ec_signers_load; pool != 0: cg_pool_ec_signers_load, every device): a scheme byte and
+ * 32 bytes of d per key; pubs_out 64 bytes (X || Y) and status_out one byte per key. The binding zeroes the
+ * secrets buffer afterwards. */
+JNIEXPORT jint JNICALL Java_net_corda_core_crypto_CryptoBatch_nativeLoadEcSigners(JNIEnv* env, jobject self, jlong ctx,
+                                                                                jlong pool, jobject schemes,
+                                                                                jobject secrets, jint n, jobject pubs_out,
+                                                                                jobject status_out) {
+  if (pool)
+    return cg_pool_ec_signers_load((cg_pool*)(intptr_t)pool, (const uint8_t*)ADDR(schemes), (const uint8_t*)ADDR(secrets),
+                                   (uint32_t)n, (uint8_t*)ADDR(pubs_out), (uint8_t*)ADDR(status_out));
+  return cg_ec_signers_load((cg_ctx*)(intptr_t)ctx, (const uint8_t*)ADDR(schemes), (const uint8_t*)ADDR(secrets),
+                            (uint32_t)n, (uint8_t*)ADDR(pubs_out), (uint8_t*)ADDR(status_out));
+}
+
+/* Crypto.doSign(keyPair, SignableData(id, metadata)) for ECDSA key pairs over many ids: cg_ec_sign_tx_ids (pool != 0:
+ * cg_pool_ec_sign_tx_ids). nonces: 32 bytes per request, the candidate k the binding drew; sigs_out: 72 bytes per
+ * request (the DER bytes, then zeros), sig_len_out and status_out: one byte per request. */
+JNIEXPORT jint JNICALL Java_net_corda_core_crypto_CryptoBatch_nativeEcSignTxIds(
+    JNIEnv* env, jobject self, jlong ctx, jlong pool, jobject ids, jlong n_ids, jobject reqs, jlong n, jobject tmpls,
+    jint n_tmpls, jobject arena, jlong arena_len, jobject nonces, jobject sigs_out, jobject sig_len_out,
+    jobject status_out) {
+  if (pool)
+    return cg_pool_ec_sign_tx_ids((cg_pool*)(intptr_t)pool, (const uint8_t*)ADDR(ids), (uint64_t)n_ids,
+                                  (const cg_sign_req*)ADDR(reqs), (uint64_t)n, (const cg_signable_tmpl*)ADDR(tmpls),
+                                  (uint32_t)n_tmpls, (const uint8_t*)ADDR(arena), (uint64_t)arena_len,
+                                  (const uint8_t*)ADDR(nonces), (uint8_t*)ADDR(sigs_out), (uint8_t*)ADDR(sig_len_out),
+                                  (uint8_t*)ADDR(status_out), 0);
+  return cg_ec_sign_tx_ids((cg_ctx*)(intptr_t)ctx, (const uint8_t*)ADDR(ids), (uint64_t)n_ids,
+                           (const cg_sign_req*)ADDR(reqs), (uint64_t)n, (const cg_signable_tmpl*)ADDR(tmpls),
+                           (uint32_t)n_tmpls, (const uint8_t*)ADDR(arena), (uint64_t)arena_len,
+                           (const uint8_t*)ADDR(nonces), (uint8_t*)ADDR(sigs_out), (uint8_t*)ADDR(sig_len_out),
+                           (uint8_t*)ADDR(status_out));
+}
+
 /* Crypto.deriveKeyPair(privateKey, seed) over many seeds (Crypto.kt:646-771): cg_derive_keys (pool != 0:
  * cg_pool_derive_keys, the whole call on one healthy device, the next one on a device fault). parents:
  * cg_derive_parent records over keyData the binding wrote into the arena; secrets_out 32 bytes, pubs_out

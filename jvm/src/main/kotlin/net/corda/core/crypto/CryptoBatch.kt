@@ -29,6 +29,7 @@ import java.security.InvalidKeyException
 import java.security.KeyPair
 import java.security.PrivateKey
 import java.security.PublicKey
+import java.security.SecureRandom
 import java.security.SignatureException
 import java.util.concurrent.TimeUnit
 import java.util.concurrent.atomic.AtomicInteger
@@ -125,6 +126,17 @@ object CryptoBatch {
     private external fun nativeSignTxIds(ctx: Long, pool: Long, ids: ByteBuffer, nIds: Long, reqs: ByteBuffer, n: Long,
                                          tmpls: ByteBuffer, nTmpls: Int, arena: ByteBuffer, arenaLen: Long,
                                          sigsOut: ByteBuffer, statusOut: ByteBuffer): Int
+    /** cg_(pool_)ec_signers_load: the ECDSA signer set (separate from the Ed25519 one): a scheme byte (2 / 3)
+     *  and 32 bytes of d, big-endian, per key; pubsOut receives X || Y, statusOut the load status. */
+    private external fun nativeLoadEcSigners(ctx: Long, pool: Long, schemes: ByteBuffer, secrets: ByteBuffer, n: Int,
+                                             pubsOut: ByteBuffer, statusOut: ByteBuffer): Int
+    /** cg_(pool_)ec_sign_tx_ids: Crypto.doSign(keyPair, SignableData(id, metadata)) for ECDSA key pairs per 8-byte
+     *  request, with one 32-byte candidate k per request (nonces); a 72-byte slot (the DER bytes, then zeros), a
+     *  length byte and a status byte per request. */
+    private external fun nativeEcSignTxIds(ctx: Long, pool: Long, ids: ByteBuffer, nIds: Long, reqs: ByteBuffer, n: Long,
+                                           tmpls: ByteBuffer, nTmpls: Int, arena: ByteBuffer, arenaLen: Long,
+                                           nonces: ByteBuffer, sigsOut: ByteBuffer, sigLenOut: ByteBuffer,
+                                           statusOut: ByteBuffer): Int
     /** cg_(pool_)derive_keys: Crypto.deriveKeyPair(privateKey, seed) per 16-byte request (cg_derive_req: seed
      *  offset and length, parent) over 16-byte parents (cg_derive_parent: keyData offset and length, scheme);
      *  32 secret bytes, 64 public bytes, a status byte and a rehash count per request. */
@@ -228,7 +240,7 @@ object CryptoBatch {
             if (ctx != 0L || pool != 0L) nativeClose(ctx, pool)   // cg_close zeroes the signer store
             ctx = 0
             pool = 0
-            signerLock.withLock { signerHandle = 0 }
+            signerLock.withLock { signerHandle = 0; ecSignerHandle = 0 }
         }
     }
 
@@ -521,13 +533,17 @@ object CryptoBatch {
 
     /** NotaryService.sign(txId) (NotaryService.kt:77-80; BFTSMaRt.kt:249-255) for many ids in one call:
      *  Crypto.doSign(keyPair, SignableData(id, signatureMetadata)) each (Crypto.kt:415-422), byte for
-     *  byte what i2p's EdDSAEngine writes. A key pair that is not EDDSA_ED25519_SHA512 (BC draws ECDSA's k
-     *  and the PSS salt at random: nothing to reproduce), fewer ids than minBatch, a device fault, or
-     *  any non-zero status falls back to Crypto.doSign on the JVM for those ids, which also raises the
+     *  byte what i2p's EdDSAEngine writes. ECDSA_SECP256R1_SHA256 / ECDSA_SECP256K1_SHA256 key pairs go to the
+     *  device too (signAllEcdsa: k drawn here from a SecureRandom). A key pair of another scheme (BC draws
+     *  the PSS salt at random inside the signer), fewer ids than minBatch, a device fault, or any other
+     *  non-zero status falls back to Crypto.doSign on the JVM for those ids, which also raises the
      *  reference's own exceptions. */
-    fun signAll(keyPair: KeyPair, txIds: List<SecureHash>, signatureMetadata: SignatureMetadata): List<TransactionSignature> {
+    fun signAll(keyPair: KeyPair, txIds: List<SecureHash>, signatureMetadata: SignatureMetadata,
+                random: SecureRandom = ecNonceRandom): List<TransactionSignature> {
         fun onJvm(id: SecureHash) = Crypto.doSign(keyPair, SignableData(id, signatureMetadata))
         if (txIds.isEmpty()) return emptyList()
+        if (txIds.size >= config.minBatch && ecdsaSchemeId(keyPair) != 0)
+            return signAllEcdsa(keyPair, txIds, signatureMetadata, random)
         if (!isEd25519(keyPair) || txIds.size < config.minBatch) return txIds.map(::onJvm)
         requireAligned(keyPair)
         val (pre, suf) = signableTemplate(signatureMetadata)
@@ -566,6 +582,132 @@ object CryptoBatch {
     }
 
     private fun wipe(b: ByteBuffer) { for (i in 0 until b.capacity()) b.put(i, 0) }
+
+    // ---- ECDSA signing (include/cordagpu.h, "ECDSA signing"). A signer set of its own, in the open context
+    // (every device of the pool), beside the Ed25519 one and under the same lock.
+    private const val CG_NONCE_REJECTED = 9
+    private const val CG_EC_SIG_MAX = 72
+    private val ecNonceRandom = SecureRandom()
+    private var ecSignerKeys: List<KeyPair> = emptyList()
+    private var ecSignerHandle = 0L
+
+    /** The scheme id (2 / 3) when both halves are keys of the same ECDSA scheme, else 0. */
+    private fun ecdsaSchemeId(k: KeyPair): Int {
+        val s = Crypto.findSignatureScheme(k.private)
+        if (s != Crypto.findSignatureScheme(k.public)) return 0
+        return if (s == Crypto.ECDSA_SECP256R1_SHA256 || s == Crypto.ECDSA_SECP256K1_SHA256) s.schemeNumberID else 0
+    }
+
+    /** 32 big-endian bytes of a value below 2^256. */
+    private fun be32(v: BigInteger): ByteArray {
+        val b = v.toByteArray()
+        val out = ByteArray(32)
+        val n = minOf(b.size, 32)
+        System.arraycopy(b, b.size - n, out, 32 - n, n)
+        return out
+    }
+
+    /** With signerLock held, inside withHandles: the ECDSA set is in the open context. The device returns each
+     *  key's Q = d G, and a pair whose public half is another key's is refused here, as
+     *  Crypto.doSign(keyPair, signableData) refuses a misaligned pair (Crypto.kt:416-419). The buffer that
+     *  held d is zeroed before it is released. */
+    private fun ensureEcSigners(c: Long, p: Long): Boolean {
+        val h = if (c != 0L) c else p
+        if (ecSignerHandle == h) return true
+        val n = ecSignerKeys.size
+        val schemes = direct(n)
+        val secrets = direct(32 * n)
+        val pubs = direct(64 * n)
+        val st = direct(n)
+        val rc = try {
+            ecSignerKeys.forEach {
+                schemes.put(ecdsaSchemeId(it).toByte())
+                val d = be32((it.private as BCECPrivateKey).d)
+                secrets.put(d)
+                d.fill(0)
+            }
+            nativeLoadEcSigners(c, p, schemes, secrets, n, pubs, st)
+        } finally {
+            wipe(secrets)
+        }
+        if (rc != CG_OK) return false
+        val bad = ecSignerKeys.indices.filter { i ->
+            val q = (ecSignerKeys[i].public as BCECPublicKey).q.normalize()
+            val want = be32(q.affineXCoord.toBigInteger()) + be32(q.affineYCoord.toBigInteger())
+            val got = ByteArray(64).also { pubs.position(64 * i); pubs.get(it) }
+            st.get(i).toInt() != 0 || !got.contentEquals(want)
+        }
+        if (bad.isNotEmpty()) {   // as ensureSigners: the offending pairs leave the set, the next call loads the rest
+            ecSignerKeys = ecSignerKeys.filterIndexed { i, _ -> i !in bad }
+            ecSignerHandle = 0
+            throw IllegalArgumentException("ECDSA signer ${bad.first()}: the public key is not the private key's")
+        }
+        ecSignerHandle = h
+        return true
+    }
+
+    /** signAll for an ECDSA key pair: BC 1.57's ECDSASigner.generateSignature with the k candidates drawn here,
+     *  32 bytes per attempt as RandomDSAKCalculator.nextK's BigInteger(256, random) does. The device applies
+     *  BC's refusals; an id that comes back CG_NONCE_REJECTED is redrawn and resubmitted, the others keep
+     *  their signatures. A device fault or any other status falls back to Crypto.doSign on the JVM for that
+     *  id. The nonce buffer is zeroed after every call. */
+    private fun signAllEcdsa(keyPair: KeyPair, txIds: List<SecureHash>, signatureMetadata: SignatureMetadata,
+                             random: SecureRandom): List<TransactionSignature> {
+        fun onJvm(id: SecureHash) = Crypto.doSign(keyPair, SignableData(id, signatureMetadata))
+        val (pre, suf) = signableTemplate(signatureMetadata)
+        val arena = direct(pre.size + suf.size + 16)
+        val tmpls = direct(24)
+        arena.align4(); val po = arena.position().toLong(); arena.put(pre)
+        arena.align4(); val so = arena.position().toLong(); arena.put(suf)
+        tmpls.putLong(po).putLong(so).putInt(pre.size).putInt(suf.size)
+        val out = arrayOfNulls<TransactionSignature>(txIds.size)
+        var pending = txIds.indices.toList()
+        val draw = ByteArray(32)
+        while (pending.isNotEmpty()) {
+            val n = pending.size
+            val ids = direct(32 * n)
+            pending.forEach { ids.put(txIds[it].bytes) }
+            val reqs = direct(8 * n)
+            val nonces = direct(32 * n)
+            val sigs = direct(CG_EC_SIG_MAX * n)
+            val lens = direct(n)
+            val status = direct(n)
+            val rc = try {
+                for (j in 0 until n) { random.nextBytes(draw); nonces.put(draw) }
+                withHandles { c, p ->
+                    signerLock.withLock {
+                        var signer = ecSignerKeys.indexOfFirst { it.public == keyPair.public && it.private == keyPair.private }
+                        if (signer < 0 && ecSignerKeys.size < CG_SIGNERS_MAX) {
+                            ecSignerKeys = ecSignerKeys + keyPair
+                            ecSignerHandle = 0
+                            signer = ecSignerKeys.size - 1
+                        }
+                        if (signer < 0 || !ensureEcSigners(c, p)) CG_ERR_DEVICE
+                        else {
+                            for (j in 0 until n) reqs.putInt(8 * j, j).putShort(8 * j + 4, signer.toShort()).putShort(8 * j + 6, 0)
+                            nativeEcSignTxIds(c, p, ids, n.toLong(), reqs, n.toLong(), tmpls, 1, arena, arena.position().toLong(),
+                                              nonces, sigs, lens, status)
+                        }
+                    }
+                }
+            } finally {
+                wipe(nonces)
+                draw.fill(0)
+            }
+            val again = ArrayList<Int>()
+            pending.forEachIndexed { j, i ->
+                val st = if (rc == CG_OK) status.get(j).toInt() and 0xFF else -1
+                when (st) {
+                    0 -> out[i] = TransactionSignature(ByteArray(lens.get(j).toInt() and 0xFF).also { sigs.position(CG_EC_SIG_MAX * j); sigs.get(it) },
+                                                       keyPair.public, signatureMetadata)
+                    CG_NONCE_REJECTED -> again.add(i)
+                    else -> out[i] = onJvm(txIds[i])
+                }
+            }
+            pending = again
+        }
+        return out.map { it!! }
+    }
 
     /** deriveHMAC's keyData (Crypto.kt:759-771) and the scheme id of a private key the device derives
      *  from, or null: d.toByteArray() of a BC EC key on secp256r1 / secp256k1, geta() of an EdDSA key. */
