@@ -218,6 +218,25 @@ def lib():
                     L.cg_pool_ec_sign_tx_ids.argtypes = [vp, vp, u64, vp, u64, vp, u32, vp, u64, vp, vp, vp, vp,
                                                          ctypes.POINTER(cg_pool_stats)]
                     L.cg_pool_ec_sign_tx_ids.restype = i32
+            if hasattr(L, "cg_rsa_signers_load"):  # older builds (A/B variants) lack the RSA-PSS signer
+                L.cg_rsa_signers_load.argtypes = [vp, vp, u32, vp, u64, vp]
+                L.cg_rsa_signers_load.restype = i32
+                L.cg_rsa_signers_clear.argtypes = [vp]
+                L.cg_rsa_signers_clear.restype = i32
+                L.cg_rsa_sign_tx_ids.argtypes = [vp, vp, u64, vp, u64, vp, u32, vp, u64, vp, vp, vp, vp]
+                L.cg_rsa_sign_tx_ids.restype = i32
+                L.cg_rsa_sign_tx_ids_device.argtypes = [vp, vp, u64, vp, u64, vp, u32, vp, u64, vp, vp, vp, vp, vp]
+                L.cg_rsa_sign_tx_ids_device.restype = i32
+                L.cg_rsa_sign_batch.argtypes = [vp, vp, u64, vp, u64, vp, vp, vp, vp]
+                L.cg_rsa_sign_batch.restype = i32
+                if pool:
+                    L.cg_pool_rsa_signers_load.argtypes = [vp, vp, u32, vp, u64, vp]
+                    L.cg_pool_rsa_signers_load.restype = i32
+                    L.cg_pool_rsa_signers_clear.argtypes = [vp]
+                    L.cg_pool_rsa_signers_clear.restype = i32
+                    L.cg_pool_rsa_sign_tx_ids.argtypes = [vp, vp, u64, vp, u64, vp, u32, vp, u64, vp, vp, vp, vp,
+                                                          ctypes.POINTER(cg_pool_stats)]
+                    L.cg_pool_rsa_sign_tx_ids.restype = i32
             if hasattr(L, "cg_derive_keys"):  # older builds (A/B variants) lack key derivation
                 L.cg_derive_keys.argtypes = [vp, vp, u32, vp, u64, vp, u64, vp, vp, vp, vp]
                 L.cg_derive_keys.restype = i32

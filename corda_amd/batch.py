@@ -34,6 +34,7 @@ DERIVE_REQ_DTYPE = np.dtype([("seed_off", "<u8"), ("seed_len", "<u4"), ("parent"
 assert DERIVE_PARENT_DTYPE.itemsize == 16 and DERIVE_REQ_DTYPE.itemsize == 16
 DERIVE_HOST, DERIVE_BAD_PARENT, KEY_REJECTED = 6, 7, 8  # CG_DERIVE_HOST, CG_DERIVE_BAD_PARENT, CG_KEY_REJECTED
 NONCE_REJECTED = 9  # CG_NONCE_REJECTED: the ECDSA signer refused this item's k candidate; redraw it
+SIGN_CHECK_FAILED = 10  # CG_SIGN_CHECK_FAILED: the RSA signer's own s^e mod n did not give EM back; nothing written
 EC_SIG_MAX = 72     # CG_EC_SIG_MAX: bytes per ECDSA signature slot
 DERIVE_MAX_RETRIES = 4
 # tear-offs (cg_pmt_node / cg_filtered_leaf / cg_filtered_tx)

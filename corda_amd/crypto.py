@@ -42,14 +42,19 @@ schemes (below):
     key is not the private key's (the Abyte ``Engine.load_signers`` returns).
   * ``Crypto.sign_all(key_pair, tx_ids, metadata)`` -- the batch form: NotaryService.sign(txId)
     (NotaryService.kt:77-80) for many ids in one call.
-  An RSA or SPHINCS private key raises UnsupportedOperationException, as SPHINCS verification does, and so
-  does an ECDSA key when no ``random=`` is given: the mirror has no host signer (a JVM caller keeps its own
+  A SPHINCS private key raises UnsupportedOperationException, as SPHINCS verification does, and so does an
+  ECDSA or RSA key when no ``random=`` is given: the mirror has no host signer (a JVM caller keeps its own
   Crypto.doSign for those).
   * ``do_sign`` / ``do_sign_tx`` / ``sign_all`` with ``random=`` (a callable ``random(nbytes) -> bytes``, e.g.
     ``secrets.token_bytes``) sign with ECDSA_SECP256K1_SHA256 / ECDSA_SECP256R1_SHA256 keys: the host
     draws BC's BigInteger(256, random) candidates for k, the device signs (cg_ec_sign_batch /
     cg_ec_sign_tx_ids) and applies BC's refusals, and only the refused items are redrawn, one draw per
     attempt as in ECDSASigner.generateSignature. Returns BC's DER bytes.
+  * With ``random=`` they also sign with RSA_SHA256 keys (``PrivateKey(RSA_SHA256, pkcs8)``, the PKCS#8 DER
+    of getEncoded()): the host draws PSSSigner's 32-byte salt, ``random(32)`` exactly once per signature
+    and never again (BC never refuses a salt), and the device signs (cg_rsa_sign_batch /
+    cg_rsa_sign_tx_ids). Returns the k = ceil(bits(n) / 8) signature bytes. A key without CRT parts, or
+    whose public exponent is 2^32 or more (the C ABI's e is 32 bits), raises UnsupportedOperationException.
 
 Key derivation (Crypto.kt:646-771), all three curves, on the GPU:
   * ``Crypto.derive_key_pair(private_key, seed, scheme=None)`` -- deriveKeyPair: a scheme that is not
@@ -137,7 +142,8 @@ class PublicKey:
 class PrivateKey:
     """A private key as the node's key store holds it. EDDSA_ED25519_SHA512: ``encoded`` is the 32-byte
     seed of EdDSAPrivateKeySpec(seed). ECDSA_SECP256R1_SHA256 / ECDSA_SECP256K1_SHA256: ``encoded`` is the
-    32-byte big-endian d of the BC EC private key."""
+    32-byte big-endian d of the BC EC private key. RSA_SHA256: ``encoded`` is the PKCS#8 DER of
+    getEncoded() (a BCRSAPrivateCrtKey)."""
     scheme: int
     encoded: bytes
 
@@ -202,6 +208,9 @@ class _Crypto:
         self._ec_signers = []    # the ECDSA private keys loaded into the engine's ECDSA signer set
         self._ec_signer_pub = []  # their X || Y
         self._ec_signer_engine = None
+        self._rsa_signers = []    # the RSA private keys loaded into the engine's RSA signer set
+        self._rsa_signer_pub = []  # their (n, e)
+        self._rsa_signer_engine = None
 
     def engine(self):
         with self._lock:
@@ -410,6 +419,9 @@ class _Crypto:
             if len(private_key.encoded) != 32:
                 raise InvalidKeyException("an ECDSA private key is 32 bytes of d, big-endian")
             return
+        if private_key.scheme == RSA_SHA256 and random is not None:
+            self._rsa_parts(private_key)
+            return
         if private_key.scheme != EDDSA_ED25519_SHA512:
             raise UnsupportedOperationException(
                 f"no signer for scheme {SCHEME_CODE_NAMES[private_key.scheme]} in this mirror; the JVM caller keeps "
@@ -449,8 +461,49 @@ class _Crypto:
             i = self._ec_signers.index(private_key)
             return i, self._ec_signer_pub[i]
 
+    @staticmethod
+    def _rsa_parts(private_key):
+        """The CRT parts of a PKCS#8 RSA key, or the mirror's refusals."""
+        from . import hostverify
+        key = hostverify.rsa_decode_private_key(private_key.encoded)
+        if key["e"] >= 1 << 32:
+            raise UnsupportedOperationException("an RSA public exponent of 2^32 or more does not fit the C ABI's "
+                                                "32-bit e; the JVM caller keeps its own Crypto.doSign")
+        return key
+
+    def _rsa_signer(self, private_key):
+        """(signer index, (n, e)) of a key in the engine's RSA signer set, loading it when it is new."""
+        from .engine import RsaSignerKey
+        eng = self.engine()
+        with self._lock:
+            if self._rsa_signer_engine is not eng:
+                self._rsa_signers, self._rsa_signer_pub, self._rsa_signer_engine = [], [], eng
+            if private_key not in self._rsa_signers:
+                keys = self._rsa_signers + [private_key]
+                parts = [self._rsa_parts(k) for k in keys]
+                be = lambda v: v.to_bytes(max(1, (v.bit_length() + 7) // 8), "big")  # noqa: E731
+                st = eng.load_rsa_signers([RsaSignerKey(be(k["n"]), k["e"], be(k["p"]), be(k["q"]), be(k["dp"]),
+                                                        be(k["dq"]), be(k["qinv"])) for k in parts])
+                if any(int(x) != 0 for x in st):
+                    self._rsa_signers, self._rsa_signer_pub = [], []  # the device set was replaced
+                    raise InvalidKeyException("the device refused an RSA private key")
+                self._rsa_signer_pub, self._rsa_signers = [(k["n"], k["e"]) for k in parts], keys
+            i = self._rsa_signers.index(private_key)
+            return i, self._rsa_signer_pub[i]
+
+    def _rsa_salts(self, n, random):
+        """PSSSigner's random.nextBytes(salt): one 32-byte draw per signature, never redrawn."""
+        salts = np.zeros(32 * n, dtype=np.uint8)
+        for j in range(n):
+            s = random(32)
+            if len(s) != 32:
+                raise ValueError("random(32) must return 32 bytes")
+            salts[32 * j:32 * j + 32] = np.frombuffer(s, dtype=np.uint8)
+        return salts
+
     def forget_signers(self):
-        """Zeroes and frees the engine's signer sets (cg_signers_clear, cg_ec_signers_clear)."""
+        """Zeroes and frees the engine's signer sets (cg_signers_clear, cg_ec_signers_clear,
+        cg_rsa_signers_clear)."""
         with self._lock:
             if self._signer_engine is not None:
                 self._signer_engine.clear_signers()
@@ -458,6 +511,9 @@ class _Crypto:
             if self._ec_signer_engine is not None:
                 self._ec_signer_engine.clear_ec_signers()
             self._ec_signers, self._ec_signer_pub, self._ec_signer_engine = [], [], None
+            if self._rsa_signer_engine is not None:
+                self._rsa_signer_engine.clear_rsa_signers()
+            self._rsa_signers, self._rsa_signer_pub, self._rsa_signer_engine = [], [], None
 
     def _ec_sign_loop(self, n, random, call):
         """ECDSASigner.generateSignature's loop over a batch: every pending item gets one 32-byte draw
@@ -494,9 +550,18 @@ class _Crypto:
 
     def do_sign(self, private_key, clear_data, random=None):
         """Crypto.doSign(privateKey, clearData) (Crypto.kt:395-402). ``random``: see the module text; without
-        it an ECDSA key raises UnsupportedOperationException."""
+        it an ECDSA or RSA key raises UnsupportedOperationException."""
         clear_data = bytes(clear_data)
         self._sign_scheme(private_key, len(clear_data), random)
+        if private_key.scheme == RSA_SHA256:
+            i, _ = self._rsa_signer(private_key)
+            salts = self._rsa_salts(1, random)
+            try:
+                sigs, ln, st = self.engine().sign_rsa([(i, clear_data)], salts)
+            finally:
+                salts[:] = 0
+            self._sign_status(int(st[0]))
+            return sigs[0, :int(ln[0])].tobytes()
         if private_key.scheme in _ECDSA_SCHEMES:
             i, _ = self._ec_signer(private_key)
             return self._ec_sign_loop(1, random, lambda pend, k: self.engine().sign_ec([(i, clear_data)], k))[0]
@@ -513,6 +578,12 @@ class _Crypto:
             raise IllegalArgumentException(f"Metadata schemeCodeName: {SCHEME_CODE_NAMES[sig_meta]} is not aligned with "
                                            f"the key type: {SCHEME_CODE_NAMES[sig_key]}.")
         self._sign_scheme(key_pair.private, 1, random)
+        if key_pair.private.scheme == RSA_SHA256:
+            from . import hostverify
+            i, ne = self._rsa_signer(key_pair.private)
+            if hostverify.rsa_decode_key(key_pair.public.encoded) != ne:
+                raise IllegalArgumentException("The public key of this pair is not the private key's.")
+            return i
         if key_pair.private.scheme in _ECDSA_SCHEMES:
             i, xy = self._ec_signer(key_pair.private)
             if K.canonical_spki(key_pair.private.scheme, B.KEY_RAW, xy) != key_pair.public.spki():
@@ -537,6 +608,20 @@ class _Crypto:
         if not tx_ids:
             return []
         pv, sid = metadata
+        if key_pair.private.scheme == RSA_SHA256:
+            b = B.SignRequestBuilder()
+            t = b.template(*signable.template(pv, sid))
+            for tx_id in tx_ids:
+                b.add_request(signer, b.tx_id(tx_id), t)
+            salts = self._rsa_salts(len(tx_ids), random)
+            try:
+                sigs, ln, st = self.engine().sign_rsa_tx_ids(b.build(), salts)
+            finally:
+                salts[:] = 0
+            for s in st:
+                self._sign_status(int(s))
+            return [TransactionSignature(sigs[j, :int(ln[j])].tobytes(), key_pair.public, pv, sid)
+                    for j in range(len(tx_ids))]
         if key_pair.private.scheme in _ECDSA_SCHEMES:
             def call(pending, nonces):
                 b = B.SignRequestBuilder()

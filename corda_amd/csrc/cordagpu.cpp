@@ -194,6 +194,11 @@ struct cg_ctx : cg::CallState<HipStreams> {
   // every sign call. Separate from the Ed25519 set above.
   DevBuf ec_signers, signecws;
   uint32_t n_ec_signers = 0;
+  // The RSA-PSS signer (sign_rsa.hip). rsa_signers: every loaded key's CRT parts and Montgomery constants,
+  // an allocation of its own made by cg_rsa_signers_load and zeroed before it is freed; signrsaws: a
+  // chunk's H and salts, zeroed behind every sign call. The third set, separate from the two above.
+  DevBuf rsa_signers, signrsaws;
+  uint32_t n_rsa_signers = 0;
   // host-buffer verify: one event per pipeline chunk (seg); timing events for cg_stats (tev)
   // a second stream on a hardware queue of its own, idle in every schedule: the CG_HOST_TRACE marker
   // "tables built" waits there (launch_chunked)
@@ -887,6 +892,15 @@ static void ec_signers_drop(cg_ctx* c) {
   c->ec_signers.release();
 }
 
+static void rsa_signers_drop(cg_ctx* c) {
+  c->n_rsa_signers = 0;
+  if (!c->rsa_signers.p) return;
+  (void)hipDeviceSynchronize();
+  (void)hipMemset(c->rsa_signers.p, 0, c->rsa_signers.cap);
+  (void)hipDeviceSynchronize();
+  c->rsa_signers.release();
+}
+
 void cg_close(cg_ctx* c) {
   if (!c) return;
   if (c->counted) --g_live_ctx;
@@ -894,8 +908,10 @@ void cg_close(cg_ctx* c) {
   if (c->stream) hipStreamSynchronize(c->stream);
   signers_drop(c);
   ec_signers_drop(c);
+  rsa_signers_drop(c);
   c->signws.release();
   c->signecws.release();
+  c->signrsaws.release();
   c->derivews.release();
   c->keyprep.release();
   c->itemws.release();
@@ -2469,6 +2485,194 @@ int cg_ec_sign_batch(cg_ctx* c, const cg_sign_item* items, uint64_t n, const uin
                        sig_len_out});
 }
 
+// ---------------------------------------------------------------- RSA-PSS signing (sign_rsa.hip)
+static_assert(sizeof(cg_rsa_signer) == 52, "cg_rsa_signer layout");
+
+// With the ctx lock held. The store: [signer records][cg_rsa_signer table][secret bytes][status n], each
+// part 256-aligned; the table and the secret bytes are zeroed on the stream right behind the expansion.
+static int rsa_signers_load_locked(cg_ctx* c, const cg_rsa_signer* signers, uint32_t n, const uint8_t* secrets,
+                                   uint64_t secrets_len, uint8_t* status_out) {
+  if (const int rc = enter(c, "cg_rsa_signers_load")) return rc;
+  rsa_signers_drop(c);
+  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  const size_t recs_b = al(cg::rsa_signer_bytes() * n), tab_b = al(sizeof(cg_rsa_signer) * (size_t)n),
+               sec_b = al(secrets_len + 4);
+  HIP_TRY(c->rsa_signers.ensure_exact(recs_b + tab_b + sec_b + al(n)), "hipMalloc(RSA signers)");
+  uint8_t* base = (uint8_t*)c->rsa_signers.p;
+  uint8_t *d_tab = base + recs_b, *d_sec = d_tab + tab_b, *d_st = d_sec + sec_b;
+  hipStream_t s = c->stream;
+  hipError_t e;
+  {
+    Call call(c, Call::kHost);
+    e = call.open();
+    if (e == hipSuccess) e = hipMemsetAsync(base, 0, recs_b + tab_b + sec_b + al(n), s);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_tab, signers, sizeof(cg_rsa_signer) * (size_t)n, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess && secrets_len) e = hipMemcpyAsync(d_sec, secrets, secrets_len, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = cg::launch_rsa_signer_expand(d_tab, n, d_sec, secrets_len, base, d_st, s);
+    if (e == hipSuccess) e = hipMemsetAsync(d_tab, 0, tab_b + sec_b, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(status_out, d_st, n, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = call.close();
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+  }
+  if (e != hipSuccess) {
+    rsa_signers_drop(c);  // nothing half-loaded, no secret left behind
+    return hip_fail(e, "cg_rsa_signers_load");
+  }
+  c->n_rsa_signers = n;
+  return CG_OK;
+}
+
+static int rsa_signers_load_args(const char* fn, const cg_rsa_signer* signers, uint32_t n, const uint8_t* secrets,
+                                 uint64_t secrets_len, const uint8_t* status_out) {
+  if (n == 0 || n > CG_SIGNERS_MAX) return fail(CG_ERR_ARG, "%s: 1 .. CG_SIGNERS_MAX signers", fn);
+  if (!signers || !status_out || (secrets_len && !secrets)) return fail(CG_ERR_ARG, "%s: NULL buffer", fn);
+  if (secrets_len >= (1ull << 32)) return fail(CG_ERR_ARG, "%s: secrets_len must be below 2^32", fn);
+  return CG_OK;
+}
+
+int cg_rsa_signers_load(cg_ctx* c, const cg_rsa_signer* signers, uint32_t n, const uint8_t* secrets,
+                        uint64_t secrets_len, uint8_t* status_out) {
+  if (!c) return fail(CG_ERR_ARG, "cg_rsa_signers_load: ctx is NULL");
+  if (const int a = rsa_signers_load_args("cg_rsa_signers_load", signers, n, secrets, secrets_len, status_out)) return a;
+  std::lock_guard<std::mutex> g(c->mu);
+  return rsa_signers_load_locked(c, signers, n, secrets, secrets_len, status_out);
+}
+
+int cg_rsa_signers_clear(cg_ctx* c) {
+  if (!c) return fail(CG_ERR_ARG, "cg_rsa_signers_clear: ctx is NULL");
+  std::lock_guard<std::mutex> g(c->mu);
+  HIP_TRY(hipSetDevice(c->device), "hipSetDevice");
+  rsa_signers_drop(c);
+  return CG_OK;
+}
+
+// One RSA-PSS sign call: a SignReq (sigs: the 512-byte slots) with the salts and the 16-bit lengths.
+struct SignRsaReq {
+  SignReq q;
+  const uint8_t* salts;
+  uint16_t* sig_len;
+};
+
+static int sign_rsa_args(const char* fn, cg_ctx* c, const SignRsaReq& r, bool host) {
+  if (const int a = sign_args(fn, c, r.q, host)) return a;
+  if (r.q.n && (!r.salts || !r.sig_len)) return fail(CG_ERR_ARG, "%s: NULL salt / length buffer", fn);
+  return CG_OK;
+}
+
+static hipError_t ensure_sign_rsa_ws(cg_ctx* c, const SignReq& q, uint64_t slot) {
+  return ensure_all({{&c->signrsaws, cg::sign_rsa_ws_bytes(chunk_of(c, q.n))},
+                     {&c->msgs, q.fused ? cg::tx_msgs_head(q.n_tmpls, slot) : 1},
+                     {&c->tmpls, sizeof(cg_signable_tmpl) * (q.n_tmpls ? q.n_tmpls : 1)}});
+}
+
+// Every launch of the call over the device tables `r` on `s` (launch_sign_ec_call's shape); the workspace is
+// zeroed behind the last kernel whatever happened before (it holds the last chunk's H and salts).
+static hipError_t launch_sign_rsa_call(cg_ctx* c, const SignRsaReq& r, uint64_t slot, hipStream_t s) {
+  const SignReq& d = r.q;
+  hipError_t e = hipSuccess;
+  const cg_signable_tmpl* dt = (const cg_signable_tmpl*)c->tmpls.p;
+  if (d.fused) {
+    if (d.n_tmpls) e = hipMemcpyAsync(c->tmpls.p, d.tmpls, sizeof(cg_signable_tmpl) * d.n_tmpls, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess)
+      e = cg::launch_tx_sig_templates(dt, d.n_tmpls, d.arena, d.arena_len, slot, d.ids, d.n_ids, (uint8_t*)c->msgs.p, s);
+  }
+  const std::vector<uint64_t> bounds = cg::equal_bounds(d.n, chunk_of(c, d.n));
+  for (size_t k = 0; e == hipSuccess && k + 1 < bounds.size(); ++k) {
+    const uint64_t first = bounds[k], cnt = bounds[k + 1] - first;
+    const cg::SignRsaArgs a = {(const uint8_t*)d.reqs + first * d.req_bytes(), cnt, d.fused, c->rsa_signers.p,
+                               c->n_rsa_signers, d.arena, d.arena_len, (const uint8_t*)c->msgs.p, dt, d.n_tmpls, d.n_ids,
+                               r.salts + 32 * first, d.sigs + CG_RSA_SIG_MAX * first, r.sig_len + first,
+                               d.status + first, c->signrsaws.p};
+    e = cg::launch_sign_rsa(a, s);
+  }
+  const hipError_t z = hipMemsetAsync(c->signrsaws.p, 0, cg::sign_rsa_ws_bytes(chunk_of(c, d.n)), s);
+  return e != hipSuccess ? e : z;
+}
+
+static int sign_rsa_device(const char* fn, cg_ctx* c, const SignRsaReq& d, void* hip_stream) {
+  if (const int a = sign_rsa_args(fn, c, d, false)) return a;
+  if (d.q.n == 0) return CG_OK;
+  std::lock_guard<std::mutex> g(c->mu);
+  if (const int rc = enter(c, fn)) return rc;
+  if (c->n_rsa_signers == 0) return fail(CG_ERR_ARG, "%s: no RSA signers loaded (cg_rsa_signers_load)", fn);
+  const uint64_t slot = tmpl_slot(d.q.tmpls, d.q.n_tmpls);
+  HIP_TRY(ensure_sign_rsa_ws(c, d.q, slot), "hipMalloc(sign workspace)");
+  Call call(c, Call::kDevice);
+  HIP_TRY(call.open(hip_stream), "hipStreamWaitEvent");
+  HIP_TRY(launch_sign_rsa_call(c, d, slot, call.stream()), "launch_sign_rsa");
+  HIP_TRY(call.close(), "hipEventRecord");
+  return CG_OK;
+}
+
+// A host-buffer call with the ctx lock held. Staged in aux0: [signatures 512 n][salts 32 n][lengths 2 n];
+// the staged salts are zeroed on the stream behind the kernels, whatever happened before.
+static int sign_rsa_host_locked(const char* fn, cg_ctx* c, const SignRsaReq& h) {
+  if (const int rc = enter(c, fn)) return rc;
+  if (c->n_rsa_signers == 0) return fail(CG_ERR_ARG, "%s: no RSA signers loaded (cg_rsa_signers_load)", fn);
+  const SignReq& q = h.q;
+  const uint64_t slot = tmpl_slot(q.tmpls, q.n_tmpls);
+  HIP_TRY(ensure_sign_rsa_ws(c, q, slot), "hipMalloc(sign workspace)");
+  hipStream_t s = c->stream;
+  Call call(c, Call::kHost);
+  HIP_TRY(call.open(), "hipStreamWaitEvent");
+  HIP_TRY(stage(c->items, q.reqs, q.req_bytes() * q.n, s), "H2D sign requests");
+  HIP_TRY(stage(c->arena, q.arena, q.arena_len, s, arena_room(q.arena_len)), "H2D arena");
+  HIP_TRY(stage(c->h_ids, q.ids, 32 * q.n_ids, s), "H2D ids");
+  HIP_TRY(c->aux0.ensure((CG_RSA_SIG_MAX + 32 + 2) * q.n), "hipMalloc(signatures)");
+  HIP_TRY(c->status.ensure(q.n), "hipMalloc(status)");
+  SignRsaReq d = h;
+  d.q.reqs = c->items.p;
+  d.q.arena = (const uint8_t*)c->arena.p;
+  d.q.ids = (const uint8_t*)c->h_ids.p;
+  d.q.sigs = (uint8_t*)c->aux0.p;
+  d.q.status = (uint8_t*)c->status.p;
+  uint8_t* d_salts = d.q.sigs + CG_RSA_SIG_MAX * q.n;
+  d.salts = d_salts;
+  d.sig_len = (uint16_t*)(d_salts + 32 * q.n);
+  hipError_t e = hipMemcpyAsync(d_salts, h.salts, 32 * q.n, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = launch_sign_rsa_call(c, d, slot, s);
+  const hipError_t z = hipMemsetAsync(d_salts, 0, 32 * q.n, s);
+  if (e == hipSuccess) e = z;
+  HIP_TRY(e, "launch_sign_rsa");
+  HIP_TRY(hipMemcpyAsync(q.sigs, d.q.sigs, CG_RSA_SIG_MAX * q.n, hipMemcpyDeviceToHost, s), "D2H signatures");
+  HIP_TRY(hipMemcpyAsync(h.sig_len, d.sig_len, 2 * q.n, hipMemcpyDeviceToHost, s), "D2H signature lengths");
+  HIP_TRY(hipMemcpyAsync(q.status, d.q.status, q.n, hipMemcpyDeviceToHost, s), "D2H status");
+  HIP_TRY(call.close(), "hipEventRecord");
+  HIP_TRY(hipStreamSynchronize(s), "hipStreamSynchronize");
+  return CG_OK;
+}
+
+static int sign_rsa_host(const char* fn, cg_ctx* c, const SignRsaReq& h) {
+  if (const int a = sign_rsa_args(fn, c, h, true)) return a;
+  if (h.q.n == 0) return CG_OK;
+  std::lock_guard<std::mutex> g(c->mu);
+  return sign_rsa_host_locked(fn, c, h);
+}
+
+int cg_rsa_sign_tx_ids(cg_ctx* c, const uint8_t* ids, uint64_t n_ids, const cg_sign_req* reqs, uint64_t n,
+                       const cg_signable_tmpl* tmpls, uint32_t n_tmpls, const uint8_t* arena, uint64_t arena_len,
+                       const uint8_t* salts, uint8_t* sigs_out, uint16_t* sig_len_out, uint8_t* status_out) {
+  return sign_rsa_host("cg_rsa_sign_tx_ids", c,
+                       {{reqs, n, true, ids, n_ids, tmpls, n_tmpls, arena, arena_len, sigs_out, status_out}, salts,
+                        sig_len_out});
+}
+
+int cg_rsa_sign_tx_ids_device(cg_ctx* c, const uint8_t* d_ids, uint64_t n_ids, const cg_sign_req* d_reqs, uint64_t n,
+                              const cg_signable_tmpl* tmpls, uint32_t n_tmpls, const uint8_t* d_arena, uint64_t arena_len,
+                              const uint8_t* d_salts, uint8_t* d_sigs, uint16_t* d_sig_len, uint8_t* d_status,
+                              void* hip_stream) {
+  return sign_rsa_device("cg_rsa_sign_tx_ids_device", c,
+                         {{d_reqs, n, true, d_ids, n_ids, tmpls, n_tmpls, d_arena, arena_len, d_sigs, d_status}, d_salts,
+                          d_sig_len}, hip_stream);
+}
+
+int cg_rsa_sign_batch(cg_ctx* c, const cg_sign_item* items, uint64_t n, const uint8_t* arena, uint64_t arena_len,
+                      const uint8_t* salts, uint8_t* sigs_out, uint16_t* sig_len_out, uint8_t* status_out) {
+  return sign_rsa_host("cg_rsa_sign_batch", c,
+                       {{items, n, false, nullptr, 0, nullptr, 0, arena, arena_len, sigs_out, status_out}, salts,
+                        sig_len_out});
+}
+
 // ---------------------------------------------------------------- key derivation (derive_keys.hip)
 static_assert(sizeof(cg_derive_parent) == 16 && sizeof(cg_derive_req) == 16, "derive request layouts");
 
@@ -2902,6 +3106,76 @@ int cg_pool_ec_sign_tx_ids(cg_pool* p, const uint8_t* ids, uint64_t n_ids, const
   const int rc = pool_call_locked(p, 1, &unit, stats, fn, [&](cg_ctx* c, uint64_t, uint64_t) {
     if (!c->fault && c->n_ec_signers == 0) return fail(CG_ERR_NOMEM, "%s: this slot holds no signer set (its load failed)", fn);
     const int r = sign_ec_host_locked(fn, c, h);
+    if (r != CG_OK) blank();
+    return r;
+  });
+  if (stats) stats->not_run = rc == CG_OK ? 0 : n;
+  return rc;
+}
+
+// The RSA signer set on every slot, and cg_rsa_sign_tx_ids whole on one live slot (as the ECDSA forms above).
+int cg_pool_rsa_signers_load(cg_pool* p, const cg_rsa_signer* signers, uint32_t n, const uint8_t* secrets,
+                             uint64_t secrets_len, uint8_t* status_out) {
+  const char* fn = "cg_pool_rsa_signers_load";
+  if (!p) return fail(CG_ERR_ARG, "%s: pool is NULL", fn);
+  if (p->ctx.empty()) return fail(CG_ERR_ARG, "%s: empty pool", fn);
+  if (const int a = rsa_signers_load_args(fn, signers, n, secrets, secrets_len, status_out)) return a;
+  std::lock_guard<std::mutex> g(p->mu);
+  std::vector<uint8_t> st(n);
+  bool any = false;
+  int last = CG_ERR_DEVICE;
+  for (size_t k = 0; k < p->ctx.size(); ++k) {
+    cg_ctx* c = p->ctx[k];
+    std::lock_guard<std::mutex> gc(c->mu);
+    const bool drill = c->fault;  // as cg_pool_signers_load: loaded all the same, for the moment the
+    c->fault = false;             // drill is cleared
+    const int rc = rsa_signers_load_locked(c, signers, n, secrets, secrets_len, any ? st.data() : status_out);
+    c->fault = drill;
+    if (rc == CG_OK) any = true;
+    else if (rc == CG_ERR_DEVICE) p->healthy[k] = 0;
+    if (rc != CG_OK) last = rc;
+  }
+  return any ? CG_OK : last;
+}
+
+int cg_pool_rsa_signers_clear(cg_pool* p) {
+  if (!p) return fail(CG_ERR_ARG, "cg_pool_rsa_signers_clear: pool is NULL");
+  std::lock_guard<std::mutex> g(p->mu);
+  for (cg_ctx* c : p->ctx) {
+    std::lock_guard<std::mutex> gc(c->mu);
+    if (hipSetDevice(c->device) == hipSuccess) rsa_signers_drop(c);
+  }
+  return CG_OK;
+}
+
+int cg_pool_rsa_sign_tx_ids(cg_pool* p, const uint8_t* ids, uint64_t n_ids, const cg_sign_req* reqs, uint64_t n,
+                            const cg_signable_tmpl* tmpls, uint32_t n_tmpls, const uint8_t* arena, uint64_t arena_len,
+                            const uint8_t* salts, uint8_t* sigs_out, uint16_t* sig_len_out, uint8_t* status_out,
+                            cg_pool_stats* stats) {
+  const char* fn = "cg_pool_rsa_sign_tx_ids";
+  if (!p) return fail(CG_ERR_ARG, "%s: pool is NULL", fn);
+  if (p->ctx.empty()) return fail(CG_ERR_ARG, "%s: empty pool", fn);
+  const SignRsaReq h = {{reqs, n, true, ids, n_ids, tmpls, n_tmpls, arena, arena_len, sigs_out, status_out}, salts,
+                        sig_len_out};
+  if (const int a = sign_rsa_args(fn, p->ctx[0], h, true)) return a;
+  if (n == 0) return CG_OK;
+  std::lock_guard<std::mutex> g(p->mu);  // one scope: the signer sets cannot change between the check and the call
+  bool any = false;
+  for (cg_ctx* c : p->ctx) {
+    std::lock_guard<std::mutex> gc(c->mu);
+    any = any || c->n_rsa_signers != 0;
+  }
+  if (!any) return fail(CG_ERR_ARG, "%s: no RSA signers loaded (cg_pool_rsa_signers_load)", fn);
+  auto blank = [&]() {
+    memset(status_out, CG_NOT_RUN, n);
+    memset(sigs_out, 0, CG_RSA_SIG_MAX * n);
+    memset(sig_len_out, 0, 2 * n);
+  };
+  blank();
+  uint8_t unit = CG_NOT_RUN;
+  const int rc = pool_call_locked(p, 1, &unit, stats, fn, [&](cg_ctx* c, uint64_t, uint64_t) {
+    if (!c->fault && c->n_rsa_signers == 0) return fail(CG_ERR_NOMEM, "%s: this slot holds no signer set (its load failed)", fn);
+    const int r = sign_rsa_host_locked(fn, c, h);
     if (r != CG_OK) blank();
     return r;
   });

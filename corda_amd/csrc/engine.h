@@ -214,6 +214,28 @@ struct SignEcArgs {
   const void* d_btab;
 };
 
+// One chunk of an RSA-PSS sign call (sign_rsa.hip): SignArgs' request forms over the context's RSA signer
+// store, the chunk's salts (32 bytes per request) and its 512-byte signature slots, 16-bit lengths and
+// status bytes. d_ws holds sign_rsa_ws_bytes(n) bytes.
+struct SignRsaArgs {
+  const void* d_reqs;
+  uint64_t n;
+  bool fused;
+  const void* d_signers;
+  uint32_t n_signers;
+  const uint8_t* d_arena;
+  uint64_t arena_len;
+  const uint8_t* d_msgs;
+  const cg_signable_tmpl* d_tmpls;
+  uint32_t n_tmpls;
+  uint64_t n_ids;
+  const uint8_t* d_salts;
+  uint8_t* d_sigs;
+  uint16_t* d_sig_len;
+  uint8_t* d_status;
+  void* d_ws;
+};
+
 // One chunk of a key-derivation call (derive_keys.hip). With d_reqs: cg_derive_keys, d_secrets is
 // written. Without: cg_public_keys, d_secrets holds the private keys of `scheme` and is only read.
 // d_ws holds derive_ws_bytes(n_parents, n) bytes and starts with the call's parent midstates
@@ -287,6 +309,7 @@ using cgt::ItemArgs;
 using cgt::PendingTabs;
 using cgt::SignArgs;
 using cgt::SignEcArgs;
+using cgt::SignRsaArgs;
 using cgt::SigTable;
 using cgt::StageTimer;
 using cgt::VerifyReq;
@@ -383,6 +406,18 @@ size_t rsa_keys_bytes(uint32_t n_keys);
 size_t rsa_list_bytes(uint64_t n_items);
 hipError_t launch_rsa_keyprep(const VerifyReq& r, void* d_rsakeys, hipStream_t stream);
 hipError_t launch_rsa_items(const VerifyReq& r, const void* d_rsakeys, void* d_rsalist, hipStream_t stream);
+
+// The RSA-PSS signer (sign_rsa.hip; BC's PSSSigner.generateSignature behind Crypto.doSign, the salt given by
+// the caller; radix-independent). The signer store holds rsa_signer_bytes() per signer
+// (launch_rsa_signer_expand fills it from the cg_rsa_signer table and the staged secret bytes, which must be
+// readable to secrets_len rounded up to 4, and writes a load status per signer); launch_sign_rsa signs one
+// chunk over a workspace of sign_rsa_ws_bytes(n) bytes, which holds secrets (H and the salt of every
+// request) until the caller zeroes it.
+size_t rsa_signer_bytes();
+size_t sign_rsa_ws_bytes(uint64_t n);
+hipError_t launch_rsa_signer_expand(const void* d_signers_in, uint32_t n, const uint8_t* d_secrets, uint64_t secrets_len,
+                                    void* d_store, uint8_t* d_status, hipStream_t stream);
+hipError_t launch_sign_rsa(const SignRsaArgs& a, hipStream_t stream);
 
 // Hashing kernels
 hipError_t launch_sha256(const cg_span* d_spans, uint64_t n, const uint8_t* d_arena, uint64_t arena_len,

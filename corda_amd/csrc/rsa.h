@@ -317,3 +317,54 @@ CG_HD bool rsa_pss_check(uint8_t* em, uint32_t block_len, uint32_t em_bits, cons
   for (uint32_t c = 0; 32u * c < db_len; ++c) rsa_pss_unmask_block(em, db_len, c);
   return rsa_pss_post(em, block_len, em_bits, mhash);
 }
+
+// ---- EMSA-PSS encoding (RFC 8017 9.1.1 as BC 1.57 PSSSigner.generateSignature does it, with the
+// salt given; corda_amd/hostverify.py rsa_pss_sign restates it). mhash, salt and h are 8 big-endian
+// words each; they are read through pointers, never indexed in registers.
+// H = SHA-256(0^8 || mHash || salt)
+CG_HD void rsa_pss_h(uint32_t h[8], const uint32_t* mhash, const uint32_t* salt) {
+  uint32_t w[16];
+  w[0] = w[1] = 0;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) w[2 + i] = mhash[i];
+#pragma unroll
+  for (int i = 0; i < 6; ++i) w[10 + i] = salt[i];
+  sha256_init(h);
+  sha256_compress(h, w);
+  w[0] = salt[6];
+  w[1] = salt[7];
+  w[2] = 0x80000000u;
+#pragma unroll
+  for (int i = 3; i < 15; ++i) w[i] = 0;
+  w[15] = 72u * 8u;
+  sha256_compress(h, w);
+}
+// Byte `pos` of PS || 01 || salt || H || BC before the masking (block_len >= 66).
+CG_HD uint32_t rsa_pss_plain_byte(uint32_t pos, uint32_t block_len, const uint32_t* salt, const uint32_t* h) {
+  const uint32_t db_len = block_len - RSA_HASH_LEN - 1u;
+  const uint32_t ps_len = db_len - RSA_SALT_LEN - 1u;
+  if (pos < ps_len) return 0u;
+  if (pos == ps_len) return 1u;
+  if (pos < db_len) {
+    const uint32_t j = pos - ps_len - 1u;
+    return (salt[j >> 2] >> (24u - 8u * (j & 3u))) & 0xffu;
+  }
+  if (pos < db_len + RSA_HASH_LEN) {
+    const uint32_t j = pos - db_len;
+    return (h[j >> 2] >> (24u - 8u * (j & 3u))) & 0xffu;
+  }
+  return RSA_TRAILER;
+}
+// The bits of EM above emBits (BC: block[0] &= 0xff >> (8 block_len - emBits))
+CG_HD void rsa_pss_clear_top(uint8_t* em, uint32_t block_len, uint32_t em_bits) {
+  em[0] &= (uint8_t)(0xFFu >> (8u * block_len - em_bits));
+}
+// The whole encoding on one thread: em[0, block_len).
+CG_HD void rsa_pss_encode(uint8_t* em, uint32_t block_len, uint32_t em_bits, const uint32_t* mhash, const uint32_t* salt) {
+  uint32_t h[8];
+  rsa_pss_h(h, mhash, salt);
+  for (uint32_t pos = 0; pos < block_len; ++pos) em[pos] = (uint8_t)rsa_pss_plain_byte(pos, block_len, salt, h);
+  const uint32_t db_len = block_len - RSA_HASH_LEN - 1u;
+  for (uint32_t c = 0; 32u * c < db_len; ++c) rsa_pss_unmask_block(em, db_len, c);  // its own inverse
+  rsa_pss_clear_top(em, block_len, em_bits);
+}

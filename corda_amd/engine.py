@@ -5,6 +5,7 @@
 per item, codes as in include/cordagpu.h. ``Engine.verify_device`` is the same on
 buffers already resident in HBM (raw device pointers, e.g. ``torch.Tensor.data_ptr()``).
 """
+import collections
 import ctypes
 
 import numpy as np
@@ -345,6 +346,51 @@ class Engine:
         return _sign_ec(lambda k, sigs, ln, st: fn(self._h, _p(items), n, _p(arena), arena.size - 8, k, sigs, ln, st),
                         "cg_ec_sign_batch", n, nonces)
 
+    # ------------------------------------------------------------------ RSA-PSS signing
+    def load_rsa_signers(self, keys):
+        """cg_rsa_signers_load: replaces the context's RSA signer set (the third one, separate from the
+        Ed25519 and ECDSA sets) with ``keys``: RsaSignerKey tuples (n, e, p, q, dp, dq, qinv), e an int, the
+        others big-endian bytes-like objects (the fields of a BCRSAPrivateCrtKey). Returns the load status
+        uint8 [n]: 0, KEY_INVALID or UNSUPPORTED (include/cordagpu.h). The staging copy of the secret bytes
+        is zeroed before this returns."""
+        return _load_rsa_signers(_lib.lib().cg_rsa_signers_load, "cg_rsa_signers_load", self._h, keys)
+
+    def clear_rsa_signers(self):
+        _lib.check(_lib.lib().cg_rsa_signers_clear(self._h), "cg_rsa_signers_clear")
+
+    def sign_rsa_tx_ids(self, sr, salts):
+        """Batch Crypto.doSign(keyPair, SignableData(txId, metadata)) for RSA keys (cg_rsa_sign_tx_ids):
+        ``sr`` is a batch.SignRequests over the RSA signer set, ``salts`` the requests' 32-byte salts (what
+        BC's PSSSigner would have drawn). Returns (signature slots uint8 [n, 512], lengths uint16 [n],
+        status uint8 [n]). The salt array handed to the C ABI is zeroed before this returns, as
+        sign_ec_tx_ids does with its nonces."""
+        assert sr.reqs.dtype == SIGN_REQ_DTYPE and sr.tmpls.dtype == TMPL_DTYPE
+        fn = _lib.lib().cg_rsa_sign_tx_ids
+        return _sign_rsa(lambda k, sigs, ln, st: fn(self._h, _p(sr.ids), sr.n_ids, _p(sr.reqs), sr.n, _p(sr.tmpls),
+                                                    len(sr.tmpls), _p(sr.arena), sr.arena.size, k, sigs, ln, st),
+                         "cg_rsa_sign_tx_ids", sr.n, salts)
+
+    def sign_rsa_tx_ids_device(self, d_ids, n_ids, d_reqs, n, tmpls, d_arena, arena_len, d_salts, d_sigs, d_sig_len,
+                               d_status, stream=0):
+        """Asynchronous device form; `tmpls` is a host TMPL_DTYPE array (template bytes in the arena). The
+        caller owns, and zeroes, d_salts; d_sig_len holds n uint16."""
+        assert tmpls.dtype == TMPL_DTYPE
+        rc = _lib.lib().cg_rsa_sign_tx_ids_device(self._h, d_ids, n_ids, d_reqs, n, _p(tmpls), len(tmpls), d_arena,
+                                                  arena_len, d_salts, d_sigs, d_sig_len, d_status, stream or None)
+        _lib.check(rc, "cg_rsa_sign_tx_ids_device")
+
+    def sign_rsa(self, signer_msgs, salts):
+        """Batch Crypto.doSign(privateKey, clearData) for RSA keys (cg_rsa_sign_batch) over (signer index,
+        message bytes) pairs. Returns what sign_rsa_tx_ids returns."""
+        n = len(signer_msgs)
+        spans, arena = self._spans([m for _, m in signer_msgs])
+        items = np.zeros(n, dtype=SIGN_ITEM_DTYPE)
+        items["msg_off"], items["msg_len"] = spans["off"], spans["len"]
+        items["signer"] = [s for s, _ in signer_msgs]
+        fn = _lib.lib().cg_rsa_sign_batch
+        return _sign_rsa(lambda k, sigs, ln, st: fn(self._h, _p(items), n, _p(arena), arena.size - 8, k, sigs, ln, st),
+                         "cg_rsa_sign_batch", n, salts)
+
     # ------------------------------------------------------------------ key derivation
     def derive_keys(self, dr):
         """Batch Crypto.deriveKeyPair(privateKey, seed) (cg_derive_keys, Crypto.kt:646-771): ``dr`` is a
@@ -489,6 +535,63 @@ def _sign_ec(call, what, n, nonces, allow_partial=False):
     if rc != 0 and not allow_partial:
         _lib.check(rc, what)
     return sigs.reshape(-1, 72), ln, st
+
+
+RsaSignerKey = collections.namedtuple("RsaSignerKey", "n e p q dp dq qinv")
+RSA_SIGNER_DTYPE = np.dtype([(f, "<u4") for f in ("n_off", "n_len", "p_off", "p_len", "q_off", "q_len", "dp_off",
+                                                  "dp_len", "dq_off", "dq_len", "qinv_off", "qinv_len", "e")])
+assert RSA_SIGNER_DTYPE.itemsize == 52  # cg_rsa_signer
+
+
+def _load_rsa_signers(fn, what, h, keys):
+    # as _load_signers: each number goes straight from the caller's object into the one array the C ABI reads
+    keys = [RsaSignerKey(*k) for k in keys]
+    if not keys:
+        raise ValueError("at least one RSA private key is needed")
+    n = len(keys)
+    table = np.zeros(n, dtype=RSA_SIGNER_DTYPE)
+    views = [[np.frombuffer(getattr(k, f), dtype=np.uint8) for f in ("n", "p", "q", "dp", "dq", "qinv")] for k in keys]
+    buf = np.zeros(max(sum(v.size for vs in views for v in vs), 1), dtype=np.uint8)
+    at = 0
+    for i, (k, vs) in enumerate(zip(keys, views)):
+        if not 0 <= k.e < 1 << 32:
+            raise ValueError("the C ABI's public exponent is 32 bits")
+        table[i]["e"] = k.e
+        for f, v in zip(("n", "p", "q", "dp", "dq", "qinv"), vs):
+            table[i][f + "_off"], table[i][f + "_len"] = at, v.size
+            buf[at:at + v.size] = v
+            at += v.size
+    st = np.full(n, 255, dtype=np.uint8)
+    try:
+        rc = fn(h, _p(table), n, _p(buf), at, _p(st))
+    finally:
+        ctypes.memset(buf.ctypes.data, 0, buf.size)  # the staging copy (the caller's bytes are its own)
+    _lib.check(rc, what)
+    return st
+
+
+def salt_array(salts, n):
+    """The 32 n bytes of a sign call's salts, from n bytes-like objects or from a uint8 array; a C-contiguous
+    uint8 array is used in place (nonce_array's rule): the caller sees it zeroed."""
+    try:
+        return nonce_array(salts, n)
+    except ValueError:
+        raise ValueError("one 32-byte salt per request") from None
+
+
+def _sign_rsa(call, what, n, salts, allow_partial=False):
+    buf = salt_array(salts, n)
+    sigs = np.zeros(512 * n, dtype=np.uint8)
+    ln = np.zeros(n, dtype=np.uint16)
+    st = np.full(n, 255, dtype=np.uint8)
+    try:
+        rc = call(_p(buf), _p(sigs), _p(ln), _p(st))
+    finally:
+        if buf.size:
+            ctypes.memset(buf.ctypes.data, 0, buf.size)  # the array the C ABI read
+    if rc != 0 and not allow_partial:
+        _lib.check(rc, what)
+    return sigs.reshape(-1, 512), ln, st
 
 
 def _public_keys(fn, what, h, scheme, secrets, stats=None):
@@ -688,6 +791,26 @@ class EnginePool:
                                                   len(sr.tmpls), _p(sr.arena), sr.arena.size, k, sigs, ln, st,
                                                   ctypes.byref(stats)),
                        "cg_pool_ec_sign_tx_ids", sr.n, nonces, allow_partial)
+        self.last_stats = {k: getattr(stats, k) for k, _ in _lib.cg_pool_stats._fields_ if k != "reserved"}
+        return out
+
+    def load_rsa_signers(self, keys):
+        """cg_pool_rsa_signers_load: the RSA signer set on every slot; returns what Engine.load_rsa_signers does."""
+        return _load_rsa_signers(_lib.lib().cg_pool_rsa_signers_load, "cg_pool_rsa_signers_load", self._h, keys)
+
+    def clear_rsa_signers(self):
+        _lib.check(_lib.lib().cg_pool_rsa_signers_clear(self._h), "cg_pool_rsa_signers_clear")
+
+    def sign_rsa_tx_ids(self, sr, salts, allow_partial=False):
+        """cg_pool_rsa_sign_tx_ids: the whole call on one healthy slot, the next one on a device fault.
+        Returns what Engine.sign_rsa_tx_ids returns."""
+        assert sr.reqs.dtype == SIGN_REQ_DTYPE and sr.tmpls.dtype == TMPL_DTYPE
+        stats = _lib.cg_pool_stats()
+        fn = _lib.lib().cg_pool_rsa_sign_tx_ids
+        out = _sign_rsa(lambda k, sigs, ln, st: fn(self._h, _p(sr.ids), sr.n_ids, _p(sr.reqs), sr.n, _p(sr.tmpls),
+                                                   len(sr.tmpls), _p(sr.arena), sr.arena.size, k, sigs, ln, st,
+                                                   ctypes.byref(stats)),
+                        "cg_pool_rsa_sign_tx_ids", sr.n, salts, allow_partial)
         self.last_stats = {k: getattr(stats, k) for k, _ in _lib.cg_pool_stats._fields_ if k != "reserved"}
         return out
 

@@ -51,6 +51,33 @@ def rsa_decode_key(encoded):
                                       f"that it corresponds to the input scheme's code name. ({x})") from None
 
 
+def rsa_decode_private_key(encoded):
+    """PKCS#8 PrivateKeyInfo (RSAPrivateKey.getEncoded() of a BCRSAPrivateCrtKey) -> dict of ints n, e, d,
+    p, q, dp, dq, qinv. InvalidKeySpecException for anything that is not a two-prime rsaEncryption key;
+    UnsupportedOperationException for a key without CRT parts (BC writes zeros for them): the device signs
+    through the CRT parts only."""
+    try:
+        top = der.read_seq(encoded)
+        if len(top) < 3 or der.read_integer(*top[0]) != 0 or top[1][0] != 0x30 or top[2][0] != 0x04:
+            raise der.DerError("not a PrivateKeyInfo")
+        alg = der.read_seq(der.tlv(0x30, top[1][1]))
+        if not alg or der.tlv(*alg[0]) != RSA_OID or [der.tlv(*a) for a in alg[1:]] not in ([], [der.tlv(0x05, b"")]):
+            raise der.DerError("not an rsaEncryption key")
+        seq = der.read_seq(top[2][1])
+        if len(seq) != 9 or der.read_integer(*seq[0]) != 0:
+            raise der.DerError("not a two-prime RSAPrivateKey")
+        vals = [der.read_integer(*f) for f in seq[1:]]
+        if any(v < 0 for v in vals) or vals[0] <= 0 or vals[1] <= 0:
+            raise der.DerError("negative or zero field")
+    except der.DerError as x:
+        raise InvalidKeySpecException(f"This private key cannot be decoded, please ensure it is PKCS8 encoded. ({x})") \
+            from None
+    key = dict(zip(("n", "e", "d", "p", "q", "dp", "dq", "qinv"), vals))
+    if not all(key[f] for f in ("p", "q", "dp", "dq", "qinv")):
+        raise UnsupportedOperationException("an RSA private key without CRT parts: the device signs through them only")
+    return key
+
+
 def mgf1_sha256(seed, length):
     out = bytearray()
     counter = 0

@@ -635,8 +635,7 @@ int cg_verify_filtered_device(cg_ctx* ctx, const cg_filtered_tx* d_ftxs, uint64_
  *     -> i2p 0.2.0 EdDSAEngine.engineSign: RFC 8032's deterministic signature
  *          r = SHA-512(h[32..64) || M) mod L, R = r B, S = (r + SHA-512(R || A || M) a) mod L
  *   (the BFT notary signs the same way, BFTSMaRt.kt:249-255). The output is byte for byte what the JVM
- *   writes. ECDSA signing has a block of its own below (the host draws k); RSA-PSS signing stays on the
- *   host: BC draws the salt from SecureRandom.
+ *   writes. ECDSA and RSA-PSS signing have blocks of their own below (the host draws k, and the salt).
  * A context holds a signer set: private keys the node keeps in its own process
  * (PersistentKeyManagementService.kt:84-95), loaded once and named by index in every request. The seeds,
  * the expanded keys and every nonce r are secret: the signer store is a device allocation of its own,
@@ -732,6 +731,74 @@ int cg_ec_sign_tx_ids_device(cg_ctx* ctx, const uint8_t* d_ids, uint64_t n_ids, 
 /* Crypto.doSign(privateKey, clearData) (Crypto.kt:395-402) over arena bytes. */
 int cg_ec_sign_batch(cg_ctx* ctx, const cg_sign_item* items, uint64_t n, const uint8_t* arena, uint64_t arena_len,
                      const uint8_t* nonces, uint8_t* sigs_out, uint8_t* sig_len_out, uint8_t* status_out);
+
+/* ---- RSA-PSS signing: the batch form of Crypto.doSign for RSA_SHA256 (1), with the salt drawn by the caller:
+ *   Crypto.doSign(privateKey, clearData)            core/.../crypto/Crypto.kt:395-402
+ *   Crypto.doSign(keyPair, signableData)            Crypto.kt:415-422
+ *     -> BC 1.57 "SHA256WITHRSAANDMGF1": PSSSignatureSpi.engineSign -> PSSSigner.generateSignature
+ *        -> RSABlindedEngine.processBlock                                           [recalled]
+ *          mHash = SHA-256(M); random.nextBytes(salt), 32 bytes; H = SHA-256(0^8 || mHash || salt);
+ *          DB = PS || 01 || salt, masked with MGF1-SHA256(H); the bits above emBits = bits(n) - 1 cleared;
+ *          EM = DB || H || BC; s = EM^d mod n through the CRT parts of a BCRSAPrivateCrtKey; the output
+ *          block padded to k = ceil(bits(n) / 8) bytes                                [recalled]
+ *   A request carries its salt (32 bytes: what random.nextBytes would have produced). Given the salt the
+ *   signature is a pure function of (key, message, salt); BC never refuses or redraws a salt, so there is
+ *   no status to resubmit. RSABlindedEngine's blinding changes no output byte and is not built. The device
+ *   never draws randomness.
+ * The RSA signer set is a third one: loading or clearing any of the three leaves the other two untouched.
+ * Secret: p, q, dP, dQ, qInv and everything derived from them, every salt and H, the 16 powers of EM per
+ * prime. The signer store is a device allocation of its own; the staged secret bytes are zeroed on the
+ * stream right behind the expansion, the store before every free (cg_rsa_signers_clear, a reload,
+ * cg_close), and no host copy is kept. A sign call zeroes its workspace on the stream behind the last
+ * chunk's last kernel, also after a failed launch; the kernels zero their LDS tables; the host forms zero
+ * their staged copy of the salts too. Not constant-time: the LDS address of a table read depends on a
+ * window digit of dP / dQ, and the conditional subtraction of every modular product branches on the
+ * operands. As for the other two signers: for keys the node already holds in memory, not a stand-in for an
+ * HSM.
+ * Every signature is checked before it leaves the device: s^e mod n is recomputed and compared with EM. A
+ * CRT signature that is wrong modulo one prime gives away the factorisation of n; such an item gets
+ * CG_SIGN_CHECK_FAILED and zero bytes.
+ * Statuses: 0 signed; CG_EMPTY msg_len == 0, checked before anything else (Crypto.kt:398); CG_NOT_RUN a
+ * signer, id or template index out of range, bytes outside the arena, or a signer refused at load;
+ * CG_SIGN_CHECK_FAILED see above. An item that is not signed gets 512 zero bytes and length 0. With no RSA
+ * signers loaded a sign call is CG_ERR_ARG and writes nothing; n == 0 is a no-op. */
+#define CG_SIGN_CHECK_FAILED 10 /* the device recomputed s^e mod n and it did not equal EM: nothing written */
+#define CG_RSA_SIG_MAX 512      /* bytes per signature slot */
+/* One CRT private key (the fields of a BCRSAPrivateCrtKey; PKCS#1 RSAPrivateKey: qInv = q^-1 mod p): each
+ * number a big-endian unsigned byte string at secrets[off .. off + len), at most one leading zero byte. */
+typedef struct cg_rsa_signer {
+  uint32_t n_off, n_len;
+  uint32_t p_off, p_len;
+  uint32_t q_off, q_len;
+  uint32_t dp_off, dp_len;
+  uint32_t dq_off, dq_len;
+  uint32_t qinv_off, qinv_len;
+  uint32_t e;        /* the public exponent, 1 .. 2^32 - 1 */
+} cg_rsa_signer;     /* 52 bytes */
+/* Replaces the context's RSA signer set with n keys, n <= CG_SIGNERS_MAX, secrets_len < 2^32. status_out
+ * (n bytes): 0 loaded; CG_UNSUPPORTED bits(n) outside 1024 .. 4096 or a prime longer than 2048 bits;
+ * CG_KEY_INVALID bytes outside `secrets`, n, p or q even, e = 0, dP >= p, dQ >= q, qInv >= p, or a failed
+ * self-test (a fixed value signed through the CRT path must come back under e: catches p q != n and wrong
+ * CRT parts). A refused signer does not disturb the others of the load; its requests later get CG_NOT_RUN. */
+int cg_rsa_signers_load(cg_ctx* ctx, const cg_rsa_signer* signers, uint32_t n, const uint8_t* secrets,
+                        uint64_t secrets_len, uint8_t* status_out); /* no host copy is kept */
+/* Zeroes and frees the RSA signer set (a no-op when none is loaded). */
+int cg_rsa_signers_clear(cg_ctx* ctx);
+/* Crypto.doSign(keyPair, SignableData(ids[tx_idx], tmpl)) for every request, as cg_sign_tx_ids; salts:
+ * 32 * n bytes, request i's salt. sigs_out: 512 * n bytes (k = ceil(bits(n) / 8) signature bytes, then
+ * zeros), sig_len_out: n uint16_t (k, or 0), status_out: n bytes. */
+int cg_rsa_sign_tx_ids(cg_ctx* ctx, const uint8_t* ids, uint64_t n_ids, const cg_sign_req* reqs, uint64_t n,
+                       const cg_signable_tmpl* tmpls, uint32_t n_tmpls, const uint8_t* arena, uint64_t arena_len,
+                       const uint8_t* salts, uint8_t* sigs_out, uint16_t* sig_len_out, uint8_t* status_out);
+/* Device buffers in HBM except `tmpls` (a small host array); asynchronous on hip_stream. d_ids, d_reqs,
+ * d_arena, d_salts and d_sigs must be 4-byte aligned. The caller owns (and zeroes) d_salts. */
+int cg_rsa_sign_tx_ids_device(cg_ctx* ctx, const uint8_t* d_ids, uint64_t n_ids, const cg_sign_req* d_reqs, uint64_t n,
+                              const cg_signable_tmpl* tmpls, uint32_t n_tmpls, const uint8_t* d_arena,
+                              uint64_t arena_len, const uint8_t* d_salts, uint8_t* d_sigs, uint16_t* d_sig_len,
+                              uint8_t* d_status, void* hip_stream);
+/* Crypto.doSign(privateKey, clearData) (Crypto.kt:395-402) over arena bytes. */
+int cg_rsa_sign_batch(cg_ctx* ctx, const cg_sign_item* items, uint64_t n, const uint8_t* arena, uint64_t arena_len,
+                      const uint8_t* salts, uint8_t* sigs_out, uint16_t* sig_len_out, uint8_t* status_out);
 
 /* ---- Key derivation: the batch form of Crypto.deriveKeyPair (core/.../crypto/Crypto.kt:646-771), the
  * call the reference points at for a unique key per transaction (Crypto.kt:631-637). Deterministic for
@@ -879,6 +946,15 @@ int cg_pool_ec_sign_tx_ids(cg_pool* pool, const uint8_t* ids, uint64_t n_ids, co
                            const cg_signable_tmpl* tmpls, uint32_t n_tmpls, const uint8_t* arena, uint64_t arena_len,
                            const uint8_t* nonces, uint8_t* sigs_out, uint8_t* sig_len_out, uint8_t* status_out,
                            cg_pool_stats* stats_opt);
+/* The RSA signer set on every slot and cg_rsa_sign_tx_ids on a pool, by the same rules (status_out of the
+ * load from the first slot that loaded). */
+int cg_pool_rsa_signers_load(cg_pool* pool, const cg_rsa_signer* signers, uint32_t n, const uint8_t* secrets,
+                             uint64_t secrets_len, uint8_t* status_out);
+int cg_pool_rsa_signers_clear(cg_pool* pool);
+int cg_pool_rsa_sign_tx_ids(cg_pool* pool, const uint8_t* ids, uint64_t n_ids, const cg_sign_req* reqs, uint64_t n,
+                            const cg_signable_tmpl* tmpls, uint32_t n_tmpls, const uint8_t* arena, uint64_t arena_len,
+                            const uint8_t* salts, uint8_t* sigs_out, uint16_t* sig_len_out, uint8_t* status_out,
+                            cg_pool_stats* stats_opt);
 /* cg_derive_keys on a pool: not sharded, the whole call runs on the first healthy slot and, if that
  * slot's device fails, on the next one (as cg_pool_sign_tx_ids). When no slot could run it the status
  * bytes are CG_NOT_RUN, the outputs zero, and the call returns CG_ERR_DEVICE. */

@@ -219,6 +219,40 @@ JNIEXPORT jint JNICALL Java_net_corda_core_crypto_CryptoBatch_nativeEcSignTxIds(
                            (uint8_t*)ADDR(status_out));
 }
 
+/* The RSA signer set (cg_rsa_signers_load; pool != 0: cg_pool_rsa_signers_load, every device): n cg_rsa_signer
+ * records over the big-endian numbers (n, p, q, dP, dQ, qInv) the binding wrote into `secrets`; status_out one
+ * byte per key. The binding zeroes the secrets buffer afterwards. */
+JNIEXPORT jint JNICALL Java_net_corda_core_crypto_CryptoBatch_nativeLoadRsaSigners(JNIEnv* env, jobject self, jlong ctx,
+                                                                                 jlong pool, jobject signers, jint n,
+                                                                                 jobject secrets, jlong secrets_len,
+                                                                                 jobject status_out) {
+  if (pool)
+    return cg_pool_rsa_signers_load((cg_pool*)(intptr_t)pool, (const cg_rsa_signer*)ADDR(signers), (uint32_t)n,
+                                    (const uint8_t*)ADDR(secrets), (uint64_t)secrets_len, (uint8_t*)ADDR(status_out));
+  return cg_rsa_signers_load((cg_ctx*)(intptr_t)ctx, (const cg_rsa_signer*)ADDR(signers), (uint32_t)n,
+                             (const uint8_t*)ADDR(secrets), (uint64_t)secrets_len, (uint8_t*)ADDR(status_out));
+}
+
+/* Crypto.doSign(keyPair, SignableData(id, metadata)) for RSA key pairs over many ids: cg_rsa_sign_tx_ids (pool != 0:
+ * cg_pool_rsa_sign_tx_ids). salts: 32 bytes per request, the salt the binding drew; sigs_out: 512 bytes per request
+ * (the signature, then zeros), sig_len_out: one uint16 and status_out: one byte per request. */
+JNIEXPORT jint JNICALL Java_net_corda_core_crypto_CryptoBatch_nativeRsaSignTxIds(
+    JNIEnv* env, jobject self, jlong ctx, jlong pool, jobject ids, jlong n_ids, jobject reqs, jlong n, jobject tmpls,
+    jint n_tmpls, jobject arena, jlong arena_len, jobject salts, jobject sigs_out, jobject sig_len_out,
+    jobject status_out) {
+  if (pool)
+    return cg_pool_rsa_sign_tx_ids((cg_pool*)(intptr_t)pool, (const uint8_t*)ADDR(ids), (uint64_t)n_ids,
+                                   (const cg_sign_req*)ADDR(reqs), (uint64_t)n, (const cg_signable_tmpl*)ADDR(tmpls),
+                                   (uint32_t)n_tmpls, (const uint8_t*)ADDR(arena), (uint64_t)arena_len,
+                                   (const uint8_t*)ADDR(salts), (uint8_t*)ADDR(sigs_out), (uint16_t*)ADDR(sig_len_out),
+                                   (uint8_t*)ADDR(status_out), 0);
+  return cg_rsa_sign_tx_ids((cg_ctx*)(intptr_t)ctx, (const uint8_t*)ADDR(ids), (uint64_t)n_ids,
+                            (const cg_sign_req*)ADDR(reqs), (uint64_t)n, (const cg_signable_tmpl*)ADDR(tmpls),
+                            (uint32_t)n_tmpls, (const uint8_t*)ADDR(arena), (uint64_t)arena_len,
+                            (const uint8_t*)ADDR(salts), (uint8_t*)ADDR(sigs_out), (uint16_t*)ADDR(sig_len_out),
+                            (uint8_t*)ADDR(status_out));
+}
+
 /* Crypto.deriveKeyPair(privateKey, seed) over many seeds (Crypto.kt:646-771): cg_derive_keys (pool != 0:
  * cg_pool_derive_keys, the whole call on one healthy device, the next one on a device fault). parents:
  * cg_derive_parent records over keyData the binding wrote into the arena; secrets_out 32 bytes, pubs_out

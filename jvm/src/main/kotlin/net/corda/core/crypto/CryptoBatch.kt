@@ -31,6 +31,8 @@ import java.security.PrivateKey
 import java.security.PublicKey
 import java.security.SecureRandom
 import java.security.SignatureException
+import java.security.interfaces.RSAPrivateCrtKey
+import java.security.interfaces.RSAPublicKey
 import java.util.concurrent.TimeUnit
 import java.util.concurrent.atomic.AtomicInteger
 import java.util.concurrent.locks.ReentrantLock
@@ -137,6 +139,17 @@ object CryptoBatch {
                                            tmpls: ByteBuffer, nTmpls: Int, arena: ByteBuffer, arenaLen: Long,
                                            nonces: ByteBuffer, sigsOut: ByteBuffer, sigLenOut: ByteBuffer,
                                            statusOut: ByteBuffer): Int
+    /** cg_(pool_)rsa_signers_load: the RSA signer set (the third one): n 52-byte cg_rsa_signer records (offset and
+     *  length of n, p, q, dP, dQ, qInv in `secrets`, then e); statusOut receives the load status per key. */
+    private external fun nativeLoadRsaSigners(ctx: Long, pool: Long, signers: ByteBuffer, n: Int, secrets: ByteBuffer,
+                                              secretsLen: Long, statusOut: ByteBuffer): Int
+    /** cg_(pool_)rsa_sign_tx_ids: Crypto.doSign(keyPair, SignableData(id, metadata)) for RSA key pairs per 8-byte
+     *  request, with one 32-byte salt per request (salts); a 512-byte slot (the signature, then zeros), a 16-bit
+     *  length and a status byte per request. */
+    private external fun nativeRsaSignTxIds(ctx: Long, pool: Long, ids: ByteBuffer, nIds: Long, reqs: ByteBuffer, n: Long,
+                                            tmpls: ByteBuffer, nTmpls: Int, arena: ByteBuffer, arenaLen: Long,
+                                            salts: ByteBuffer, sigsOut: ByteBuffer, sigLenOut: ByteBuffer,
+                                            statusOut: ByteBuffer): Int
     /** cg_(pool_)derive_keys: Crypto.deriveKeyPair(privateKey, seed) per 16-byte request (cg_derive_req: seed
      *  offset and length, parent) over 16-byte parents (cg_derive_parent: keyData offset and length, scheme);
      *  32 secret bytes, 64 public bytes, a status byte and a rehash count per request. */
@@ -534,16 +547,18 @@ object CryptoBatch {
     /** NotaryService.sign(txId) (NotaryService.kt:77-80; BFTSMaRt.kt:249-255) for many ids in one call:
      *  Crypto.doSign(keyPair, SignableData(id, signatureMetadata)) each (Crypto.kt:415-422), byte for
      *  byte what i2p's EdDSAEngine writes. ECDSA_SECP256R1_SHA256 / ECDSA_SECP256K1_SHA256 key pairs go to the
-     *  device too (signAllEcdsa: k drawn here from a SecureRandom). A key pair of another scheme (BC draws
-     *  the PSS salt at random inside the signer), fewer ids than minBatch, a device fault, or any other
-     *  non-zero status falls back to Crypto.doSign on the JVM for those ids, which also raises the
-     *  reference's own exceptions. */
+     *  device too (signAllEcdsa: k drawn here from a SecureRandom), and so do RSA_SHA256 key pairs with CRT
+     *  parts (signAllRsa: the PSS salt drawn here). A key pair of another scheme, fewer ids than minBatch, a
+     *  device fault, or any other non-zero status falls back to Crypto.doSign on the JVM for those ids,
+     *  which also raises the reference's own exceptions. */
     fun signAll(keyPair: KeyPair, txIds: List<SecureHash>, signatureMetadata: SignatureMetadata,
                 random: SecureRandom = ecNonceRandom): List<TransactionSignature> {
         fun onJvm(id: SecureHash) = Crypto.doSign(keyPair, SignableData(id, signatureMetadata))
         if (txIds.isEmpty()) return emptyList()
         if (txIds.size >= config.minBatch && ecdsaSchemeId(keyPair) != 0)
             return signAllEcdsa(keyPair, txIds, signatureMetadata, random)
+        if (txIds.size >= config.minBatch && isRsaCrt(keyPair))
+            return signAllRsa(keyPair, txIds, signatureMetadata, random)
         if (!isEd25519(keyPair) || txIds.size < config.minBatch) return txIds.map(::onJvm)
         requireAligned(keyPair)
         val (pre, suf) = signableTemplate(signatureMetadata)
@@ -707,6 +722,118 @@ object CryptoBatch {
             pending = again
         }
         return out.map { it!! }
+    }
+
+    // ---- RSA-PSS signing (include/cordagpu.h, "RSA-PSS signing"). The third signer set, under the same lock.
+    private const val CG_RSA_SIG_MAX = 512
+    private var rsaSignerKeys: List<KeyPair> = emptyList()
+    private var rsaSignerHandle = 0L
+
+    /** Both halves RSA_SHA256 keys, the private one with CRT parts and a public exponent that fits the C ABI's
+     *  32-bit e. */
+    private fun isRsaCrt(k: KeyPair): Boolean {
+        if (Crypto.findSignatureScheme(k.private) != Crypto.RSA_SHA256 || Crypto.findSignatureScheme(k.public) != Crypto.RSA_SHA256) return false
+        val priv = k.private as? RSAPrivateCrtKey ?: return false
+        return priv.publicExponent.signum() > 0 && priv.publicExponent.bitLength() <= 32
+    }
+
+    /** The magnitude bytes of a non-negative value, big-endian, without BigInteger's sign byte. */
+    private fun magnitude(v: BigInteger): ByteArray {
+        val b = v.toByteArray()
+        return if (b.size > 1 && b[0] == 0.toByte()) b.copyOfRange(1, b.size).also { b.fill(0) } else b
+    }
+
+    /** With signerLock held, inside withHandles: the RSA set is in the open context. A pair whose public half is
+     *  not (n, e) of the private key is refused here, as Crypto.doSign(keyPair, signableData) refuses a
+     *  misaligned pair (Crypto.kt:416-419); a key the device refuses (its load self-test) leaves the set. The
+     *  buffer that held the CRT parts is zeroed before it is released. */
+    private fun ensureRsaSigners(c: Long, p: Long): Boolean {
+        val h = if (c != 0L) c else p
+        if (rsaSignerHandle == h) return true
+        val n = rsaSignerKeys.size
+        val table = direct(52 * n)
+        val secrets = direct(n * (513 + 5 * 257))
+        val st = direct(n)
+        val rc = try {
+            rsaSignerKeys.forEach {
+                val k = it.private as RSAPrivateCrtKey
+                for (v in listOf(k.modulus, k.primeP, k.primeQ, k.primeExponentP, k.primeExponentQ, k.crtCoefficient)) {
+                    val m = magnitude(v)
+                    table.putInt(secrets.position()).putInt(m.size)
+                    secrets.put(m)
+                    m.fill(0)
+                }
+                table.putInt(k.publicExponent.toInt())
+            }
+            nativeLoadRsaSigners(c, p, table, n, secrets, secrets.position().toLong(), st)
+        } finally {
+            wipe(secrets)
+        }
+        if (rc != CG_OK) return false
+        val bad = rsaSignerKeys.indices.filter { i ->
+            val pub = rsaSignerKeys[i].public as RSAPublicKey
+            val priv = rsaSignerKeys[i].private as RSAPrivateCrtKey
+            st.get(i).toInt() != 0 || pub.modulus != priv.modulus || pub.publicExponent != priv.publicExponent
+        }
+        if (bad.isNotEmpty()) {   // as ensureSigners: the offending pairs leave the set, the next call loads the rest
+            rsaSignerKeys = rsaSignerKeys.filterIndexed { i, _ -> i !in bad }
+            rsaSignerHandle = 0
+            throw IllegalArgumentException("RSA signer ${bad.first()}: the public key is not the private key's, or the device refused the key")
+        }
+        rsaSignerHandle = h
+        return true
+    }
+
+    /** signAll for an RSA key pair: BC 1.57's PSSSigner.generateSignature with the salts drawn here, 32 bytes per
+     *  signature as its random.nextBytes(salt) does, exactly once: BC never refuses a salt. A device fault or
+     *  any non-zero status (CG_SIGN_CHECK_FAILED among them) falls back to Crypto.doSign on the JVM for that id.
+     *  The salt buffer is zeroed after the call. */
+    private fun signAllRsa(keyPair: KeyPair, txIds: List<SecureHash>, signatureMetadata: SignatureMetadata,
+                           random: SecureRandom): List<TransactionSignature> {
+        fun onJvm(id: SecureHash) = Crypto.doSign(keyPair, SignableData(id, signatureMetadata))
+        val (pre, suf) = signableTemplate(signatureMetadata)
+        val arena = direct(pre.size + suf.size + 16)
+        val tmpls = direct(24)
+        arena.align4(); val po = arena.position().toLong(); arena.put(pre)
+        arena.align4(); val so = arena.position().toLong(); arena.put(suf)
+        tmpls.putLong(po).putLong(so).putInt(pre.size).putInt(suf.size)
+        val n = txIds.size
+        val ids = direct(32 * n)
+        txIds.forEach { ids.put(it.bytes) }
+        val reqs = direct(8 * n)
+        val salts = direct(32 * n)
+        val sigs = direct(CG_RSA_SIG_MAX * n)
+        val lens = direct(2 * n)
+        val status = direct(n)
+        val draw = ByteArray(32)
+        val rc = try {
+            for (j in 0 until n) { random.nextBytes(draw); salts.put(draw) }
+            withHandles { c, p ->
+                signerLock.withLock {
+                    var signer = rsaSignerKeys.indexOfFirst { it.public == keyPair.public && it.private == keyPair.private }
+                    if (signer < 0 && rsaSignerKeys.size < CG_SIGNERS_MAX) {
+                        rsaSignerKeys = rsaSignerKeys + keyPair
+                        rsaSignerHandle = 0
+                        signer = rsaSignerKeys.size - 1
+                    }
+                    if (signer < 0 || !ensureRsaSigners(c, p)) CG_ERR_DEVICE
+                    else {
+                        for (j in 0 until n) reqs.putInt(8 * j, j).putShort(8 * j + 4, signer.toShort()).putShort(8 * j + 6, 0)
+                        nativeRsaSignTxIds(c, p, ids, n.toLong(), reqs, n.toLong(), tmpls, 1, arena, arena.position().toLong(),
+                                           salts, sigs, lens, status)
+                    }
+                }
+            }
+        } finally {
+            wipe(salts)
+            draw.fill(0)
+        }
+        return txIds.mapIndexed { j, id ->
+            if (rc == CG_OK && status.get(j).toInt() == 0)
+                TransactionSignature(ByteArray(lens.getShort(2 * j).toInt() and 0xFFFF).also { sigs.position(CG_RSA_SIG_MAX * j); sigs.get(it) },
+                                     keyPair.public, signatureMetadata)
+            else onJvm(id)
+        }
     }
 
     /** deriveHMAC's keyData (Crypto.kt:759-771) and the scheme id of a private key the device derives
