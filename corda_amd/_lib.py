@@ -105,6 +105,16 @@ def lib():
             L.cg_verify_tx_signatures_device.restype = i32
             L.cg_verify_filtered.argtypes = [vp, vp, u64, vp, u64, vp, u64, vp, u64, vp]
             L.cg_verify_filtered_device.argtypes = [vp, vp, u64, vp, u64, vp, u64, vp, u64, vp, vp]
+            if hasattr(L, "cg_build_filtered"):  # older builds (A/B variants) lack tear-off building
+                outs = [u64, vp, vp, u64, vp, u64, vp, u64, vp, vp]  # out_base, ftxs, nodes + cap, leaves + cap, out + cap, status, totals
+                L.cg_build_filtered.argtypes = [vp, vp, u64, vp, u64, vp, u64, vp] + outs
+                L.cg_build_filtered.restype = i32
+                L.cg_build_filtered_device.argtypes = [vp, vp, u64, vp, u64, vp, u64, vp] + outs + [vp]
+                L.cg_build_filtered_device.restype = i32
+                L.cg_build_partial_trees.argtypes = [vp, vp, vp, vp, u64, vp, vp, vp] + outs
+                L.cg_build_partial_trees.restype = i32
+                L.cg_build_partial_trees_device.argtypes = [vp, vp, u64, vp, vp, u64, u64, vp, u64, vp, vp] + outs + [vp]
+                L.cg_build_partial_trees_device.restype = i32
             if hasattr(L, "cg_stage_times"):
                 L.cg_stage_times.argtypes = [vp, vp, vp, u32]
                 L.cg_stage_times.restype = i32

@@ -46,6 +46,11 @@ assert PMT_NODE_DTYPE.itemsize == 16 and FLEAF_DTYPE.itemsize == 24 and FTX_DTYP
 PMT_NODE, PMT_LEAF, PMT_INCLUDED = 0, 1, 2
 FLEAF_SALT, FLEAF_HASH = 1, 2
 FTX_FILTERED = 1
+# tear-off building (cg_build_totals; statuses of cg_build_filtered / cg_build_partial_trees)
+BUILD_TOTALS_DTYPE = np.dtype([("n_nodes", "<u8"), ("n_leaves", "<u8"), ("out_bytes", "<u8"), ("over", "<u4"),
+                               ("reserved", "<u4")])
+assert BUILD_TOTALS_DTYPE.itemsize == 32
+BUILD_ZERO_HASH, BUILD_NOT_IN_TREE, BUILD_BAD_VISIBLE = 4, 5, 6
 assert TXSIG_DTYPE.itemsize == 24 and TMPL_DTYPE.itemsize == 24
 # per-transaction verdicts (cg_tx_check / cg_req_node / cg_tx_verdict)
 TX_CHECK_DTYPE = np.dtype([("first_sig", "<u8"), ("n_sigs", "<u4"), ("first_req", "<u4"), ("n_req", "<u4"),

@@ -179,6 +179,9 @@ struct cg_ctx : cg::CallState<HipStreams> {
   DevBuf txvws, txvio;
   // tear-offs: leaf-hash workspace
   DevBuf ftxws;
+  // tear-off building (build_filtered.hip): the walks' workspace; the host forms' inputs that have no
+  // buffer of their own above, and their result tables
+  DevBuf bfws, bfin, bfio;
   // The Ed25519 signer (sign_ed.hip). signers: the expanded keys, an allocation of its own made by
   // cg_signers_load and zeroed before it is freed (secret: a, prefix); a context that never signs
   // allocates neither. signws: a chunk's r column and digit slots, zeroed behind every sign call.
@@ -927,7 +930,7 @@ void cg_close(cg_ctx* c) {
   c->aux1.release();
   c->aux2.release();
   for (DevBuf* b : {&c->txitems, &c->msgs, &c->tmpls, &c->h_txs, &c->h_comps, &c->h_sigs, &c->h_ids, &c->h_txst,
-                    &c->ftxws, &c->sig12ws, &c->rsakeys, &c->rsalist, &c->txvws, &c->txvio})
+                    &c->ftxws, &c->bfws, &c->bfin, &c->bfio, &c->sig12ws, &c->rsakeys, &c->rsalist, &c->txvws, &c->txvio})
     b->release();
   for (int k = 0; k < 3; ++k) {
     if (c->fork.side[k]) {
@@ -2123,6 +2126,215 @@ int cg_verify_filtered(cg_ctx* c, const cg_filtered_tx* ftxs, uint64_t n_ftx, co
                               (const cg_filtered_leaf*)c->h_sigs.p, n_leaves, (const uint8_t*)c->arena.p, arena_len,
                               (uint8_t*)c->status.p, (uint8_t*)c->ftxws.p, s), "launch_filtered");
   HIP_TRY(hipMemcpyAsync(status_out, c->status.p, n_ftx, hipMemcpyDeviceToHost, s), "D2H status");
+  HIP_TRY(call.close(), "hipEventRecord");
+  HIP_TRY(hipStreamSynchronize(s), "hipStreamSynchronize");
+  return CG_OK;
+}
+
+// ---------------------------------------------------------------- tear-off building (build_filtered.hip)
+static_assert(sizeof(cg_build_totals) == 32, "cg_build_totals layout");
+
+using cg::al256;
+
+static int build_out_args(const char* fn, uint64_t n, const cg::BuildOut& o, bool device) {
+  if (n && (!o.ftxs || !o.status || !o.totals)) return fail(CG_ERR_ARG, "%s: NULL buffer", fn);
+  if ((o.node_cap && !o.nodes) || (o.leaf_cap && !o.leaves) || (o.out_cap && !o.out))
+    return fail(CG_ERR_ARG, "%s: NULL table", fn);
+  if (device && ((uintptr_t)o.out & 15) != 0) return fail(CG_ERR_ARG, "%s: out is not 16-byte aligned", fn);
+  return CG_OK;
+}
+
+// A host form between its two enqueues: the count pass's totals read back, and the result tables of
+// exactly that size in bfio. d: the device-side BuildOut (ftxs, status and totals set by the caller).
+static int build_host_tables(cg_ctx* c, const char* fn, const cg::BuildOut& h, cg::BuildOut* d, hipStream_t s) {
+  cg_build_totals t;
+  HIP_TRY(hipMemcpyAsync(&t, d->totals, sizeof t, hipMemcpyDeviceToHost, s), "D2H totals");
+  HIP_TRY(hipStreamSynchronize(s), "hipStreamSynchronize");
+  *h.totals = t;
+  if (t.over) {
+    char msg[256];
+    snprintf(msg, sizeof msg, "a capacity is too small: the call needs %llu node rows, %llu leaf rows, %llu output bytes",
+             (unsigned long long)t.n_nodes, (unsigned long long)t.n_leaves, (unsigned long long)t.out_bytes);
+    return fail(CG_ERR_ARG, (std::string(fn) + ": %s").c_str(), msg);
+  }
+  const uint64_t nodes_b = al256(sizeof(cg_pmt_node) * t.n_nodes), leaves_b = al256(sizeof(cg_filtered_leaf) * t.n_leaves);
+  HIP_TRY(c->bfio.ensure(nodes_b + leaves_b + t.out_bytes + 256), "hipMalloc(build tables)");
+  uint8_t* p = (uint8_t*)c->bfio.p;
+  d->nodes = (cg_pmt_node*)p;
+  d->leaves = (cg_filtered_leaf*)(p + nodes_b);
+  d->out = p + nodes_b + leaves_b;
+  d->node_cap = t.n_nodes;
+  d->leaf_cap = t.n_leaves;
+  d->out_cap = t.out_bytes;
+  return CG_OK;
+}
+
+static int build_host_results(const cg::BuildOut& h, const cg::BuildOut& d, uint64_t n, hipStream_t s) {
+  const cg_build_totals& t = *h.totals;
+  HIP_TRY(hipMemcpyAsync(h.ftxs, d.ftxs, sizeof(cg_filtered_tx) * n, hipMemcpyDeviceToHost, s), "D2H ftxs");
+  HIP_TRY(hipMemcpyAsync(h.status, d.status, n, hipMemcpyDeviceToHost, s), "D2H status");
+  if (t.n_nodes)
+    HIP_TRY(hipMemcpyAsync(h.nodes, d.nodes, sizeof(cg_pmt_node) * t.n_nodes, hipMemcpyDeviceToHost, s), "D2H nodes");
+  if (t.n_leaves)
+    HIP_TRY(hipMemcpyAsync(h.leaves, d.leaves, sizeof(cg_filtered_leaf) * t.n_leaves, hipMemcpyDeviceToHost, s),
+            "D2H leaves");
+  if (t.out_bytes) HIP_TRY(hipMemcpyAsync(h.out, d.out, t.out_bytes, hipMemcpyDeviceToHost, s), "D2H out");
+  return CG_OK;
+}
+
+// The part of bfin a host form's fixed-size results take: [ftxs 40 n][status n][totals]
+static uint64_t build_fixed_bytes(uint64_t n) { return al256(sizeof(cg_filtered_tx) * n) + al256(n) + 256; }
+static void build_fixed_split(uint8_t* p, uint64_t n, cg::BuildOut* d) {
+  d->ftxs = (cg_filtered_tx*)p;
+  d->status = p + al256(sizeof(cg_filtered_tx) * n);
+  d->totals = (cg_build_totals*)(d->status + al256(n));
+}
+
+int cg_build_filtered_device(cg_ctx* c, const cg_tx* d_txs, uint64_t n_tx, const cg_component* d_comps,
+                             uint64_t n_comps, const uint8_t* d_arena, uint64_t arena_len, const uint8_t* d_visible,
+                             uint64_t out_base, cg_filtered_tx* d_ftxs, cg_pmt_node* d_nodes, uint64_t node_cap,
+                             cg_filtered_leaf* d_leaves, uint64_t leaf_cap, uint8_t* d_out, uint64_t out_cap,
+                             uint8_t* d_status, cg_build_totals* d_totals, void* hip_stream) {
+  const char* fn = "cg_build_filtered_device";
+  if (!c) return fail(CG_ERR_ARG, "%s: ctx is NULL", fn);
+  const cg::BuildOut o{out_base, d_ftxs, d_nodes, node_cap, d_leaves, leaf_cap, d_out, out_cap, d_status, d_totals};
+  if (!d_totals) return fail(CG_ERR_ARG, "%s: NULL buffer", fn);
+  if (const int rc = build_out_args(fn, n_tx, o, true)) return rc;
+  if (n_tx && (!d_txs || (n_comps && (!d_comps || !d_visible)))) return fail(CG_ERR_ARG, "%s: NULL buffer", fn);
+  const cg::BuildTxIn in{d_txs, n_tx, d_comps, n_comps, d_arena, arena_len, d_visible};
+  std::lock_guard<std::mutex> g(c->mu);
+  if (const int rc = enter(c, fn)) return rc;
+  HIP_TRY(ensure_all({{&c->aux2, cg::tx_ws_bytes(n_comps)}, {&c->bfws, cg::build_ws_bytes(n_tx, n_comps)}}),
+          "hipMalloc(build ws)");
+  Call call(c, Call::kDevice);
+  HIP_TRY(call.open(hip_stream), "hipStreamWaitEvent");
+  HIP_TRY(cg::launch_build_filtered_count(in, o, (uint8_t*)c->aux2.p, (uint8_t*)c->bfws.p, call.stream()),
+          "launch_build_filtered_count");
+  HIP_TRY(cg::launch_build_filtered_emit(in, o, (uint8_t*)c->aux2.p, (uint8_t*)c->bfws.p, call.stream()),
+          "launch_build_filtered_emit");
+  HIP_TRY(call.close(), "hipEventRecord");
+  return CG_OK;
+}
+
+int cg_build_filtered(cg_ctx* c, const cg_tx* txs, uint64_t n_tx, const cg_component* comps, uint64_t n_comps,
+                      const uint8_t* arena, uint64_t arena_len, const uint8_t* visible, uint64_t out_base,
+                      cg_filtered_tx* ftxs_out, cg_pmt_node* nodes_out, uint64_t node_cap,
+                      cg_filtered_leaf* leaves_out, uint64_t leaf_cap, uint8_t* out, uint64_t out_cap,
+                      uint8_t* status_out, cg_build_totals* totals_out) {
+  const char* fn = "cg_build_filtered";
+  if (!c) return fail(CG_ERR_ARG, "%s: ctx is NULL", fn);
+  cg::BuildOut h{out_base, ftxs_out, nodes_out, node_cap, leaves_out, leaf_cap, out, out_cap, status_out, totals_out};
+  if (!totals_out) return fail(CG_ERR_ARG, "%s: NULL buffer", fn);
+  if (const int rc = build_out_args(fn, n_tx, h, false)) return rc;
+  if (n_tx && (!txs || (n_comps && (!comps || !visible)) || (arena_len && !arena)))
+    return fail(CG_ERR_ARG, "%s: NULL buffer", fn);
+  memset(totals_out, 0, sizeof *totals_out);
+  if (n_tx == 0) return CG_OK;
+  std::lock_guard<std::mutex> g(c->mu);
+  if (const int rc = enter(c, fn)) return rc;
+  hipStream_t s = c->stream;
+  Call call(c, Call::kHost);
+  HIP_TRY(call.open(), "hipStreamWaitEvent");
+  HIP_TRY(stage(c->keys, txs, sizeof(cg_tx) * n_tx, s), "H2D txs");
+  HIP_TRY(stage(c->items, comps, sizeof(cg_component) * n_comps, s), "H2D comps");
+  HIP_TRY(stage(c->arena, arena, arena_len, s, arena_room(arena_len)), "H2D arena");
+  const uint64_t vis_b = al256(n_comps ? n_comps : 1);
+  HIP_TRY(c->bfin.ensure(vis_b + build_fixed_bytes(n_tx)), "hipMalloc(build inputs)");
+  if (n_comps) HIP_TRY(hipMemcpyAsync(c->bfin.p, visible, n_comps, hipMemcpyHostToDevice, s), "H2D visible");
+  HIP_TRY(c->aux2.ensure(cg::tx_ws_bytes(n_comps)), "hipMalloc(leaf ws)");
+  HIP_TRY(c->bfws.ensure(cg::build_ws_bytes(n_tx, n_comps)), "hipMalloc(build ws)");
+  const cg::BuildTxIn in{(const cg_tx*)c->keys.p, n_tx, (const cg_component*)c->items.p, n_comps,
+                         (const uint8_t*)c->arena.p, arena_len, (const uint8_t*)c->bfin.p};
+  cg::BuildOut d = h;
+  d.nodes = nullptr;
+  d.leaves = nullptr;
+  d.out = nullptr;
+  build_fixed_split((uint8_t*)c->bfin.p + vis_b, n_tx, &d);
+  HIP_TRY(cg::launch_build_filtered_count(in, d, (uint8_t*)c->aux2.p, (uint8_t*)c->bfws.p, s),
+          "launch_build_filtered_count");
+  if (const int rc = build_host_tables(c, fn, h, &d, s)) return rc;
+  HIP_TRY(cg::launch_build_filtered_emit(in, d, (uint8_t*)c->aux2.p, (uint8_t*)c->bfws.p, s),
+          "launch_build_filtered_emit");
+  if (const int rc = build_host_results(h, d, n_tx, s)) return rc;
+  HIP_TRY(call.close(), "hipEventRecord");
+  HIP_TRY(hipStreamSynchronize(s), "hipStreamSynchronize");
+  return CG_OK;
+}
+
+int cg_build_partial_trees_device(cg_ctx* c, const uint8_t* d_leaves, uint64_t n_leaf_hashes, const uint64_t* d_first,
+                                  const uint32_t* d_count, uint64_t n, uint64_t leaf_total, const uint8_t* d_include,
+                                  uint64_t n_inc_hashes, const uint64_t* d_inc_first, const uint32_t* d_inc_count,
+                                  uint64_t out_base, cg_filtered_tx* d_ftxs, cg_pmt_node* d_nodes, uint64_t node_cap,
+                                  cg_filtered_leaf* d_leaves_out, uint64_t leaf_cap, uint8_t* d_out, uint64_t out_cap,
+                                  uint8_t* d_status, cg_build_totals* d_totals, void* hip_stream) {
+  const char* fn = "cg_build_partial_trees_device";
+  if (!c) return fail(CG_ERR_ARG, "%s: ctx is NULL", fn);
+  const cg::BuildOut o{out_base, d_ftxs, d_nodes, node_cap, d_leaves_out, leaf_cap, d_out, out_cap, d_status, d_totals};
+  if (!d_totals) return fail(CG_ERR_ARG, "%s: NULL buffer", fn);
+  if (const int rc = build_out_args(fn, n, o, true)) return rc;
+  if (n && (!d_first || !d_count || !d_inc_first || !d_inc_count || (n_leaf_hashes && !d_leaves) ||
+            (n_inc_hashes && !d_include)))
+    return fail(CG_ERR_ARG, "%s: NULL buffer", fn);
+  if ((((uintptr_t)d_leaves | (uintptr_t)d_include) & 3) != 0)
+    return fail(CG_ERR_ARG, "%s: a hash table is not 4-byte aligned", fn);
+  const cg::BuildPtIn in{d_leaves, n_leaf_hashes, d_first, d_count, n, leaf_total, d_include, n_inc_hashes,
+                         d_inc_first, d_inc_count};
+  std::lock_guard<std::mutex> g(c->mu);
+  if (const int rc = enter(c, fn)) return rc;
+  HIP_TRY(ensure_all({{&c->bfws, cg::build_pt_ws_bytes(n, leaf_total)}}), "hipMalloc(build ws)");
+  Call call(c, Call::kDevice);
+  HIP_TRY(call.open(hip_stream), "hipStreamWaitEvent");
+  HIP_TRY(cg::launch_build_pt_count(in, o, (uint8_t*)c->bfws.p, call.stream()), "launch_build_pt_count");
+  HIP_TRY(cg::launch_build_pt_emit(in, o, (uint8_t*)c->bfws.p, call.stream()), "launch_build_pt_emit");
+  HIP_TRY(call.close(), "hipEventRecord");
+  return CG_OK;
+}
+
+int cg_build_partial_trees(cg_ctx* c, const uint8_t* leaves, const uint64_t* first, const uint32_t* count, uint64_t n,
+                           const uint8_t* include, const uint64_t* inc_first, const uint32_t* inc_count,
+                           uint64_t out_base, cg_filtered_tx* ftxs_out, cg_pmt_node* nodes_out, uint64_t node_cap,
+                           cg_filtered_leaf* leaves_out, uint64_t leaf_cap, uint8_t* out, uint64_t out_cap,
+                           uint8_t* status_out, cg_build_totals* totals_out) {
+  const char* fn = "cg_build_partial_trees";
+  if (!c) return fail(CG_ERR_ARG, "%s: ctx is NULL", fn);
+  cg::BuildOut h{out_base, ftxs_out, nodes_out, node_cap, leaves_out, leaf_cap, out, out_cap, status_out, totals_out};
+  if (!totals_out) return fail(CG_ERR_ARG, "%s: NULL buffer", fn);
+  if (const int rc = build_out_args(fn, n, h, false)) return rc;
+  if (n && (!first || !count || !inc_first || !inc_count)) return fail(CG_ERR_ARG, "%s: NULL buffer", fn);
+  memset(totals_out, 0, sizeof *totals_out);
+  if (n == 0) return CG_OK;
+  uint64_t n_leaf_hashes = 0, n_inc_hashes = 0, leaf_total = 0;
+  for (uint64_t j = 0; j < n; ++j) {
+    if (first[j] + count[j] > n_leaf_hashes) n_leaf_hashes = first[j] + count[j];
+    if (inc_first[j] + inc_count[j] > n_inc_hashes) n_inc_hashes = inc_first[j] + inc_count[j];
+    leaf_total += count[j];
+  }
+  if ((n_leaf_hashes && !leaves) || (n_inc_hashes && !include)) return fail(CG_ERR_ARG, "%s: NULL buffer", fn);
+  std::lock_guard<std::mutex> g(c->mu);
+  if (const int rc = enter(c, fn)) return rc;
+  hipStream_t s = c->stream;
+  Call call(c, Call::kHost);
+  HIP_TRY(call.open(), "hipStreamWaitEvent");
+  HIP_TRY(stage(c->arena, leaves, 32 * n_leaf_hashes, s), "H2D leaves");
+  HIP_TRY(stage(c->aux0, include, 32 * n_inc_hashes, s), "H2D include");
+  HIP_TRY(stage(c->keys, first, 8 * n, s), "H2D first");
+  HIP_TRY(stage(c->items, count, 4 * n, s), "H2D count");
+  HIP_TRY(stage(c->aux1, inc_first, 8 * n, s), "H2D inc_first");
+  HIP_TRY(stage(c->aux2, inc_count, 4 * n, s), "H2D inc_count");
+  HIP_TRY(c->bfin.ensure(build_fixed_bytes(n)), "hipMalloc(build results)");
+  HIP_TRY(c->bfws.ensure(cg::build_pt_ws_bytes(n, leaf_total)), "hipMalloc(build ws)");
+  const cg::BuildPtIn in{(const uint8_t*)c->arena.p, n_leaf_hashes, (const uint64_t*)c->keys.p,
+                         (const uint32_t*)c->items.p, n, leaf_total, (const uint8_t*)c->aux0.p, n_inc_hashes,
+                         (const uint64_t*)c->aux1.p, (const uint32_t*)c->aux2.p};
+  cg::BuildOut d = h;
+  d.nodes = nullptr;
+  d.leaves = nullptr;
+  d.out = nullptr;
+  build_fixed_split((uint8_t*)c->bfin.p, n, &d);
+  HIP_TRY(cg::launch_build_pt_count(in, d, (uint8_t*)c->bfws.p, s), "launch_build_pt_count");
+  if (const int rc = build_host_tables(c, fn, h, &d, s)) return rc;
+  HIP_TRY(cg::launch_build_pt_emit(in, d, (uint8_t*)c->bfws.p, s), "launch_build_pt_emit");
+  if (const int rc = build_host_results(h, d, n, s)) return rc;
   HIP_TRY(call.close(), "hipEventRecord");
   HIP_TRY(hipStreamSynchronize(s), "hipStreamSynchronize");
   return CG_OK;

@@ -427,7 +427,16 @@ hipError_t launch_sha512(const cg_span* d_spans, uint64_t n, const uint8_t* d_ar
 
 // WireTransaction ids: leaf hashing + per-tx Merkle levels. `d_leaf_ws` must hold
 // tx_ws_bytes(n_comps) bytes.
+// workspace sections start 256-aligned
+static inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 size_t tx_ws_bytes(uint64_t n_comps);
+// The workspace's component -> transaction map (0xffffffff: no transaction claims the component).
+uint32_t* tx_ws_map(uint8_t* d_leaf_ws, uint64_t n_comps);
+// launch_tx_ids without the roots: statuses and the leaf hashes, 8 big-endian words at
+// d_leaf_ws[32 * component] (build_filtered.hip walks them).
+hipError_t launch_tx_leaves(const cg_tx* d_txs, uint64_t n_tx, const cg_component* d_comps, uint64_t n_comps,
+                            const uint8_t* d_arena, uint64_t arena_len, uint8_t* d_status, uint8_t* d_leaf_ws,
+                            hipStream_t stream);
 hipError_t launch_tx_ids(const cg_tx* d_txs, uint64_t n_tx, const cg_component* d_comps, uint64_t n_comps,
                          const uint8_t* d_arena, uint64_t arena_len, uint8_t* d_ids, uint8_t* d_status,
                          uint8_t* d_leaf_ws, hipStream_t stream);
@@ -479,6 +488,53 @@ size_t ftx_ws_bytes(uint64_t n_leaves);
 hipError_t launch_filtered(const cg_filtered_tx* d_ftxs, uint64_t n_ftx, const cg_pmt_node* d_nodes, uint64_t n_nodes,
                            const cg_filtered_leaf* d_leaves, uint64_t n_leaves, const uint8_t* d_arena,
                            uint64_t arena_len, uint8_t* d_status, uint8_t* d_ws, hipStream_t stream);
+
+// Tear-off building (build_filtered.hip). Each form is two enqueues, so that a host form can read the
+// totals in between: count (the leaf stages, the count walk, the scan: d_totals is complete behind it)
+// and emit (the tables). BuildOut: the caller's tables and capacities. `d_ws` must hold
+// build_ws_bytes(n_tx, n_comps) resp. build_pt_ws_bytes(n, leaf_total) bytes, `d_leaf_ws`
+// tx_ws_bytes(n_comps).
+struct BuildOut {
+  uint64_t out_base;
+  cg_filtered_tx* ftxs;
+  cg_pmt_node* nodes;
+  uint64_t node_cap;
+  cg_filtered_leaf* leaves;
+  uint64_t leaf_cap;
+  uint8_t* out;
+  uint64_t out_cap;
+  uint8_t* status;
+  cg_build_totals* totals;
+};
+struct BuildTxIn {
+  const cg_tx* txs;
+  uint64_t n_tx;
+  const cg_component* comps;
+  uint64_t n_comps;
+  const uint8_t* arena;
+  uint64_t arena_len;
+  const uint8_t* visible;
+};
+struct BuildPtIn {
+  const uint8_t* leaves;
+  uint64_t n_leaf_hashes;
+  const uint64_t* first;
+  const uint32_t* count;
+  uint64_t n;
+  uint64_t leaf_total;
+  const uint8_t* include;
+  uint64_t n_inc_hashes;
+  const uint64_t* inc_first;
+  const uint32_t* inc_count;
+};
+size_t build_ws_bytes(uint64_t n_tx, uint64_t n_comps);
+hipError_t launch_build_filtered_count(const BuildTxIn& in, const BuildOut& o, uint8_t* d_leaf_ws, uint8_t* d_ws,
+                                       hipStream_t stream);
+hipError_t launch_build_filtered_emit(const BuildTxIn& in, const BuildOut& o, uint8_t* d_leaf_ws, uint8_t* d_ws,
+                                      hipStream_t stream);
+size_t build_pt_ws_bytes(uint64_t n, uint64_t leaf_total);
+hipError_t launch_build_pt_count(const BuildPtIn& in, const BuildOut& o, uint8_t* d_ws, hipStream_t stream);
+hipError_t launch_build_pt_emit(const BuildPtIn& in, const BuildOut& o, uint8_t* d_ws, hipStream_t stream);
 
 
 // Per-transaction verdicts (txverdict.hip). One call's tables and results, all on one side of the bus:

@@ -401,18 +401,20 @@ hipError_t launch_sha512(const cg_span* d_spans, uint64_t n, const uint8_t* d_ar
 }
 
 // workspace: [leaves 32 x n][map 4 x n][perm 4 x n][block class counts][ranges]
-static uint64_t al256(uint64_t x) { return (x + 255) & ~(uint64_t)255; }
 size_t tx_ws_bytes(uint64_t n_comps) {
   const uint64_t n = n_comps ? n_comps : 1;
   return al256(32 * n) + al256(4 * n) + al256(4 * n) + al256(4 * part_bcnt_words(TX_LEAF_CLASSES, n)) + 256;
 }
+uint32_t* tx_ws_map(uint8_t* d_ws, uint64_t n_comps) { return (uint32_t*)(d_ws + al256(32 * (n_comps ? n_comps : 1))); }
 
-hipError_t launch_tx_ids(const cg_tx* d_txs, uint64_t n_tx, const cg_component* d_comps, uint64_t n_comps,
-                         const uint8_t* d_arena, uint64_t arena_len, uint8_t* d_ids, uint8_t* d_status,
-                         uint8_t* d_ws, hipStream_t s) {
+// The stages both cg_tx_ids and cg_build_filtered start with: statuses 1 / 2 / 3 and every leaf hash
+// (big-endian words) at d_ws[32 * component].
+hipError_t launch_tx_leaves(const cg_tx* d_txs, uint64_t n_tx, const cg_component* d_comps, uint64_t n_comps,
+                            const uint8_t* d_arena, uint64_t arena_len, uint8_t* d_status, uint8_t* d_ws,
+                            hipStream_t s) {
   if (!n_tx) return hipSuccess;
   const uint64_t n = n_comps ? n_comps : 1;
-  uint32_t* map = (uint32_t*)(d_ws + al256(32 * n));
+  uint32_t* map = tx_ws_map(d_ws, n_comps);
   uint32_t* perm = map + al256(4 * n) / 4;
   uint32_t* bcnt = perm + al256(4 * n) / 4;
   uint32_t* ranges = bcnt + al256(4 * part_bcnt_words(TX_LEAF_CLASSES, n)) / 4;
@@ -429,6 +431,15 @@ hipError_t launch_tx_ids(const cg_tx* d_txs, uint64_t n_tx, const cg_component* 
     hipLaunchKernelGGL(k_tx_leaves, dim3(blocks(n_comps)), dim3(256), 0, s, d_txs, d_comps, (const uint32_t*)perm,
                        (const uint32_t*)ranges, (const uint32_t*)map, d_arena, arena_len, d_status, d_ws);
   }
+  return hipGetLastError();
+}
+
+hipError_t launch_tx_ids(const cg_tx* d_txs, uint64_t n_tx, const cg_component* d_comps, uint64_t n_comps,
+                         const uint8_t* d_arena, uint64_t arena_len, uint8_t* d_ids, uint8_t* d_status,
+                         uint8_t* d_ws, hipStream_t s) {
+  if (!n_tx) return hipSuccess;
+  const hipError_t e = launch_tx_leaves(d_txs, n_tx, d_comps, n_comps, d_arena, arena_len, d_status, d_ws, s);
+  if (e != hipSuccess) return e;
   hipLaunchKernelGGL(k_tx_roots, dim3(blocks(n_tx)), dim3(256), 0, s, d_txs, n_tx, d_ids, (const uint8_t*)d_status,
                      d_ws);
   return hipGetLastError();

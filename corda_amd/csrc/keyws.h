@@ -203,7 +203,6 @@ __device__ __forceinline__ int plan_class_of_curve(int curve) { return curve == 
 // and, per family, the full / row-0 builds' park (ed_row_build_parked / ec_row_build_parked): one
 // lane-interleaved region of min(n_keys x rows, TAB_PARK_LANES) lanes, the build kernels' grid
 // (each lane loops over the compacted (key, row) tasks), 5 120 B (Ed25519) / 4 608 B (ECDSA) a lane.
-static inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 #define TAB_PARK_LANES 131072u  // 2 waves per SIMD on 1024 SIMDs
 static inline uint32_t tab_park_lanes(uint32_t n_keys, uint32_t rows) {
   uint64_t l = (uint64_t)(n_keys ? n_keys : 1) * rows;

@@ -12,6 +12,7 @@ import numpy as np
 
 from . import _lib
 from .batch import COMPONENT_DTYPE, FLEAF_DTYPE, FTX_DTYPE, KEY_DTYPE, PMT_NODE_DTYPE, MODE_DOVERIFY, SPAN_DTYPE, TMPL_DTYPE, TX_DTYPE, TXSIG_DTYPE
+from .batch import BUILD_TOTALS_DTYPE
 from .batch import REQ_NODE_DTYPE, TX_CHECK_DTYPE, TX_VERDICT_DTYPE, TXSIG12_DTYPE
 from .batch import SIGN_ITEM_DTYPE, SIGN_REQ_DTYPE
 from .batch import DERIVE_PARENT_DTYPE, DERIVE_REQ_DTYPE
@@ -168,6 +169,11 @@ class Engine:
                                         _p(ids), _p(st)), "cg_tx_ids")
         return ids.reshape(-1, 32), st
 
+    def tx_ids_device(self, d_txs, n_tx, d_comps, n_comps, d_arena, arena_len, d_ids, d_status, stream=0):
+        """Asynchronous device form of tx_ids (every table already in HBM)."""
+        _lib.check(_lib.lib().cg_tx_ids_device(self._h, d_txs, n_tx, d_comps, n_comps, d_arena, arena_len, d_ids,
+                                               d_status, stream or None), "cg_tx_ids_device")
+
     def verify_filtered(self, ftxs, nodes, leaves, arena):
         """FilteredTransaction.verify / PartialMerkleTree.verify for packed tear-offs
         (FTX_DTYPE / PMT_NODE_DTYPE / FLEAF_DTYPE / arena, cg_verify_filtered). Returns the
@@ -184,6 +190,81 @@ class Engine:
         _lib.check(_lib.lib().cg_verify_filtered_device(self._h, d_ftxs, n_ftx, d_nodes, n_nodes, d_leaves, n_leaves,
                                                         d_arena, arena_len, d_status, stream or None),
                    "cg_verify_filtered_device")
+
+    @staticmethod
+    def _build_tables(n, node_cap, leaf_cap, slot_cap):
+        return (np.zeros(n, FTX_DTYPE), np.zeros(node_cap, PMT_NODE_DTYPE), np.zeros(leaf_cap, FLEAF_DTYPE),
+                np.zeros(32 * slot_cap, np.uint8), np.full(n, 255, np.uint8), np.zeros(1, BUILD_TOTALS_DTYPE))
+
+    @staticmethod
+    def _build_trim(ftxs, nodes, leaves, out, st, totals):
+        t = totals[0]
+        return (ftxs, nodes[:int(t["n_nodes"])], leaves[:int(t["n_leaves"])], out[:int(t["out_bytes"])], st, t)
+
+    def build_filtered(self, txs, comps, arena, visible, out_base=0):
+        """WireTransaction.buildFilteredTransaction for packed transactions (cg_build_filtered): ``visible`` is one
+        byte per component. Returns (ftxs, nodes, leaves, out, status, totals): the tables of verify_filtered,
+        whose offsets into ``out`` have ``out_base`` added; status 0 built, 1 / 2 / 3 as tx_ids, 6 a visible
+        byte that is not 0 or 1 or a visible privacy salt."""
+        assert txs.dtype == TX_DTYPE and comps.dtype == COMPONENT_DTYPE
+        visible = np.ascontiguousarray(visible, np.uint8)
+        assert visible.size == len(comps)
+        nc = len(comps)
+        t = self._build_tables(len(txs), 4 * nc, nc, len(txs) + 3 * nc)
+        ftxs, nodes, leaves, out, st, totals = t
+        _lib.check(_lib.lib().cg_build_filtered(self._h, _p(txs), len(txs), _p(comps), nc, _p(arena), arena.size,
+                                                _p(visible), out_base, _p(ftxs), _p(nodes), len(nodes), _p(leaves),
+                                                len(leaves), _p(out), out.size, _p(st), _p(totals)),
+                   "cg_build_filtered")
+        return self._build_trim(*t)
+
+    def build_filtered_device(self, d_txs, n_tx, d_comps, n_comps, d_arena, arena_len, d_visible, out_base, d_ftxs,
+                              d_nodes, node_cap, d_leaves, leaf_cap, d_out, out_cap, d_status, d_totals, stream=0):
+        """Asynchronous device form of build_filtered (every table already in HBM; d_totals: a
+        BUILD_TOTALS_DTYPE record, ``over`` set where a capacity was too small)."""
+        _lib.check(_lib.lib().cg_build_filtered_device(self._h, d_txs, n_tx, d_comps, n_comps, d_arena, arena_len,
+                                                       d_visible, out_base, d_ftxs, d_nodes, node_cap, d_leaves,
+                                                       leaf_cap, d_out, out_cap, d_status, d_totals, stream or None),
+                   "cg_build_filtered_device")
+
+    @staticmethod
+    def _hash_lists(lists):
+        first = np.zeros(len(lists), np.uint64)
+        count = np.zeros(len(lists), np.uint32)
+        flat = []
+        for j, lv in enumerate(lists):
+            first[j], count[j] = len(flat), len(lv)
+            flat.extend(bytes(x) for x in lv)
+        if any(len(x) != 32 for x in flat):
+            raise ValueError("a SHA-256 hash is 32 bytes")
+        return np.frombuffer(b"".join(flat) + bytes(32), np.uint8).copy(), first, count
+
+    def build_partial_trees(self, leaf_lists, include_lists, out_base=0):
+        """PartialMerkleTree.build(tree, includeHashes) for each (leaf list, include list) pair
+        (cg_build_partial_trees). Returns the tables of build_filtered; status 0 built, 1 no leaves, 4 a zero
+        hash in the include list, 5 the included leaves are not the include list."""
+        assert len(leaf_lists) == len(include_lists)
+        leaves, first, count = self._hash_lists(leaf_lists)
+        include, inc_first, inc_count = self._hash_lists(include_lists)
+        n, nl, ni = len(leaf_lists), int(count.sum()), int(inc_count.sum())
+        t = self._build_tables(n, 4 * nl, ni, n + ni + 2 * nl)
+        ftxs, nodes, lrec, out, st, totals = t
+        _lib.check(_lib.lib().cg_build_partial_trees(self._h, _p(leaves), _p(first), _p(count), n, _p(include),
+                                                     _p(inc_first), _p(inc_count), out_base, _p(ftxs), _p(nodes),
+                                                     len(nodes), _p(lrec), len(lrec), _p(out), out.size, _p(st),
+                                                     _p(totals)), "cg_build_partial_trees")
+        return self._build_trim(*t)
+
+    def build_partial_trees_device(self, d_leaves, n_leaf_hashes, d_first, d_count, n, leaf_total, d_include,
+                                   n_inc_hashes, d_inc_first, d_inc_count, out_base, d_ftxs, d_nodes, node_cap,
+                                   d_leaves_out, leaf_cap, d_out, out_cap, d_status, d_totals, stream=0):
+        """Asynchronous device form of build_partial_trees."""
+        _lib.check(_lib.lib().cg_build_partial_trees_device(self._h, d_leaves, n_leaf_hashes, d_first, d_count, n,
+                                                            leaf_total, d_include, n_inc_hashes, d_inc_first,
+                                                            d_inc_count, out_base, d_ftxs, d_nodes, node_cap,
+                                                            d_leaves_out, leaf_cap, d_out, out_cap, d_status,
+                                                            d_totals, stream or None),
+                   "cg_build_partial_trees_device")
 
     # ------------------------------------------------------------------ transactions
     def verify_transactions(self, txs, comps, keys, sigs, tmpls, arena, mode=MODE_DOVERIFY):

@@ -621,6 +621,15 @@ class WireTransaction:
         return WireTransactionData(components=[serialize(c) for c in self.available_components()],
                                    salt=self.privacy_salt.bytes_, salt_blob=serialize(self.privacy_salt))
 
+    def build_filtered_transaction(self, predicate, engine=None):
+        """WireTransaction.buildFilteredTransaction(Predicate) (WireTransaction.kt:97-167): the predicate runs
+        on the host over available_components(), the tear-off is built on the GPU (cg_build_filtered)."""
+        from .transactions import build_filtered_transactions
+        res = build_filtered_transactions([self], predicate, engine)[0]
+        if isinstance(res, Exception):
+            raise res
+        return res
+
 
 # ------------------------------------------------------------------ X.500 names (BC X500Name)
 _X500_OIDS = {"CN": "2.5.4.3", "O": "2.5.4.10", "OU": "2.5.4.11", "L": "2.5.4.7", "C": "2.5.4.6", "ST": "2.5.4.8"}

@@ -14,8 +14,8 @@ module only packs them.
 """
 import numpy as np
 
-from .batch import (COMPONENT_DTYPE, FLEAF_DTYPE, FLEAF_HASH, FTX_DTYPE, FTX_FILTERED, PMT_INCLUDED, PMT_LEAF,
-                    PMT_NODE, PMT_NODE_DTYPE, TX_DTYPE)
+from .batch import (BUILD_BAD_VISIBLE, BUILD_NOT_IN_TREE, BUILD_ZERO_HASH, COMPONENT_DTYPE, FLEAF_DTYPE, FLEAF_HASH,
+                    FTX_DTYPE, FTX_FILTERED, PMT_INCLUDED, PMT_LEAF, PMT_NODE, PMT_NODE_DTYPE, TX_DTYPE)
 from .crypto import Crypto
 
 
@@ -166,6 +166,39 @@ class PartialMerkleTree:
             raise MerkleTreeException("Some of the provided hashes are not in the tree.")
         return PartialMerkleTree(tree)
 
+    @staticmethod
+    def from_postorder(stream):
+        """The inverse of postorder(): [(kind, hash | None)] -> PartialMerkleTree (ValueError on a stream that
+        does not reduce to one tree)."""
+        stk = []
+        for kind, h in stream:
+            if kind == PMT_NODE:
+                if len(stk) < 2:
+                    raise ValueError("node without two children")
+                right = stk.pop()
+                stk.append(Node(stk.pop(), right))
+            elif kind in (PMT_LEAF, PMT_INCLUDED):
+                stk.append((IncludedLeaf if kind == PMT_INCLUDED else Leaf)(h))
+            else:
+                raise ValueError("unknown node kind")
+        if len(stk) != 1:
+            raise ValueError("stream does not reduce to one root")
+        return PartialMerkleTree(stk[0])
+
+    @staticmethod
+    def build_batch(leaf_lists, include_lists, engine=None):
+        """PartialMerkleTree.build for each (leaf hashes, include hashes) pair in one GPU call
+        (cg_build_partial_trees): per pair ``(root hash, PartialMerkleTree)``, or the exception the serial
+        build raises."""
+        if not leaf_lists:
+            return []
+        ftxs, nodes, _, out, st, _ = (engine or Crypto.engine()).build_partial_trees(leaf_lists, include_lists)
+        res = []
+        for j, f in enumerate(ftxs):
+            e = build_status_exception(st[j])
+            res.append(e if e is not None else (_slot(out, f["root_off"]), _tree_of(f, nodes, out, 0)))
+        return res
+
     def postorder(self):
         """[(kind, hash | None)] in cg_pmt_node post-order (iterative: no recursion limit)."""
         out, stack = [], [(self.root, False)]
@@ -266,3 +299,77 @@ def verify_filtered_batch(ftxs, engine=None, filtered=True):
         return np.zeros(0, np.uint8)
     t, n, lv, arena = pack_filtered(ftxs, filtered)
     return (engine or Crypto.engine()).verify_filtered(t, n, lv, arena)
+
+
+# ---------------------------------------------------------------- building tear-offs
+def build_status_exception(st):
+    """The exception a status of cg_build_filtered / cg_build_partial_trees stands for (None: built)."""
+    st = int(st)
+    if st == 0:
+        return None
+    if st == 1:
+        return MerkleTreeException("Cannot calculate Merkle root on empty hash list.")
+    if st == BUILD_ZERO_HASH:
+        return ValueError("Zero hashes shouldn't be included in partial tree.")
+    if st == BUILD_NOT_IN_TREE:
+        return MerkleTreeException("Some of the provided hashes are not in the tree.")
+    if st == BUILD_BAD_VISIBLE:
+        return ValueError("The privacy salt cannot be a visible component, and a visible flag is 0 or 1.")
+    if st in (2, 3):
+        return ValueError(f"malformed transaction tables (status {st})")
+    return RuntimeError(f"tear-off not built (status {st})")
+
+
+def _slot(out, off, out_base=0):
+    o = int(off) - out_base
+    return out[o:o + 32].tobytes()
+
+
+def _tree_of(f, nodes, out, out_base):
+    rows = nodes[int(f["first_node"]):int(f["first_node"]) + int(f["n_nodes"])]
+    return PartialMerkleTree.from_postorder(
+        [(int(r["kind"]), None if r["kind"] == PMT_NODE else _slot(out, r["hash_off"], out_base)) for r in rows])
+
+
+def pack_visible(txs, visible_masks):
+    """The ``visible`` bytes of cg_build_filtered for transactions in the pack_transactions form: one mask per
+    transaction over its components (the salt leaf, packed last, is hidden; a mask may name it explicitly)."""
+    vis = []
+    for (blobs, _, _), mask in zip(txs, visible_masks):
+        mask = [int(v) for v in mask]
+        if len(mask) == len(blobs):
+            mask.append(0)
+        if len(mask) != len(blobs) + 1:
+            raise ValueError("one visible flag per component")
+        vis.extend(mask)
+    return np.array(vis, np.uint8)
+
+
+def unpack_built(tables, arena, out_base=0):
+    """FilteredTransactions (or the exception a status stands for) from the tables of Engine.build_filtered."""
+    ftxs, nodes, leaves, out, st, _ = tables
+    res = []
+    for t, f in enumerate(ftxs):
+        e = build_status_exception(st[t])
+        if e is not None:
+            res.append(e)
+            continue
+        rows = leaves[int(f["first_leaf"]):int(f["first_leaf"]) + int(f["n_leaves"])]
+        blobs = [arena[int(r["off"]):int(r["off"]) + int(r["len"])].tobytes() for r in rows]
+        nonces = [_slot(out, r["nonce_off"], out_base) for r in rows]
+        res.append(FilteredTransaction(_slot(out, f["root_off"], out_base), blobs, nonces,
+                                       _tree_of(f, nodes, out, out_base)))
+    return res
+
+
+def build_filtered_batch(txs, visible_masks, engine=None):
+    """WireTransaction.buildFilteredTransaction for a batch, one GPU call (cg_build_filtered). ``txs``:
+    [(component_blobs, salt32, salt_blob)] as pack_transactions takes them; ``visible_masks``: per transaction
+    one flag per component. Returns per transaction a FilteredTransaction, or the exception its status
+    stands for."""
+    if len(txs) != len(visible_masks):
+        raise ValueError("one mask per transaction")
+    if not txs:
+        return []
+    t, c, arena = pack_transactions(txs)
+    return unpack_built((engine or Crypto.engine()).build_filtered(t, c, arena, pack_visible(txs, visible_masks)), arena)

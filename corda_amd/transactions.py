@@ -243,6 +243,20 @@ def verify_wire_transactions(stxs, crypto=Crypto):
     return out_ids, results
 
 
+def build_filtered_transactions(wtxs, predicate, engine=None):
+    """buildFilteredTransaction(predicate) for a batch of kryo.WireTransaction objects, one GPU call
+    (merkle.build_filtered_batch): NotaryFlow.Client's tear-off is ``lambda c: isinstance(c, (StateRef,
+    TimeWindow))``. The predicate runs on the host over available_components(), Kryo stays on the host.
+    Returns per transaction a merkle.FilteredTransaction, or the exception its status stands for."""
+    from .merkle import build_filtered_batch
+    txs, masks = [], []
+    for w in wtxs:
+        d = w.data()
+        txs.append((d.components, d.salt, d.salt_blob))
+        masks.append([1 if predicate(c) else 0 for c in w.available_components()])
+    return build_filtered_batch(txs, masks, engine)
+
+
 # ---------------------------------------------------------------------------------------------
 # Whole-chain resolution (SURVEY §8 f2): ResolveTransactionsFlow verifies every downloaded
 # dependency in topological order, one SignedTransaction.verify at a time, and each verify

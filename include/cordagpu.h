@@ -626,6 +626,89 @@ int cg_verify_filtered_device(cg_ctx* ctx, const cg_filtered_tx* d_ftxs, uint64_
                               uint64_t n_nodes, const cg_filtered_leaf* d_leaves, uint64_t n_leaves,
                               const uint8_t* d_arena, uint64_t arena_len, uint8_t* d_status, void* hip_stream);
 
+/* ---- Building tear-offs: WireTransaction.buildFilteredTransaction / PartialMerkleTree.build, the other
+ * side of cg_verify_filtered. Replaces, for a batch of transactions (NotaryFlow.Client before a
+ * non-validating notary, an oracle flow before Oracle.sign(ftx)), the serial
+ *   filteredLeaves = filterWithFun(pred)                 visible component i keeps computeNonce(privacySalt, i)
+ *                                                        = SHA256(salt32 || BE32(i)); the privacy salt is never
+ *                                                        part of FilteredLeaves (WireTransaction.kt:97-167)
+ *   rootHash = wtx.merkleTree.hash                       (MerkleTransaction.kt:159-166)
+ *   pmt = PartialMerkleTree.build(merkleTree, filteredLeaves.availableComponentHashes)
+ *                                                        (PartialMerkleTree.kt:66-123: a subtree without an
+ *                                                        included leaf is cut to Leaf(its hash); the zeroHash
+ *                                                        padding leaves are ordinary leaves of the full tree)
+ * A filter that matches nothing still builds (one Leaf(root)); the later verify() is what throws.
+ *
+ * cg_build_filtered takes the cg_tx / cg_component tables and the arena as cg_tx_ids does, plus
+ * visible[n_comps]: one byte per component, 0 hidden / 1 visible. It writes the tables cg_verify_filtered
+ * reads, dense and in transaction order:
+ *   ftxs_out[n_tx]   flags = CG_FTX_FILTERED, first_node / n_nodes / first_leaf / n_leaves, root_off
+ *   nodes_out[]      the partial tree in cg_pmt_node post-order (NODE: hash_off 0)
+ *   leaves_out[]     one record per visible component: off / len copied from the component (they still
+ *                    point into the input arena), nonce_off into the output region, flags 0
+ *   out[]            32-byte slots, per transaction: the root (the transaction id), the nonce of each
+ *                    visible component in order, the hash of each LEAF / INCLUDED node in stream order
+ * Every offset written into the tables that points into out[] is out_base + its byte position in out[]:
+ * a caller that places out[] at arena[out_base ...) of one allocation passes everything to
+ * cg_verify_filtered unchanged. out must be 16-byte aligned (the device form's d_out; out_base itself is
+ * only a number).
+ * Inclusion is by component index, the JVM's is by hash value; here they are the same rule: every
+ * non-salt leaf of one transaction is hashed with the nonce of its own index, so two leaves of a tree
+ * have equal hashes only by a SHA-256 collision, the salt leaf cannot be visible and no leaf is zeroHash.
+ * Capacities (rows of nodes_out / leaves_out, bytes of out) come from the caller. Always enough, for a
+ * transaction of n components padded to P = 2^k leaves: nodes <= 2P - 1 < 4n, LEAF + INCLUDED nodes
+ * <= P < 2n, so node_cap = 4 n_comps, leaf_cap = n_comps, out_cap = 32 (n_tx + 3 n_comps).
+ * totals_out: what the call needed. A capacity below it: the host form fails with CG_ERR_ARG, the needed
+ * totals in cg_last_error and in totals_out, and writes no table; the device form (nothing syncs with the
+ * host) sets totals.over = 1 and writes no row or slot at or past a capacity (ftxs and status are
+ * complete, the other tables are not).
+ * status_out per transaction: 0 built; 1 / 2 / 3 as cg_tx_ids (1 also: more than 2^30 components);
+ * 6 a visible byte other than 0 or 1, or a visible privacy-salt component (FilteredLeaves cannot hold
+ * one). A transaction that failed gets one zeroed root slot, n_nodes = 0 and n_leaves = 0.
+ *
+ * cg_build_partial_trees is bare PartialMerkleTree.build(tree, includeHashes): leaf-hash lists as
+ * cg_merkle_roots takes them, plus one include list per tree, include[32 * inc_first[j] ..
+ * 32 * (inc_first[j] + inc_count[j])). Inclusion is by value, as in the JVM. Same output tables; the leaf
+ * records are CG_FLEAF_HASH and point at copies of the include hashes in out[] (slot order per
+ * tree: root, include hashes, node hashes); ftx flags = 0, so the result is the input of bare
+ * PartialMerkleTree.verify. Lists may share leaves. status per tree: 0 built; 1 an empty leaf list, more
+ * than 2^30 leaves, or (device form) a list outside its table; 4 zeroHash in the include list
+ * (IllegalArgumentException "Zero hashes shouldn't be included in partial tree."); 5 the number of
+ * included leaves differs from inc_count (MerkleTreeException "Some of the provided hashes are not in
+ * the tree.": a duplicate in the list, a hash the tree lacks, or an included hash that also sits at
+ * another leaf). The device form's tables are 4-byte aligned; leaf_total is the sum of count[] (or any
+ * upper bound of it: the size of the per-leaf scratch). */
+typedef struct cg_build_totals {
+  uint64_t n_nodes;    /* cg_pmt_node rows */
+  uint64_t n_leaves;   /* cg_filtered_leaf rows */
+  uint64_t out_bytes;  /* bytes of out[] */
+  uint32_t over;       /* 1: a capacity is below what the call needed */
+  uint32_t reserved;
+} cg_build_totals;     /* 32 bytes */
+
+int cg_build_filtered(cg_ctx* ctx, const cg_tx* txs, uint64_t n_tx, const cg_component* comps, uint64_t n_comps,
+                      const uint8_t* arena, uint64_t arena_len, const uint8_t* visible, uint64_t out_base,
+                      cg_filtered_tx* ftxs_out, cg_pmt_node* nodes_out, uint64_t node_cap,
+                      cg_filtered_leaf* leaves_out, uint64_t leaf_cap, uint8_t* out, uint64_t out_cap,
+                      uint8_t* status_out, cg_build_totals* totals_out);
+int cg_build_filtered_device(cg_ctx* ctx, const cg_tx* d_txs, uint64_t n_tx, const cg_component* d_comps,
+                             uint64_t n_comps, const uint8_t* d_arena, uint64_t arena_len, const uint8_t* d_visible,
+                             uint64_t out_base, cg_filtered_tx* d_ftxs, cg_pmt_node* d_nodes, uint64_t node_cap,
+                             cg_filtered_leaf* d_leaves, uint64_t leaf_cap, uint8_t* d_out, uint64_t out_cap,
+                             uint8_t* d_status, cg_build_totals* d_totals, void* hip_stream);
+int cg_build_partial_trees(cg_ctx* ctx, const uint8_t* leaves, const uint64_t* first, const uint32_t* count,
+                           uint64_t n, const uint8_t* include, const uint64_t* inc_first, const uint32_t* inc_count,
+                           uint64_t out_base, cg_filtered_tx* ftxs_out, cg_pmt_node* nodes_out, uint64_t node_cap,
+                           cg_filtered_leaf* leaves_out, uint64_t leaf_cap, uint8_t* out, uint64_t out_cap,
+                           uint8_t* status_out, cg_build_totals* totals_out);
+int cg_build_partial_trees_device(cg_ctx* ctx, const uint8_t* d_leaves, uint64_t n_leaf_hashes,
+                                  const uint64_t* d_first, const uint32_t* d_count, uint64_t n,
+                                  uint64_t leaf_total, const uint8_t* d_include, uint64_t n_inc_hashes,
+                                  const uint64_t* d_inc_first, const uint32_t* d_inc_count, uint64_t out_base,
+                                  cg_filtered_tx* d_ftxs, cg_pmt_node* d_nodes, uint64_t node_cap,
+                                  cg_filtered_leaf* d_leaves_out, uint64_t leaf_cap, uint8_t* d_out,
+                                  uint64_t out_cap, uint8_t* d_status, cg_build_totals* d_totals, void* hip_stream);
+
 /* ---- Ed25519 signing: the batch form of Crypto.doSign for EDDSA_ED25519_SHA512, the notary's own
  * step after it has checked a transaction's signatures:
  *   NotaryService.sign(txId)   core/.../node/services/NotaryService.kt:77-80
