@@ -155,6 +155,54 @@ def bare_cases():
     return out
 
 
+def prefix_tables(want, n):
+    """The oracle's tables for the first n transactions (or trees) of a batch: the tables are dense and in
+    order, so this is a cut at transaction n's first_node / first_leaf / root_off (out_base 0)."""
+    ftxs, nodes, leaves, out, st, totals = want
+    if n == len(ftxs):
+        return want
+    f = ftxs[n]
+    cut = (int(f["first_node"]), int(f["first_leaf"]), int(f["root_off"]))
+    t = np.zeros(1, B.BUILD_TOTALS_DTYPE)[0]
+    t["n_nodes"], t["n_leaves"], t["out_bytes"] = cut
+    return ftxs[:n], nodes[:cut[0]], leaves[:cut[1]], out[:cut[2]], st[:n], t
+
+
+def row_counts(want):
+    """Per transaction (or tree) the three counts k_bf_scan scans: node rows, leaf rows, 32-byte slots."""
+    ftxs, _, _, out, _, _ = want
+    ends = np.append(ftxs["root_off"][1:], out.size).astype(np.int64)
+    return (ftxs["n_nodes"].astype(np.int64), ftxs["n_leaves"].astype(np.int64),
+            (ends - ftxs["root_off"].astype(np.int64)) // 32)
+
+
+DEEP_COUNTS = (31, 32, 33, 255, 256, 257, 1025, 4097)   # 33, 257, 1025, 4097: P / 2 + 1
+DEEP_MASKS = ("none", "first", "last", "split", "alternate", "p01", "p50", "all")
+
+
+def deep_masks(n, m=None):
+    """{name: mask over n leaves} of which only the first m (default: all) may be included: nothing, the first
+    leaf, the last includable leaf, both sides of the top split (leaves P/2 - 1 and P/2), every other leaf,
+    seeded random at density 0.01 and 0.5, all."""
+    m = n if m is None else m
+    p = 1
+    while p < n:
+        p <<= 1
+    rng = np.random.default_rng(1000 + n)
+    sets = {"none": [], "first": [0], "last": [m - 1], "split": [p // 2 - 1, p // 2], "alternate": range(0, n, 2),
+            "p01": np.flatnonzero(rng.random(n) < 0.01), "p50": np.flatnonzero(rng.random(n) < 0.5),
+            "all": range(n)}
+    assert tuple(sets) == DEEP_MASKS
+    out = {}
+    for name, idx in sets.items():
+        mask = [0] * n
+        for i in idx:
+            if i < m:
+                mask[int(i)] = 1
+        out[name] = mask
+    return out
+
+
 def wire_transaction():
     """The WireTransaction of tests/test_kryo.py (test_wire_transaction_id_from_encoded_components)."""
     h = K.SecureHash(hashlib.sha256(b"prev").digest())

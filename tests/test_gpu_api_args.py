@@ -1,5 +1,5 @@
-"""Every argument refusal of the verify, transactions, tx-signature and verdict entry points (the
-cg_pool_* twins included), in the order the library checks them: the return code is CG_ERR_ARG and
+"""Every argument refusal of the verify, transactions, tx-signature, verdict and tear-off building entry
+points (the cg_pool_* twins included), in the order the library checks them: the return code is CG_ERR_ARG and
 cg_last_error gives the exact text. The table was written down from the checks in
 corda_amd/csrc/cordagpu.cpp, entry point by entry point in source order; a call with two faults at
 once pins which check comes first (a device form has no check of the key table, so there the mode
@@ -53,6 +53,21 @@ TXV_ALL = [({"stride": 16}, STRIDE), ({"sigs": None}, TXV_SIG), ({"status": None
            ({"keys": None}, "keys is NULL")] + TXV_TABLES
 BAD_CHECKS = ({"checks": "reserved"}, RESERVED)
 KEYS_AND_MODE = {"keys": None, "mode": 2}
+# tear-off building: the totals, the fixed-size results, the tables behind a non-zero capacity, the alignment a
+# device form asks for (ODD: the valid pointer plus one), then the inputs
+BUILD_OUT = "out_base ftxs node_rows node_cap leaves leaf_cap out out_cap status totals"
+BUILD_TX = "txs n_tx comps n_comps arena arena_len visible " + BUILD_OUT
+BUILD_PT = "leaf_hashes first count n include inc_first inc_count " + BUILD_OUT
+BUILD_PT_DEV = "leaf_hashes n_leaf_hashes first count n leaf_total include n_inc_hashes inc_first inc_count " + BUILD_OUT
+ODD = "the valid pointer plus one"
+BUILD_HEAD = [({k: None}, "NULL buffer") for k in ("totals", "ftxs", "status")] + \
+    [({k: None}, "NULL table") for k in ("node_rows", "leaves", "out")]
+BUILD_ALIGN = [({"out": ODD}, "out is not 16-byte aligned")]
+BUILD_TX_IN = [({k: None}, "NULL buffer") for k in ("txs", "comps", "visible")]
+BUILD_PT_IN = [({k: None}, "NULL buffer") for k in ("first", "count", "inc_first", "inc_count")]
+BUILD_PT_DEV_IN = BUILD_PT_IN + [({k: None}, "NULL buffer") for k in ("leaf_hashes", "include")] + \
+    [({k: ODD}, "a hash table is not 4-byte aligned") for k in ("leaf_hashes", "include")]
+TABLE_FIRST = ({"out": None, "first": None, "txs": None}, "NULL table")
 
 # entry point -> (its arguments after the handle, what follows them, the refusals in order, the two-fault call)
 ENTRIES = {
@@ -83,10 +98,16 @@ ENTRIES = {
     "cg_pool_verify_required_signatures_packed": (
         REQ, "stats", [({"sigs": None}, TXV_SIG), ({"keys": None}, "keys is NULL")] + TXV_TABLES + [BAD_CHECKS]
         + [(bad, (INNER, text)) for bad, text in TXSIG_HEAD[1:] + STREAM_HOST], (KEYS_AND_MODE, "keys is NULL")),
+    "cg_build_filtered_device": (BUILD_TX, "hip", BUILD_HEAD + BUILD_ALIGN + BUILD_TX_IN, TABLE_FIRST),
+    "cg_build_filtered": (BUILD_TX, "", BUILD_HEAD + BUILD_TX_IN + [({"arena": None}, "NULL buffer")], TABLE_FIRST),
+    "cg_build_partial_trees_device": (BUILD_PT_DEV, "hip", BUILD_HEAD + BUILD_ALIGN + BUILD_PT_DEV_IN, TABLE_FIRST),
+    "cg_build_partial_trees": (BUILD_PT, "", BUILD_HEAD + BUILD_PT_IN, TABLE_FIRST),
 }
 COUNTS = dict(n_keys=1, n_items=1, n_tx=1, n_comps=1, n_sigs=1, n_tmpls=1, n_ids=1, n_reqs=1, n_nodes=1, arena_len=64,
-              mode=0, stride=12)
-RESULTS = ("status", "ids", "tx_status", "sig_status", "verdicts", "req_status")
+              mode=0, stride=12, out_base=0, node_cap=1, leaf_cap=1, out_cap=32, n=1, leaf_total=1, n_leaf_hashes=1,
+              n_inc_hashes=1)
+RESULTS = ("status", "ids", "tx_status", "sig_status", "verdicts", "req_status", "ftxs", "node_rows", "leaves", "out",
+           "totals")
 
 
 def test_every_refusal_in_order(engine):
@@ -121,7 +142,7 @@ def test_every_refusal_in_order(engine):
             handle = pool._h if name.startswith("cg_pool_") else engine._h
 
             def call(bad, h=handle):
-                a = dict(good, **bad)
+                a = dict(good, **{k: good[k] + 1 if v is ODD else v for k, v in bad.items() if k in good})
                 if a.get("checks") == "reserved":
                     a["checks"] = reserved.ctypes.data
                 return getattr(L, name)(h, *[a[k] for k in params.split()], *([None] if tail else []))

@@ -2,8 +2,10 @@
 inclusion rule that build_filtered.hip's lanes run, tests/native/pmt_build_test.cpp) against
 oracle.corda: partial_tree_postorder(partial_tree_build(merkle_tree(h), incl)) and merkle_root. Every mask
 at every leaf count 1..9 (P = 1, 2, 4, 8, 16; padding blocks of 1, 2, 4 and 1 + 2 + 4 leaves), seeded
-random masks at 16, 17, 33 and 100 leaves, and the rules of the bare form; the same cases once more
-through the program built with -fsanitize=address,undefined."""
+random masks at 16, 17, 33 and 100 leaves, the deep trees of build_filtered_ref.deep_masks (31 .. 4097 leaves,
+levels 5 .. 13: the stack above level 7, the largest hidden blocks, the zeroHash padding of P / 2 - 1 leaves as
+hidden blocks of every size), and the rules of the bare form; the same cases once more through the program
+built with -fsanitize=address,undefined."""
 import os
 import struct
 import subprocess
@@ -11,7 +13,7 @@ import subprocess
 import numpy as np
 import pytest
 
-from build_filtered_ref import bare_cases, leaf_hashes
+from build_filtered_ref import DEEP_COUNTS, DEEP_MASKS, bare_cases, deep_masks, leaf_hashes
 from oracle import corda as O
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -28,8 +30,17 @@ def build_program(out, flags):
     return out
 
 
+def deep_cases():
+    """(leaves, mask) for every mask of deep_masks at every leaf count of DEEP_COUNTS, count-major."""
+    out = []
+    for n in DEEP_COUNTS:
+        hs = leaf_hashes(n, n)
+        out += [(hs, mask) for mask in deep_masks(n).values()]
+    return out
+
+
 def mask_cases():
-    """(leaves, mask) for every mask at n = 1..9 and seeded random masks at n = 16, 17, 33, 100."""
+    """(leaves, mask) for every mask at n = 1..9, seeded random masks at n = 16, 17, 33, 100, and the deep trees."""
     out = []
     for n in range(1, 10):
         hs = leaf_hashes(n, n)
@@ -43,7 +54,7 @@ def mask_cases():
                 out.append((hs, [int(x) for x in rng.random(n) < density]))
         out.append((hs, [0] * (n - 1) + [1]))
         out.append((hs, [1] + [0] * (n - 1)))
-    return out
+    return out + deep_cases()
 
 
 def to_file(cases, path):
@@ -112,7 +123,21 @@ def program():
 
 def test_every_mask_up_to_nine_leaves_and_random_masks(program, tmp_path):
     cases = [(hs, m, True) for hs, m in mask_cases()]
-    assert len(cases) == sum(1 << n for n in range(1, 10)) + 4 * 32
+    n_deep = len(DEEP_COUNTS) * len(DEEP_MASKS)
+    assert len(cases) == sum(1 << n for n in range(1, 10)) + 4 * 32 + n_deep
+    # what the deep cases are there for, as the oracle sees them: at P / 2 + 1 leaves with only the last one
+    # included, the left half is one hidden block of level top - 1 and the padding is one hidden block of every
+    # level below that; with everything included the padding alone is cut
+    deep = {(len(hs), name): (hs, m) for (hs, m, _), name in zip(cases[-n_deep:], DEEP_MASKS * len(DEEP_COUNTS))}
+    assert max(DEEP_COUNTS) > 1 << 12 and {33, 257, 1025, 4097} <= set(DEEP_COUNTS)
+    for n in (33, 257, 1025, 4097):
+        top = (n - 2).bit_length() + 1
+        assert 1 << top == 2 * (n - 1) and deep[n, "last"][1] == [0] * (n - 1) + [1] and sum(deep[n, "first"][1]) == 1
+        kinds = [k for k, _ in expected(*deep[n, "last"], True)[1]]
+        assert kinds == [1, 2] + [1, 0] * (top - 1) + [0]
+        assert sum(deep[n, "split"][1]) == 2 and deep[n, "split"][1][n - 2:] == [1, 1]
+        kinds = [k for k, _ in expected(*deep[n, "all"], True)[1]]
+        assert kinds.count(2) == n and kinds.count(1) == top - 1
     assert check(cases, program, tmp_path) == {0}
 
 
